@@ -10,15 +10,17 @@ each proof = static-R1CS evaluation, 7 NTTs of 2^17, 4 G1 MSMs + 1 G2 MSM, assem
 witnesses with fresh blinding scalars (r, s), so every timed proof is different.  MASP_BENCH_CIRCUIT=output|convert|mixed
 selects the other workloads (mixed = configs[4]'s job mix: 512 jobs per GPU and step, job j of circuit j mod 3).
 
-Two timed regions, K steps each, bracketed by barrier + device synchronisation, max over ranks:
+A plain run sets up, warms up, times the K steps of `value` and prints the line (contract keys, config, library hash);
+`--dump-outputs DIR` also writes the proofs of the last timed step to DIR/proofs.npy.  Everything else runs only with `--full`
+(marked below).  Two timed regions, K steps each, bracketed by barrier + device synchronisation, max over ranks:
   `value`     BASELINE.md §4's region: witnesses in page-locked HOST memory -> proofs on the host of rank 0, through
               masp_hip_prove_batch (H2D of 3.2 MB per Spend, D2H of the proofs and the RCCL gather of N*K*256*192 bytes inside)
-  `resident`  witnesses already resident in HBM -> proofs on the host (what rounds 1-2 reported as `value`; 2 % faster)
-plus `end_to_end`: LocalTxProver.prove_batch over 1 024 Spend descriptions per GPU — witness synthesis on the host cores, H2D,
+  `resident`  (--full) witnesses already resident in HBM -> proofs on the host (what rounds 1-2 reported as `value`; 2 % faster)
+plus, with --full, `end_to_end`: LocalTxProver.prove_batch over 1 024 Spend descriptions per GPU — witness synthesis on the host cores, H2D,
 proving and the GPU batch self-verification (not part of `value`: the metric starts from witnesses).
 The library reads no environment; this script translates MASP_HIP_SLOTS / MASP_HIP_BATCH / MASP_HIP_NTT_SUB /
 MASP_HIP_MSM_C_{H,LA,B,B2_LONE} into masp_hip_options (A/B runs of the tools).
-After timing, EVERY timed proof is checked with the product's Groth16 batch verifier (pairing equation; no oracle involved)
+With --full, after timing, EVERY timed proof is checked with the product's Groth16 batch verifier (pairing equation; no oracle involved)
 and a sample is compared byte for byte with the oracle's toxic-waste closed form; the line carries `verified`.
 Ranks shard the proofs with no data-path collective (weak scaling).  Prints ONE JSON line on rank 0.
 """
@@ -142,6 +144,13 @@ def library_sha16():
         return None
 
 
+def dump_outputs(directory, proofs):
+    """--dump-outputs: the proofs of the last timed step, (proofs, 192) bytes as float32 (exact for 0 .. 255), so that two builds run with
+    the same arguments — same instances, same blinding scalars — can be compared output for output."""
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "proofs.npy"), np.ascontiguousarray(proofs, dtype=np.uint8).reshape(-1, 192).astype(np.float32))
+
+
 def relaunch_under_torchrun(args):
     """`python bench.py --gpus N` with N > 1 and no launcher: become N ranks (one per GPU) under torch.distributed.run."""
     with socket.socket() as s:
@@ -226,6 +235,8 @@ def main_in_library(args):
     assert len(set(p.tobytes() for p in out.reshape(-1, 192))) == K * N * n
     vk.close()
     ctx.close()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out[K - 1])
     print(json.dumps({"metric": "Spend proofs/sec", "value": K * N * n / elapsed, "unit": "proofs/s", "n_gpus": N, "steps": K, "warmup": Wm,
                       "ms_per_step": elapsed * 1e3 / K, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
                       "launcher": "in-library: one process, masp_hip_ctx_create_ex over %d device(s), no torch / RCCL" % N,
@@ -241,7 +252,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8, help="timed steps; one step = one batch of 256 distinct proofs per GPU")
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the `resident` region, verification of every timed proof, the oracle's closed "
+                         "form, the CPU baseline, roofline / clock figures, lone-proof latencies, end_to_end and the other circuits")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the proofs of the last timed step to DIR/proofs.npy (float32, one byte per element)")
     ap.add_argument("--in-library", action="store_true", help="one process over all --gpus devices through masp_hip_ctx_create_ex (no torch, no RCCL)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / process-group / gather path only, no GPU work, no figure (CPU test hook)")
     args = ap.parse_args()
@@ -329,6 +344,7 @@ def main():
     kinds = list(KINDS) if WORKLOAD == "mixed" else [WORKLOAD]
     n = PROOFS_PER_STEP[WORKLOAD]
     K, Wm = args.steps, args.warmup
+    FULL = args.full            # a plain run: set-up, warm-up, the K steps of `value`, the line; the rest only with --full
     # ---- circuits: the real MASP R1CS (structure hashes pinned to the reference's KATs) + CRS from known toxic waste, same on every rank
     # (N ranks: rank 0 generates each CRS, the others receive the same bytes over the process group instead of running the
     # set-up kernels eight times side by side)
@@ -339,7 +355,8 @@ def main():
         mine = ctx.generate_parameters(cs[kind], synthetic.toxic_waste(1 + KINDS.index(kind))) if rank == 0 else None
         params[kind] = D.broadcast_bytes(mine, dist, dev)
         ctx.load_circuit(KINDS.index(kind), params[kind], cs[kind])
-        vk[kind] = ctx.prepare_verifying_key(params[kind])      # Groth16 batch verifier, Miller loops on the GPU (product code)
+        if FULL:
+            vk[kind] = ctx.prepare_verifying_key(params[kind])      # Groth16 batch verifier, Miller loops on the GPU (product code)
     setup_s = time.perf_counter() - t_setup
     sys.stderr.write("bench.py: rank %d: CRS %s + window tables in %.1f s\n" % (rank, "generated" if rank == 0 else "received", setup_s))
     # ---- n distinct instances per rank, synthesised on the host cores before anything is timed, aux written to page-locked memory
@@ -385,8 +402,8 @@ def main():
     groups_per_step = sum(-(-job_kind.count(k) // BATCH) for k in kinds)
     sizing_steps = max(2, SLOTS // math.gcd(groups_per_step, SLOTS))
     ctx.batch_prove_resident_steps(handle, n, sizing_steps, fresh_rs(sizing_steps))
-    if Wm > 0:
-        ctx.batch_prove_resident_steps(handle, n, Wm, rs_warm)
+    if FULL and Wm > 0:
+        ctx.batch_prove_resident_steps(handle, n, Wm, rs_warm)      # the warm-up of the `resident` region
     marshalled = [ctx.marshal_jobs(jobs_with(rs_b[k])) for k in range(K)]
     h2h_calls = int(os.environ.get("MASP_BENCH_H2H_CALLS", SLOTS))
     # the W warm-up steps of the region `value` is measured on: the same call pattern (h2h_calls masp_hip_prove_batch calls in
@@ -394,8 +411,8 @@ def main():
     warm_b = [ctx.marshal_jobs(jobs_with(rs_warm[k])) for k in range(max(Wm, 1))]
     with ThreadPoolExecutor(h2h_calls) as ex:
         list(ex.map(lambda k: ctx.prove_marshalled(warm_b[k][0], n), range(len(warm_b))))
-    # single-proof latency (not the headline value; MASP_BENCH_LONE=0 skips it: the tests that compare bench lines)
-    LONE = os.environ.get("MASP_BENCH_LONE", "1") != "0"
+    # single-proof latency (not the headline value: --full only; MASP_BENCH_LONE=0 skips it there: the tests that compare bench lines)
+    LONE = FULL and os.environ.get("MASP_BENCH_LONE", "1") != "0"
     one = None
     latency_ms = latency_host_ms = None
     lone_graphs = 0
@@ -430,48 +447,96 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    # ---- region A (`resident`): witnesses resident in HBM -> K steps -> proofs gathered on rank 0
-    ctx.profile_enable(True)
-    clocks = ClockWatch(local_rank)
-    barrier()
-    clocks.start("resident")
-    t0 = time.perf_counter()
-    proofs_a, gpu_ms = ctx.batch_prove_resident_steps(handle, n, K, rs_a)       # exactly K steps
-    gathered = D.gather_proofs(proofs_a.reshape(K * n, 192), K * n * world, dist, dev) if dist is not None else proofs_a.reshape(K * n, 192)
-    barrier()
-    elapsed = time.perf_counter() - t0
-    clocks.stop()
-    acc_ms, launches, alg_bytes = ctx.profile_read()
-    split_a = ctx.profile_read_split()
-    # The same launches with ONE batch in flight (one launch sequence of the first circuit's jobs, nothing else on the chip):
-    # with four batches in flight the HIP events around a launch also span the time it waits for the chip behind other
-    # streams' kernels, which is not kernel time (rocprofv3's begin / end of the same launches agree with THIS figure).
-    first = [j for j in range(n) if job_kind[j] == kinds[0]][:BATCH]
-    excl, n_excl = ctx.batch_upload([jobs_with(rs_warm[0])[j] for j in first])
-    ctx.sync()
-    ctx.batch_prove_resident(excl, n_excl)
-    x_ms, x_launches, x_bytes = ctx.profile_read()          # cumulative since profile_enable
-    x_ms, x_launches, x_bytes = x_ms - acc_ms, x_launches - launches, x_bytes - alg_bytes
-    x_split = {k: v - split_a[k] for k, v in ctx.profile_read_split().items()}
-    ctx.batch_free(excl)
-    ctx.profile_enable(False)
+    def headline(elapsed_b):
+        """The keys of a plain run's line (rank 0); --full appends its own after them."""
+        c0 = cs[kinds[0]]
+        sh = synthetic.SHAPES[kinds[0]]
+        config_name = {"spend": "BASELINE.json configs[3]: batch of 256 distinct Spend proofs per step on one MI355X (throughput mode)",
+                       "mixed": "BASELINE.json configs[4]'s job mix: 512 jobs per GPU and step, job j of circuit j mod 3"}.get(
+                           WORKLOAD, "batch of 256 distinct %s proofs per step" % WORKLOAD)
+        return {
+            "metric": "Spend proofs/sec" if WORKLOAD == "spend" else "%s proofs/sec" % WORKLOAD, "value": round(K * n * world / elapsed_b, 2), "unit": "proofs/s",
+            "n_gpus": world, "steps": K, "warmup": Wm, "ms_per_step": round(elapsed_b * 1e3 / K, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+            "config": {"workload": config_name, "proofs_per_step": n, "proofs_per_gpu": K * n, "distinct_witnesses_per_gpu": n,
+                       "ntt_log2": c0.logm, "g1_msm_points": [(1 << c0.logm) - 1, c0.n_aux, sh[3] + c0.n_inputs, sh[4] + 1], "g2_msm_points": sh[4] + 1,
+                       "batch_cap": BATCH, "slots": SLOTS, "calls_in_flight": h2h_calls, "hw_queues": ctx.options.get("hw_queues"),
+                       "parallelism": "proofs sharded over %d GPU(s), no data-path collective, gather of the proofs" % world},
+            "notes": "BENCH_NOTES.md", "library_sha16": library_sha16(), "full": FULL,
+        }
+
+    def finish(out):
+        for k_ in vk.values():
+            k_.close()
+        ctx.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        # RCCL writes its version banner (NCCL_DEBUG=VERSION) through C stdio, which is flushed at exit when stdout is a file:
+        # push it out now so that the JSON line really is the last thing on stdout
+        import ctypes
+        try:
+            ctypes.CDLL(None).fflush(None)
+        except Exception:
+            pass
+        if out is not None:
+            sys.stderr.flush()
+            if world > 1:
+                time.sleep(1.0)                     # the other ranks share this stdout: let their flushes land first
+            print(json.dumps(out), flush=True)      # the ONE JSON line, last thing on stdout
+
+    clocks = ClockWatch(local_rank) if FULL else None
+    if FULL:
+        # ---- region A (`resident`): witnesses resident in HBM -> K steps -> proofs gathered on rank 0
+        ctx.profile_enable(True)
+        barrier()
+        clocks.start("resident")
+        t0 = time.perf_counter()
+        proofs_a, gpu_ms = ctx.batch_prove_resident_steps(handle, n, K, rs_a)       # exactly K steps
+        gathered = D.gather_proofs(proofs_a.reshape(K * n, 192), K * n * world, dist, dev) if dist is not None else proofs_a.reshape(K * n, 192)
+        barrier()
+        elapsed = time.perf_counter() - t0
+        clocks.stop()
+        acc_ms, launches, alg_bytes = ctx.profile_read()
+        split_a = ctx.profile_read_split()
+        # The same launches with ONE batch in flight (one launch sequence of the first circuit's jobs, nothing else on the chip):
+        # with four batches in flight the HIP events around a launch also span the time it waits for the chip behind other
+        # streams' kernels, which is not kernel time (rocprofv3's begin / end of the same launches agree with THIS figure).
+        first = [j for j in range(n) if job_kind[j] == kinds[0]][:BATCH]
+        excl, n_excl = ctx.batch_upload([jobs_with(rs_warm[0])[j] for j in first])
+        ctx.sync()
+        ctx.batch_prove_resident(excl, n_excl)
+        x_ms, x_launches, x_bytes = ctx.profile_read()          # cumulative since profile_enable
+        x_ms, x_launches, x_bytes = x_ms - acc_ms, x_launches - launches, x_bytes - alg_bytes
+        x_split = {k: v - split_a[k] for k, v in ctx.profile_read_split().items()}
+        ctx.batch_free(excl)
+        ctx.profile_enable(False)
     # ---- region B (`value`, BASELINE.md §4): witnesses in page-locked host memory -> K masp_hip_prove_batch calls (one per slot
     # in flight) -> proofs on the host of rank 0 (H2D, D2H and the RCCL gather inside)
     out_b = np.zeros((K, n, 192), np.uint8)
     barrier()
-    clocks.start("value")
+    if clocks is not None:
+        clocks.start("value")
     t0 = time.perf_counter()
     with ThreadPoolExecutor(h2h_calls) as ex:
         list(ex.map(lambda k: ctx.prove_marshalled(marshalled[k][0], n, out_b[k]), range(K)))          # exactly K steps
     gathered_b = D.gather_proofs(out_b.reshape(K * n, 192), K * n * world, dist, dev) if dist is not None else out_b.reshape(K * n, 192)
     barrier()
     elapsed_b = time.perf_counter() - t0
-    clocks.stop()
+    if clocks is not None:
+        clocks.stop()
     if dist is not None:
-        elapsed = D.max_over_ranks(elapsed, dist, dev)
+        if FULL:
+            elapsed = D.max_over_ranks(elapsed, dist, dev)
         elapsed_b = D.max_over_ranks(elapsed_b, dist, dev)
         if rank == 0:
-            assert len(gathered) == K * n * world and len(gathered_b) == K * n * world
+            assert len(gathered_b) == K * n * world and (not FULL or len(gathered) == K * n * world)
+    if args.dump_outputs and rank == 0:
+        # the last timed step as the caller of the timed path receives it: every rank's proofs of that step, rank by rank
+        dump_outputs(args.dump_outputs, out_b[K - 1] if dist is None else
+                     np.frombuffer(b"".join(gathered_b), np.uint8).reshape(world, K, n, 192)[:, K - 1])
+    if not FULL:
+        return finish(headline(elapsed_b) if rank == 0 else None)
     # ---- verification of what was timed (product code: GPU + host Groth16 batch verifiers; plus oracle closed form on a sample)
     pub = [W.public_inputs(i) for i, _ in insts]
 
@@ -652,8 +717,9 @@ def main():
                             "single_proof_latency_ms": None if lat_k is None else round(lat_k, 3), "constraints": cs_k.n_constraints}
     if rank == 0:
         total = K * n * world
+        out = headline(elapsed_b)
         achieved = x_bytes / (x_ms * 1e-3) / 1e9 if x_ms > 0 else 0.0
-        lib_sha = library_sha16()
+        lib_sha = out["library_sha16"]
         # HBM bytes per launch of the same stage: NOT measured by this run (PMC counters need rocprofv3 passes of their own) — read from the
         # tracked rocprofv3 result (tools/pmc_traffic.sh), with the build it was measured on next to it
         traffic = traffic_source = None
@@ -690,11 +756,6 @@ def main():
                                  "model_library_sha16": vm.get("library_sha16"), "model_stale": vm.get("library_sha16") != lib_sha}
             except Exception as e:
                 roofline_valu = {"error": repr(e)}
-        c0 = cs[kinds[0]]
-        sh = synthetic.SHAPES[kinds[0]]
-        config_name = {"spend": "BASELINE.json configs[3]: batch of 256 distinct Spend proofs per step on one MI355X (throughput mode)",
-                       "mixed": "BASELINE.json configs[4]'s job mix: 512 jobs per GPU and step, job j of circuit j mod 3"}.get(
-                           WORKLOAD, "batch of 256 distinct %s proofs per step" % WORKLOAD)
 
         def r3(x):
             return None if x is None else round(x, 3)
@@ -708,15 +769,7 @@ def main():
         # The ONE line: numbers only, in <= 4.5 KB — what each key means, how it was measured and what was verified is in BENCH_NOTES.md
         # (the driver's record keeps the head and the tail of the line; two thirds of the 7.7 KB one were prose and its
         # middle — lone latencies, end_to_end, other_circuits — was lost).  Contract keys first; end_to_end / other_circuits / lone last.
-        out = {
-            "metric": "Spend proofs/sec" if WORKLOAD == "spend" else "%s proofs/sec" % WORKLOAD, "value": round(total / elapsed_b, 2), "unit": "proofs/s",
-            "n_gpus": world, "steps": K, "warmup": Wm, "ms_per_step": r3(elapsed_b * 1e3 / K), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "u32", "data": "synthetic",
-            "config": {"workload": config_name, "proofs_per_step": n, "proofs_per_gpu": K * n, "distinct_witnesses_per_gpu": n,
-                       "ntt_log2": c0.logm, "g1_msm_points": [(1 << c0.logm) - 1, c0.n_aux, sh[3] + c0.n_inputs, sh[4] + 1], "g2_msm_points": sh[4] + 1,
-                       "batch_cap": BATCH, "slots": SLOTS, "calls_in_flight": h2h_calls, "hw_queues": ctx.options.get("hw_queues"),
-                       "parallelism": "proofs sharded over %d GPU(s), no data-path collective, gather of the proofs" % world},
-            "notes": "BENCH_NOTES.md", "library_sha16": lib_sha,
+        out.update({
             "roofline": {"bound": "hbm", "kernel": "G1 bucket-accumulation stage of one G1 MSM of a batch (bucket tree %s levels, sub-batches of %d, then "
                                                    "k_msm_accumulate_pts)" % (ctx_tree_levels, ctx_tree_sub),
                          "achieved": r3(achieved), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
@@ -726,7 +779,7 @@ def main():
                          "kernel_ms_per_launch": {k: round(v / x_launches, 3) for k, v in x_split.items()} if x_launches else None,
                          "timed_region": {"launches": launches, "avg_span_ms": r3(acc_ms / launches) if launches else None}},
             "roofline_valu": roofline_valu,
-        }
+        })
         if not args.no_cpu_baseline and world == 1:
             k0 = kinds[0]
             out["cpu_baseline"] = cpu_baseline(cs[k0], params[k0], base_instance[0], base_instance[1])
@@ -752,26 +805,7 @@ def main():
         })
     else:
         out = None
-    for k_ in vk.values():
-        k_.close()
-    if ctx is not None:
-        ctx.close()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    # RCCL writes its version banner (NCCL_DEBUG=VERSION) through C stdio, which is flushed at exit when stdout is a file:
-    # push it out now so that the JSON line really is the last thing on stdout
-    import ctypes
-    try:
-        ctypes.CDLL(None).fflush(None)
-    except Exception:
-        pass
-    if out is not None:
-        sys.stderr.flush()
-        if world > 1:
-            time.sleep(1.0)                     # the other ranks share this stdout: let their flushes land first
-        print(json.dumps(out), flush=True)      # the ONE JSON line, last thing on stdout
-
+    finish(out)
 
 if __name__ == "__main__":
     main()

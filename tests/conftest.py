@@ -6,8 +6,9 @@ import pytest
 
 # The HIP runtime reads GPU_MAX_HW_QUEUES once, at the process's first HIP call — which in this process may be a test-side HIP unit
 # (tests/native) loaded before libmasp_hip.so: say it here (round 5: the contexts' measured masp_hip_options::hw_queues showed the whole
-# GPU suite running on the runtime's default of four)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# GPU suite running on the runtime's default of four).  Set, not defaulted: the suite asserts 16 (a context's 15 streams a queue each), and a
+# launcher that exports a smaller value of its own would otherwise leave every context of the suite short of queues
+os.environ["GPU_MAX_HW_QUEUES"] = "16"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)

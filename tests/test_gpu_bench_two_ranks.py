@@ -23,7 +23,7 @@ def test_bench_two_ranks_on_one_gpu_gathers_real_proofs():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MASP_BENCH_BACKEND="gloo", MASP_HIP_SLOTS="1", MASP_HIP_TREE_SUB="32", MASP_BENCH_E2E="128", MASP_BENCH_LONE="0", OMP_NUM_THREADS="1")
     K = 2
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", str(K), "--warmup", "1", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", str(K), "--warmup", "1", "--full", "--no-cpu-baseline"],
                          env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -55,7 +55,7 @@ def test_bench_eight_ranks_rehearsal_on_one_gpu():
     from masp_amd.host import effective_cpus
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MASP_BENCH_BACKEND="gloo", MASP_BENCH_CIRCUIT="output", MASP_HIP_SLOTS="1", MASP_HIP_TREE_SUB="16", MASP_BENCH_LONE="0", OMP_NUM_THREADS="1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"],
                          env=env, cwd=ROOT, capture_output=True, text=True, timeout=2400)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -3,12 +3,13 @@
 # bench (default = 4 slots overlapped; MASP_HIP_SLOTS=1 = every kernel alone on the chip).  usage: tools/gpu_cycle.sh <tag> [quick]
 tag=$1
 mkdir -p gpurun_out/$tag
+o=$_                      # (the directory just made: this cycle's output)
 if [ "$2" != "quick" ]; then
   python -m pytest tests -m gpu -x -q 2>&1 | tail -3
 else
   python -m pytest tests/test_gpu_batch_mode.py -m gpu -x -q 2>&1 | tail -3
 fi
-python bench.py --steps 8 --warmup 2 --no-cpu-baseline > gpurun_out/$tag/bench.json 2> gpurun_out/$tag/bench.err || tail -5 gpurun_out/$tag/bench.err
+python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline > $o/bench.json 2> $o/bench.err || tail -5 $o/bench.err
 python - <<PY
 import json
 d=json.loads(open("gpurun_out/$tag/bench.json").read().strip().splitlines()[-1])

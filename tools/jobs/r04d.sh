@@ -3,7 +3,7 @@
 o=gpurun_out/r04d; mkdir -p $o
 timeout 1800 python -m pytest tests -m gpu -x -q 2>&1 | tail -8 > $o/tests.txt
 cat $o/tests.txt
-python bench.py > $o/bench.json 2> $o/bench.err || tail -5 $o/bench.err
+python bench.py --full > $o/bench.json 2> $o/bench.err || tail -5 $o/bench.err
 python - <<PY
 import json
 d=json.loads(open("$o/bench.json").read().strip().splitlines()[-1])

@@ -1,7 +1,7 @@
 #!/bin/bash
 o=gpurun_out/r04f; mkdir -p $o
 timeout 1800 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 > $o/tests.txt; cat $o/tests.txt
-python bench.py > $o/bench.json 2> $o/bench.err || tail -5 $o/bench.err
+python bench.py --full > $o/bench.json 2> $o/bench.err || tail -5 $o/bench.err
 python - <<PY
 import json
 d=json.loads(open("$o/bench.json").read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # r04v: the round's evidence in one call: GPU suite, default bench line (20 steps), PMC traffic, kernel statistics (one slot and default), SQ counters, lone-proof timeline
 o=gpurun_out/r04v; mkdir -p $o
 timeout 1800 python -m pytest tests -m gpu -x -q 2>&1 | tail -4 > $o/tests.txt; cat $o/tests.txt
-python bench.py --steps 20 --warmup 2 > $o/bench20.json 2> $o/bench20.err || tail -5 $o/bench20.err
+python bench.py --full --steps 20 --warmup 2 > $o/bench20.json 2> $o/bench20.err || tail -5 $o/bench20.err
 python - <<PY
 import json
 d=json.loads(open("$o/bench20.json").read().strip().splitlines()[-1])

@@ -13,7 +13,7 @@ grep "lone ms\|==" $o/lone_ab.txt
 bash tools/abn.sh 2 masp_amd/libmasp_hip.so tools/_build/ab/libmasp_hip_unroll2.so > $o/unroll2_ab.txt 2>&1; cat $o/unroll2_ab.txt
 for rep in 1 2; do
   for c in "" 13 14; do
-    v=$(MASP_HIP_MSM_C_B2=$c MASP_BENCH_E2E=0 MASP_BENCH_LONE=0 python bench.py --steps 8 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); o=d['other_circuits']; print('%.1f resident %.1f output %.0f convert %.0f' % (d['value'], d['resident']['value'], o['output']['value'], o['convert']['value']))")
+    v=$(MASP_HIP_MSM_C_B2=$c MASP_BENCH_E2E=0 MASP_BENCH_LONE=0 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); o=d['other_circuits']; print('%.1f resident %.1f output %.0f convert %.0f' % (d['value'], d['resident']['value'], o['output']['value'], o['convert']['value']))")
     echo "window_bits_b2=${c:-default}: $v" | tee -a $o/b2_window_ab.txt
   done
 done

@@ -6,12 +6,12 @@ root=$PWD
 out=$root/gpurun_out/pmc_sq
 rm -rf $out; mkdir -p $out
 ctrs="SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_BUSY_CYCLES SQ_INSTS_VMEM_RD SQ_WAVES"
-(cd /tmp && MASP_HIP_SLOTS=1 rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $out -o run -- python $root/bench.py --steps 4 --warmup 1 --no-cpu-baseline > $out/run.log 2>&1)
+(cd /tmp && MASP_HIP_SLOTS=1 rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $out -o run -- python $root/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline > $out/run.log 2>&1)
 python - <<PY
 import csv, glob, json, collections
 f = glob.glob("$out/**/*counter_collection.csv", recursive=True)[0]
 allrows = list(csv.DictReader(open(f)))
-doc = {"command": "tools/pmc_sq.sh: MASP_HIP_SLOTS=1 rocprofv3 --pmc <8 SQ counters> --kernel-trace -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline",
+doc = {"command": "tools/pmc_sq.sh: MASP_HIP_SLOTS=1 rocprofv3 --pmc <8 SQ counters> --kernel-trace -- python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline",
        "note": "one batch in flight (every kernel alone on the chip), averages per launch of the full 128-proof batch; quad-cycle units (MI355X_MICROARCH.md)"}
 for key, pat, vgprs in (("k_msm_accumulate<G1>", "k_msm_accumulate<masp::FpOps>", "226 VGPRs, no spills: 2 waves per SIMD"),
                         ("k_msm_accumulate<G2>", "k_msm_accumulate<masp::Fp2Ops>", "396 VGPRs, no spills in the loop (the exceptional cases of the addition are one out-of-line call: 512 B of scratch for its arguments): 1 wave per SIMD; the 384-bit product is an out-of-line call")):

@@ -7,7 +7,7 @@ root=$PWD
 out=$root/gpurun_out/pmc_sqk
 rm -rf $out; mkdir -p $out
 ctrs="SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_BUSY_CYCLES SQ_INSTS_VMEM_RD SQ_WAVES"
-(cd /tmp && MASP_HIP_SLOTS=1 MASP_BENCH_E2E=0 rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $out -o run -- python $root/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $out/run.log 2>&1)
+(cd /tmp && MASP_HIP_SLOTS=1 MASP_BENCH_E2E=0 rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $out -o run -- python $root/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $out/run.log 2>&1)
 python - <<PY
 import csv, glob, json, collections, re
 f = glob.glob("$out/**/*counter_collection.csv", recursive=True)[0]
@@ -17,7 +17,7 @@ for r in csv.DictReader(open(f)):
     k = re.sub(r"\(.*", "", r["Kernel_Name"]).replace("void ", "").replace("masp::", "")
     acc[k][r["Counter_Name"]] += float(r["Counter_Value"])
     if r["Counter_Name"] == "SQ_WAVES": n[k] += 1
-doc = {"command": "tools/pmc_sq_kernels.sh: MASP_HIP_SLOTS=1 rocprofv3 --pmc <8 SQ counters> --kernel-trace -- python bench.py --steps 2 --warmup 1",
+doc = {"command": "tools/pmc_sq_kernels.sh: MASP_HIP_SLOTS=1 rocprofv3 --pmc <8 SQ counters> --kernel-trace -- python bench.py --full --steps 2 --warmup 1",
        "note": "one batch in flight; counters summed over all dispatches of a kernel; SQ_WAIT_* / SQ_ACTIVE_* in quad-cycles (MI355X_MICROARCH.md)", "kernels": {}}
 tot = sum(v.get("SQ_BUSY_CYCLES", 0) for v in acc.values()) or 1
 for k, v in sorted(acc.items(), key=lambda kv: -kv[1].get("SQ_BUSY_CYCLES", 0))[:28]:

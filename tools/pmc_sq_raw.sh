@@ -5,7 +5,7 @@ root=$PWD
 out=$root/gpurun_out/pmc_sqr
 rm -rf $out; mkdir -p $out
 ctrs=${1:-"SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAVES"}
-(cd /tmp && MASP_HIP_SLOTS=1 MASP_BENCH_E2E=0 rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $out -o run -- python $root/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $out/run.log 2>&1)
+(cd /tmp && MASP_HIP_SLOTS=1 MASP_BENCH_E2E=0 rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d $out -o run -- python $root/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $out/run.log 2>&1)
 python - <<PY
 import csv, glob, json, collections, re
 f = glob.glob("$out/**/*counter_collection.csv", recursive=True)[0]

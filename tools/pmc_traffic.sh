@@ -13,7 +13,7 @@ rm -rf $out; mkdir -p $out
 [ -x $root/tools/_build/pmc_calib ] || { mkdir -p $root/tools/_build; /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 $root/tools/pmc_calib.hip -o $root/tools/_build/pmc_calib; }
 (cd /tmp && rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/calib -o run -- $root/tools/_build/pmc_calib > $out/calib.log 2>&1)
 for c in FETCH_SIZE WRITE_SIZE; do
-  (cd /tmp && MASP_BENCH_OTHER=0 MASP_BENCH_LONE=0 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/$c -o run -- python $root/bench.py --steps ${PMC_STEPS:-4} --warmup 1 --no-cpu-baseline > $out/$c.log 2>&1)
+  (cd /tmp && MASP_BENCH_OTHER=0 MASP_BENCH_LONE=0 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/$c -o run -- python $root/bench.py --full --steps ${PMC_STEPS:-4} --warmup 1 --no-cpu-baseline > $out/$c.log 2>&1)
 done
 python - <<PY
 import csv, glob, json, os, re
@@ -68,7 +68,7 @@ doc = {
  "library_sha16": hashlib.sha256(open("$root/masp_amd/libmasp_hip.so", "rb").read()).hexdigest()[:16],
  "kernel": "G1 bucket-accumulation stage per G1 MSM: k_tree_plan / k_tree_records / k_tree_pass1 / k_tree_pass2 / k_tree_copy / k_binv_* over 4 tree levels in sub-batches of 86 proofs, then k_msm_accumulate_pts",
  "date": time.strftime("%Y-%m-%d"),
- "command": "tools/pmc_traffic.sh: rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) --kernel-trace -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline (256 distinct Spend witnesses per step); calibration pass on tools/_build/pmc_calib",
+ "command": "tools/pmc_traffic.sh: rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) --kernel-trace -- python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline (256 distinct Spend witnesses per step); calibration pass on tools/_build/pmc_calib",
  "calibration": {"pattern": "one 96-byte row (6 x global_load_dwordx4) per lane at a random index, 3 GiB table, 2^24 rows per launch",
                  "stride128_reported_KB": rep128, "stride128_line_bytes": true128, "stride96_reported_KB": rep96, "stride96_expected_line_bytes": true96,
                  "bytes_per_reported_byte": factor, "stride96_over_stride128_reported": rep96 / rep128,

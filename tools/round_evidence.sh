@@ -6,7 +6,7 @@ tag=${1:-evidence}
 o=gpurun_out/$tag
 mkdir -p $o
 timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -3 > $o/gpu_tests.txt
-python bench.py --steps 20 --warmup 5 > $o/bench_driver_flags_steps20_warmup5.json 2> $o/bench.err
+python bench.py --full --steps 20 --warmup 5 > $o/bench_driver_flags_steps20_warmup5.json 2> $o/bench.err
 PROF_ARGS="--steps 2 --warmup 1 --no-cpu-baseline" bash tools/prof_run.sh ${tag}_slots1 MASP_HIP_SLOTS=1 > $o/prof_slots1.log 2>&1
 cp gpurun_out/prof_${tag}_slots1/all.txt $o/kernel_stats_one_slot_serialized_all_dispatches.txt
 cp gpurun_out/prof_${tag}_slots1/batch.txt $o/kernel_stats_one_slot_serialized_batches_of_256_only.txt

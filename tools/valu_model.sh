@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 root=$PWD
 out=$root/gpurun_out/pmc_valu
 rm -rf $out; mkdir -p $out
-(cd /tmp && MASP_HIP_SLOTS=1 MASP_BENCH_E2E=0 MASP_BENCH_OTHER=0 MASP_BENCH_LONE=0 rocprofv3 --pmc SQ_INSTS_VALU --kernel-trace --output-format csv -d $out -o run -- python $root/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $out/run.log 2>&1)
+(cd /tmp && MASP_HIP_SLOTS=1 MASP_BENCH_E2E=0 MASP_BENCH_OTHER=0 MASP_BENCH_LONE=0 rocprofv3 --pmc SQ_INSTS_VALU --kernel-trace --output-format csv -d $out -o run -- python $root/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $out/run.log 2>&1)
 python - <<PY
 import csv, glob, json, collections, re
 f = glob.glob("$out/**/*counter_collection.csv", recursive=True)[0]
