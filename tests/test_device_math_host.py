@@ -2,29 +2,20 @@
 the host and checked against python big integers and the oracle.  Runs without a GPU; the same
 functions run on the device in the -m gpu tests."""
 import ctypes as C
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
+import device_shim
 import oracle_lib as O
 import pyref
 from pyref import P, R, F1, F2
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "device_math_host.hip")
-SO = os.path.join(HERE, "native", "_device_math_host.so")
-
 
 @pytest.fixture(scope="module")
 def mh():
-    hdrs = [os.path.join(HERE, "..", "masp_amd", "csrc", "device", f) for f in ("field.hpp", "curve.hpp", "io.hpp", "consts.hpp")] + [os.path.join(HERE, "..", "tools", "fp28.hpp")]
-    newest = max(os.path.getmtime(p) for p in hdrs + [SRC])
-    if not os.path.exists(SO) or os.path.getmtime(SO) < newest:
-        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O2", "-std=c++17", "-fPIC", "-shared", SRC, "-o", SO])
-    return C.CDLL(SO)
+    return device_shim.load()
 
 
 def test_field_ops(mh):

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from pyref import R
+from pyref import F1, G1, R, ec_add, ec_mul, g1_unc
 
 pytestmark = pytest.mark.gpu
 
@@ -74,6 +74,37 @@ def test_g1_batch_of_msms_with_every_exceptional_pair(ctxs, which, window_bits):
     mixed[3::5, :] = 0
     mixed[3::5, 0] = 0x40
     assert ctxs[which].msm_g1_multi(mixed, sc[3:13], window_bits=window_bits) == [O.msm_g1(mixed, sc[p]) for p in range(3, 13)]
+
+
+def _x_zero_case(rng, n, nvec):
+    """bases t_i T + [k_i] G with T = (0, 2) of order 3 (on the curve, outside the subgroup, accepted by the loader, which checks
+    flags and canonical encoding only): (0, 2), (0, p - 2) and their sums with ordinary points among ordinary bases, runs of them side
+    by side.  x = 0 is what marks the point at infinity inside the bucket tree (k_tree_pass1 / k_tree_pass2: O::is_zero(c.x1)): these
+    are the only inputs that reach that branch without being infinity.  -> bases, scalar vectors, expected results from pyref"""
+    T = (0, 2)
+    ts = [rng.choice([0, 1, 2]) for _ in range(n)]
+    ts[:6] = [1, 1, 2, 2, 1, 2]
+    ks = [0 if i < 6 else rng.randrange(1, R) for i in range(n)]
+    pts = [ec_add(F1, ec_mul(F1, T, t), ec_mul(F1, G1, k)) for t, k in zip(ts, ks)]
+    bases = np.stack([np.frombuffer(g1_unc(p), np.uint8) for p in pts])
+    vecs = [np.tile(_le(s), (n, 1)) for s in (1, 3, 0x1234567)] + [_rand(rng, n) for _ in range(nvec - 3)]
+    want = []
+    for v in vecs:
+        sc = [int.from_bytes(v[i].tobytes(), "little") for i in range(n)]
+        want.append(g1_unc(ec_add(F1, ec_mul(F1, T, sum(s * t for s, t in zip(sc, ts)) % 3),
+                                  ec_mul(F1, G1, sum(s * k for s, k in zip(sc, ks)) % R))))
+    return bases, np.stack(vecs), want
+
+
+@pytest.mark.parametrize("which", ["auto", "off", "deep"])
+def test_g1_bases_with_x_zero(ctxs, which):
+    rng = random.Random(3000)
+    bases, sc, want = _x_zero_case(rng, 40, 10)
+    assert [bytes(b) for b in ctxs[which].msm_g1_multi(bases, sc, window_bits=4)] == want
+    assert [bytes(b) for b in ctxs[which].msm_g1_multi(bases, sc, window_bits=7)] == want
+    # the lone path (msm_g1: one MSM)
+    for p in range(4):
+        assert ctxs[which].msm_g1(bases, sc[p]) == want[p], p
 
 
 @pytest.mark.parametrize("which", ["auto", "off", "deep"])
