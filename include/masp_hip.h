@@ -121,7 +121,7 @@ typedef struct {
     int32_t hw_queues;               /* OUTPUT of masp_hip_ctx_get_options (ignored on input; was reserved[0]): the hardware queues the HIP
                                         runtime of this process spreads its streams over, MEASURED when the context was created (as many
                                         single-wave kernels as the context's slots have streams, at most 21, launched at once on streams of
-                                        their own, once per process and device: how many ran concurrently).  A slot owns five streams; with
+                                        their own, once per process and device: how many ran concurrently).  A slot works on five streams; with
                                         fewer queues than streams, independent kernels wait for each other (round 4, 8 queues: -3 ... -10 %
                                         proofs/s) — and with MORE than MASP_HIP_MAX_USEFUL_HW_QUEUES in the process every dispatch is slower
                                         (see there).  The runtime's default is FOUR (profiles/r05_hw_queues_probe.txt); it reads
@@ -189,10 +189,10 @@ int masp_hip_ctx_inject_fault(masp_hip_ctx* ctx, int device, uint32_t nth);
 /* How many of THIS context's own streams (mains_only: only the ones that work side by side — the context's, the slots' main streams, the
  * verifier's two) run a kernel at the same time, measured now (the context must be idle).  *concurrent < *n_streams means two of them
  * share a hardware queue and run their work one after the other.  Which queue the runtime gives a stream depends on everything the PROCESS
- * created before, so a context creates all of its streams when it is created — 15 with the default four slots (slots 2 and up use slot 1's
- * side streams), one queue each of the default 16 —, measures the ones that work side by side and replaces any that share a queue:
- * a first, second and third context of a process prove at the same rate (profiles/r06_slot_streams_creation_order.txt,
- * profiles/r06_second_context_root_cause.txt). */
+ * created before, so a context creates all of its streams when it is created (and destroys them with itself) — 15 with the default four
+ * slots (slots 2 and up use slot 1's side streams), one queue each of the default 16 —, measures the ones that work side by side and
+ * replaces any that share a queue: a first, second and third context of a process prove at the same rate
+ * (profiles/r06_slot_streams_creation_order.txt, profiles/r06_second_context_root_cause.txt). */
 int masp_hip_ctx_stream_concurrency(masp_hip_ctx* ctx, int mains_only, int* n_streams, int* concurrent);
 /* *out = calls of masp_hip_prove_batch groups so far that were replayed from a captured launch graph
  * (masp_hip_options::lone_proof_graph); a caller that proves one description at a time sees it grow from its third proof on */

@@ -131,6 +131,7 @@ struct Circuit {
 
 // scratch for one batch of up to `ctx->batch_cap` proofs of the same circuit + a stream.  Every stage is ONE launch for the
 // whole batch (gridDim.y = proofs); a few slots let the stages of different batches overlap on the device.
+// A slot BORROWS its streams from its context's stream table (masp_hip_ctx::streams) and never creates or destroys one.
 struct Slot {
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
@@ -140,7 +141,6 @@ struct Slot {
     // with its own workspace, next to the quotient pipeline on the main stream
     static constexpr int N_AUX = 4;
     hipStream_t aux[N_AUX] = {nullptr, nullptr, nullptr, nullptr};
-    bool owns_aux = true;   // false: the side streams are slot 1's (masp_hip_ctx::slot_streams)
     hipEvent_t ev_fork = nullptr, ev_sort_b = nullptr, ev_fixed = nullptr, ev_join[N_AUX] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_uploaded = nullptr;   // behind the host-to-device copies of this slot's batch (masp_hip_ctx::upload_tail)
     MsmWorkspace<FpOps> ws_l, ws_a, ws_b;
@@ -194,12 +194,9 @@ struct Slot {
     }
     ~Slot() {
         drop_graphs();
-        if (stream) hipStreamDestroy(stream);
         if (done) hipEventDestroy(done);
-        for (int i = 0; i < N_AUX; ++i) {
-            if (aux[i] && owns_aux) hipStreamDestroy(aux[i]);
-            if (ev_join[i]) hipEventDestroy(ev_join[i]);
-        }
+        for (hipEvent_t e : ev_join)
+            if (e) hipEventDestroy(e);
         for (hipEvent_t e : ev_lone)
             if (e) hipEventDestroy(e);
         if (ev_fork) hipEventDestroy(ev_fork);
@@ -221,29 +218,19 @@ struct Slot {
         ws1.tree.own.limit = (size_t)o.bucket_tree_scratch_mb << 20;
         lone_graph = o.lone_proof_graph > 0;
     }
-    // `streams`: this slot's five streams (main, then the four side streams), created by the context when IT was created (see
-    // masp_hip_ctx::slot_streams); nullptr: the slot creates its own
-    int init(const hipStream_t* streams = nullptr, bool side_streams_are_mine = true) {
-        owns_aux = side_streams_are_mine;
-        if (streams) {
-            stream = streams[0];
-            for (int i = 0; i < N_AUX; ++i) aux[i] = streams[1 + i];
-        } else {
-            HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        }
+    // `streams`: this slot's row of the context's stream table (main, then the four side streams), borrowed for the slot's life.
+    // (The side streams exist before the slot's first lone proof.  Creating them at that proof instead — so that a batch prover holds one
+    // stream per slot — was measured in round 6: batch throughput equal, lone proofs 4.1 - 4.2 instead of 3.6 - 3.7 ms inside bench.py,
+    // equal in the standalone tool; not understood, not kept: profiles/r06_second_context_root_cause.txt.)
+    int init(const std::array<hipStream_t, 5>& streams) {
+        stream = streams[0];
+        for (int i = 0; i < N_AUX; ++i) aux[i] = streams[1 + i];
         HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&ev_uploaded, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&ev_sort_b, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&ev_fixed, hipEventDisableTiming));
-        // (the four side streams are created WITH the slot.  Creating them at the slot's first lone proof instead — so that a batch prover
-        // holds one stream per slot — was measured in round 6: batch throughput equal, lone proofs 4.1 - 4.2 instead of 3.6 - 3.7 ms inside
-        // bench.py, equal in the standalone tool; not understood, not kept: profiles/r06_second_context_root_cause.txt.  With the default
-        // 3 slots a context's 16 streams cover the default 16 hardware queues exactly once.)
-        for (int i = 0; i < N_AUX; ++i) {
-            if (!aux[i]) HIP_TRY(hipStreamCreateWithFlags(&aux[i], hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&ev_join[i], hipEventDisableTiming));
-        }
+        for (hipEvent_t& e : ev_join) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         HIP_TRY(hipHostMalloc(&h_flags, sizeof(int)));
         int rc;
         if ((rc = flags.reserve(1))) return rc;
@@ -279,6 +266,28 @@ struct ResidentBatch {
     DevBuf<uint32_t> rs;        // n x 16
 };
 
+// Every stream of a device context, as plain handles (masp_hip_ctx::streams).  The table destroys each DISTINCT handle once, with the
+// context; the only other place that destroys one is separate_main_streams, when it replaces a main stream in place.
+struct StreamTable {
+    hipStream_t main = nullptr;                     // the context's own
+    std::vector<std::array<hipStream_t, 5>> slot;   // per slot: [0] main, [1..4] side streams (several rows may hold the same side streams)
+    hipStream_t vk[2] = {nullptr, nullptr};         // the batch verifier's keys (masp_hip_vk_prepare hands them out in turn)
+    std::vector<hipStream_t> distinct() const {
+        std::vector<hipStream_t> out;
+        auto add = [&](hipStream_t s) {
+            if (s && std::find(out.begin(), out.end(), s) == out.end()) out.push_back(s);
+        };
+        add(main);
+        for (const auto& row : slot)
+            for (hipStream_t s : row) add(s);
+        for (hipStream_t s : vk) add(s);
+        return out;
+    }
+    ~StreamTable() {
+        for (hipStream_t s : distinct()) (void)hipStreamDestroy(s);
+    }
+};
+
 }  // namespace masp
 
 using masp::Circuit;
@@ -309,7 +318,18 @@ struct masp_hip_ctx {
     std::condition_variable slot_cv;
     std::vector<char> slot_busy;
     std::string err;
-    hipStream_t main_stream = nullptr;
+    // Every stream the context uses, in one table: the context CREATES all of them when it is created (create_single), slot by slot, and
+    // the table destroys them with it, after the slots (declared before them).  A slot borrows its row when it is created — a failed
+    // attempt leaves the row as it was — and never creates or destroys a stream.  The main streams are then MEASURED and, where two share
+    // a hardware queue, replaced in place (separate_main_streams): the runtime hands hardware queues to streams in creation order, so the
+    // main streams — the ones that carry batches — get queues of their own whatever the process created before (round 6: with 21 streams
+    // created slot by slot over 16 queues, a later context of a process could find two of its main streams on one queue: -3.5 % at 4 slots).
+    // Slots 0 and 1 have side streams of their own; from slot 2 on a slot's row holds slot 1's (a lone proof takes the first free slot, so
+    // three lone proofs must be in flight at once before two of them share side streams — they then interleave on them, each behind its own
+    // events).  A default context so has 1 + 4 + 8 + 2 = 15 streams: one hardware queue each of the default 16, nothing shares.  (With
+    // masp_hip_options::lone_proof_graph every slot has its own: a stream that is being captured cannot take another thread's launches.)
+    // The verifier's two: a verification that shared a hardware queue with a slot's main stream waited behind a 185 ms batch (end to end -10 %).
+    masp::StreamTable streams;
     std::unique_ptr<Circuit> circ[MASP_HIP_MAX_CIRCUITS];
     std::map<uint32_t, std::unique_ptr<NttDomain>> domains;
     std::vector<std::unique_ptr<Slot>> slots;
@@ -321,25 +341,11 @@ struct masp_hip_ctx {
     std::atomic<uint64_t> requeued{0};
     // device context: the n-th masp_hip_prove_batch call from now fails before it touches the device (masp_hip_ctx_inject_fault; 0 = disarmed)
     std::atomic<uint32_t> fault_countdown{0};
+    std::atomic<unsigned> vk_next{0};   // which verifier stream the next key gets
+    int main_streams_concurrent = 0;   // of the 1 + slots streams that carry batches, how many ran at once when the context was created
     // Host-to-device copies of concurrent masp_hip_prove_batch calls go ONE BATCH AFTER THE OTHER: a batch's copies wait for the event
     // behind the previous batch's copies (whatever slot that was).  Three calls that start together (the beginning of a job list, of a
     // timed region) otherwise share the link, and none of them can start computing before all 3 x 820 MB have crossed it.
-    // The streams of ALL slots are created with the context, slot by slot (create_single), and the main streams are then MEASURED and, where
-    // two share a hardware queue, replaced (separate_main_streams): the runtime hands hardware queues to streams in creation order, so the main streams — the ones that carry batches — get
-    // queues of their own whatever the process created before (round 6: with 21 streams created slot by slot over 16 queues, a later
-    // context of a process could find two of its main streams on one queue: -3.5 % at 4 slots).  [slot][0] main, [slot][1..4] side streams;
-    // a slot takes its five when it is created and owns them from then on (taken[slot]).
-    // Slots 0 and 1 have side streams of their own; from slot 2 on a slot uses slot 1's (a lone proof takes the first free slot, so three lone
-    // proofs must be in flight at once before two of them share side streams — they then interleave on them, each behind its own events).  A
-    // default context so has 1 + 4 + 8 + 2 = 15 streams: one hardware queue each of the default 16, nothing shares.  (With
-    // masp_hip_options::lone_proof_graph every slot keeps its own: a stream that is being captured cannot take another thread's launches.)
-    std::vector<std::array<hipStream_t, 5>> slot_streams;
-    // ... and two streams for the batch verifier's keys (masp_hip_vk_prepare hands them out in turn; a key does not own its stream): a
-    // verification that shared a hardware queue with a slot's main stream waited behind a 185 ms batch (end to end -10 %)
-    hipStream_t vk_streams[2] = {nullptr, nullptr};
-    std::atomic<unsigned> vk_next{0};
-    int main_streams_concurrent = 0;   // of the 1 + slots streams that carry batches, how many ran at once when the context was created
-    std::vector<char> slot_streams_taken;
     std::mutex upload_mu;
     hipEvent_t upload_tail = nullptr;   // an event of some slot of this context (slots live as long as the context)
     // the building-block MSM entry points (masp_hip_msm_g1_multi ...) run on a workspace of their own: what lack of tree scratch did there
@@ -365,11 +371,14 @@ static inline int fail(masp_hip_ctx* ctx, int rc) {
     return rc;
 }
 
+// the context a single-device entry point works on: a multi-device front's first device context
+#define FIRST_DEVICE(ctx) ((ctx) && !(ctx)->children.empty() ? (ctx)->children[0] : (ctx))
+
 static inline int get_domain(masp_hip_ctx* ctx, uint32_t logm, NttDomain** out) {
     auto it = ctx->domains.find(logm);
     if (it == ctx->domains.end()) {
         std::unique_ptr<NttDomain> d(new NttDomain);
-        int rc = d->init(logm, ctx->main_stream);
+        int rc = d->init(logm, ctx->streams.main);
         if (rc) return rc;
         it = ctx->domains.emplace(logm, std::move(d)).first;
     }

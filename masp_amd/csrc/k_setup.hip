@@ -5,8 +5,6 @@
 
 using namespace masp;
 
-#define FIRST_DEVICE(ctx) ((ctx) && !(ctx)->children.empty() ? (ctx)->children[0] : (ctx))
-
 extern "C" {
 
 // ---- parameter generation -------------------------------------------------------------------------
@@ -24,7 +22,7 @@ int masp_hip_generate_parameters(masp_hip_ctx* ctx, const masp_hip_r1cs* cs, con
     ctx = FIRST_DEVICE(ctx);
     std::unique_lock<std::shared_mutex> lock(ctx->mu);
     hipSetDevice(ctx->device);
-    hipStream_t s = ctx->main_stream;
+    hipStream_t s = ctx->streams.main;
     Fr tw[5];
     for (int i = 0; i < 5; ++i) {
         Fr v = fe_load_le<FrCfg>(toxic + 32 * i);

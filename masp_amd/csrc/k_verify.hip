@@ -27,14 +27,9 @@ struct masp_hip_vk {
     DevBuf<int> d_status;
     DevBuf<Fp> d_f;
     hipStream_t stream = nullptr;  // verification runs next to the provers' batches, on one of the context's two verifier streams (not owned:
-                                   // masp_hip_ctx::vk_streams — created and kept off the batch streams' hardware queues with the context)
+                                   // masp_hip_ctx::streams — created and kept off the batch streams' hardware queues with the context)
     std::mutex mu;                 // one verification at a time per key
 };
-
-// (fail() takes slot_mu for the error text: fine under the shared context lock too)
-static int fail_shared_v(masp_hip_ctx* ctx, int rc) { return fail(ctx, rc); }
-
-#define FIRST_DEVICE(ctx) ((ctx) && !(ctx)->children.empty() ? (ctx)->children[0] : (ctx))
 
 extern "C" {
 
@@ -58,7 +53,7 @@ int masp_hip_vk_prepare(masp_hip_ctx* ctx, const uint8_t* params, size_t params_
         ops.insert(ops.end(), ps[i]->ops.begin(), ps[i]->ops.end());
     }
     int rc;
-    hipStream_t s = ctx->main_stream;
+    hipStream_t s = ctx->streams.main;
     if ((rc = v->ops.upload(ops.data(), ops.size(), s)) || (rc = v->steps.upload(steps.data(), steps.size(), s))) return fail(ctx, rc);
     if (hipStreamSynchronize(s) != hipSuccess) return fail(ctx, MASP_HIP_E_HIP);
     PairingProgramDev* dst[3] = {&v->dbl, &v->add, &v->mul12};
@@ -70,7 +65,7 @@ int masp_hip_vk_prepare(masp_hip_ctx* ctx, const uint8_t* params, size_t params_
     v->n_slots = pp.n_slots;
     v->lds_ok = hipFuncSetAttribute((const void*)k_miller_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess &&
                 hipFuncSetAttribute((const void*)k_fp12_product, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;
-    v->stream = ctx->vk_streams[ctx->vk_next.fetch_add(1) % 2];
+    v->stream = ctx->streams.vk[ctx->vk_next.fetch_add(1) % 2];
     *out = v.release();
     return MASP_HIP_OK;
 }
@@ -107,13 +102,13 @@ int masp_hip_verify_batch(masp_hip_ctx* ctx, masp_hip_vk* vk, size_t n, const ui
     int rc;
     if ((rc = d_proofs.upload(proofs, 192 * n, s)) || (rc = d_z.upload(z, 16 * n, s)) || (rc = d_za.reserve(n)) || (rc = d_b.reserve(n)) ||
         (rc = d_zc.reserve(n)) || (rc = d_status.reserve(n)) || (rc = d_f.reserve(12 * n)) || (rc = d_sum.reserve(96)))
-        return fail_shared_v(ctx, rc);
+        return fail(ctx, rc);
     HIP_TRY(hipMemsetAsync(d_status.p, 0, sizeof(int) * n, s));
     // the interpreter keeps its slots in LDS: n_slots x 48 bytes per wave
     const uint32_t lds = vk->n_slots * 48;
     if (!vk->lds_ok || lds > 64 * 1024) {
         last_hip_error() = "pairing interpreter: LDS configuration failed";
-        return fail_shared_v(ctx, MASP_HIP_E_HIP);
+        return fail(ctx, MASP_HIP_E_HIP);
     }
     MASP_LAUNCH(k_verify_prepare, dim3((nn + 63) / 64, 5), dim3(64), 0, s, d_proofs.p, d_z.p, nn, d_za.p, d_b.p, d_zc.p, d_status.p);
     MASP_LAUNCH(k_g1_sum_export, dim3(1), dim3(256), 0, s, d_zc.p, nn, d_sum.p);
@@ -129,15 +124,15 @@ int masp_hip_verify_batch(masp_hip_ctx* ctx, masp_hip_vk* vk, size_t n, const ui
         hipMemcpyAsync(&f, d_f.p, 12 * 48, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemcpyAsync(sum96, d_sum.p, 96, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
         last_hip_error() = std::string("batch verification failed: ") + hipGetErrorString(hipGetLastError());
-        return fail_shared_v(ctx, MASP_HIP_E_HIP);
+        return fail(ctx, MASP_HIP_E_HIP);
     }
-    if (launch_status() != MASP_HIP_OK) return fail_shared_v(ctx, MASP_HIP_E_HIP);  // a refused launch: the buffers read back mean nothing
+    if (launch_status() != MASP_HIP_OK) return fail(ctx, MASP_HIP_E_HIP);  // a refused launch: the buffers read back mean nothing
     for (int st : status)
         if (st & (PT_BAD_FLAGS | PT_NOT_CANONICAL | PT_NOT_IN_SUBGROUP | PT_INFINITY)) return MASP_HIP_OK;  // what Proof::read refuses (the identity included: "point at infinity"): not valid (*all_valid stays 0)
     masp_host::bls::G1A csum;
     if (!masp_host::bls::g1_uncompressed(csum, sum96)) {
         last_hip_error() = "batch verification: device returned a malformed point";
-        return fail_shared_v(ctx, MASP_HIP_E_HIP);
+        return fail(ctx, MASP_HIP_E_HIP);
     }
     int v = masp_host::batch_verify_finish(vk->vk, n, public_inputs, n_public, z, f, csum);
     if (v < 0) return MASP_HIP_E_SCALAR_RANGE;

@@ -26,9 +26,6 @@
 using namespace masp;
 
 // host-to-device copies of concurrent calls one batch after the other (masp_hip_ctx::upload_tail); 0: as they come (A/B builds)
-#ifndef MASP_STREAM_ORDER
-#define MASP_STREAM_ORDER 2   // slot by slot (see create_single); separate_main_streams then makes sure the main streams do not share queues
-#endif
 #ifndef MASP_UPLOAD_CHAIN
 #define MASP_UPLOAD_CHAIN 1
 #endif
@@ -82,30 +79,22 @@ static std::vector<std::pair<size_t, size_t>> even_groups(size_t n, size_t cap) 
     return out;
 }
 
-// slots 0 and 1 — and every slot when lone proofs are replayed from captured graphs — have side streams of their own (masp_hip_ctx::slot_streams)
-static bool slot_owns_side_streams(const masp_hip_ctx* ctx, size_t si) { return si < 2 || ctx->opt.lone_proof_graph > 0; }
-// the five streams the context created for its next slot (slot_mu held), or nullptr if it has none left
-static const hipStream_t* take_slot_streams(masp_hip_ctx* ctx, bool* side_streams_are_its_own) {
-    const size_t i = ctx->slots.size();
-    *side_streams_are_its_own = true;
-    if (i >= ctx->slot_streams.size() || ctx->slot_streams_taken[i]) return nullptr;
-    ctx->slot_streams_taken[i] = 1;
-    *side_streams_are_its_own = slot_owns_side_streams(ctx, i);
-    return ctx->slot_streams[i].data();
+// a new slot on the context's next row of streams (slot_mu held; the caller has checked that the row exists)
+static int add_slot(masp_hip_ctx* ctx, char busy) {
+    std::unique_ptr<Slot> s(new Slot);
+    int rc = s->init(ctx->streams.slot[ctx->slots.size()]);
+    if (rc) return rc;
+    s->profiling = ctx->profiling;
+    s->configure(ctx->opt);
+    ctx->slots.push_back(std::move(s));
+    ctx->slot_busy.push_back(busy);
+    return MASP_HIP_OK;
 }
 static int ensure_slots(masp_hip_ctx* ctx, size_t want) {
     std::lock_guard<std::mutex> g(ctx->slot_mu);
-    want = std::min(want, masp_hip_ctx::MAX_SLOTS);
-    while (ctx->slots.size() < want) {
-        std::unique_ptr<Slot> s(new Slot);
-        bool own = true;
-        const hipStream_t* st = take_slot_streams(ctx, &own);
-        int rc = s->init(st, own);
-        if (rc) return rc;
-        s->configure(ctx->opt);
-        ctx->slots.push_back(std::move(s));
-        ctx->slot_busy.push_back(0);
-    }
+    want = std::min(want, ctx->streams.slot.size());
+    while (ctx->slots.size() < want)
+        if (int rc = add_slot(ctx, 0)) return rc;
     // (a slot is configured once, when it is created: its options never change, and a busy slot's workspaces are read by the
     // thread that owns it — the tree sub-batch may also have been halved there for lack of scratch)
     for (auto& sl : ctx->slots) sl->profiling = ctx->profiling;
@@ -122,15 +111,7 @@ static int slot_try_acquire(masp_hip_ctx* ctx, size_t* si) {
             return MASP_HIP_OK;
         }
     if (ctx->slots.size() >= (size_t)ctx->n_slots) return -1;
-    std::unique_ptr<Slot> s(new Slot);
-    bool own = true;
-    const hipStream_t* st = take_slot_streams(ctx, &own);
-    int rc = s->init(st, own);
-    if (rc) return rc;
-    s->profiling = ctx->profiling;
-    s->configure(ctx->opt);
-    ctx->slots.push_back(std::move(s));
-    ctx->slot_busy.push_back(1);
+    if (int rc = add_slot(ctx, 1)) return rc;
     *si = ctx->slots.size() - 1;
     return MASP_HIP_OK;
 }
@@ -159,14 +140,6 @@ static void slot_release(masp_hip_ctx* ctx, size_t si) {
     // nothing of this context is in flight: the moment to give back what its workspaces outgrew (util.h, dev_free)
     if (idle) dev_free_drain();
 }
-static int fail_shared(masp_hip_ctx* ctx, int rc) {
-    if (rc == MASP_HIP_E_HIP) {
-        std::lock_guard<std::mutex> g(ctx->slot_mu);
-        ctx->err = last_hip_error();
-    }
-    return rc;
-}
-
 // Quotient for np proofs on slot buffers: in[i] + p * in_stride are Montgomery (mont_in) or canonical evaluation
 // vectors of `nrows` entries on the device; result: sl.h + p * m = canonical coefficients h[0..m-1).
 // h_out (stride h_stride elements per proof; NULL: sl.h, stride m).
@@ -544,9 +517,9 @@ void masp_hip_options_default(masp_hip_options* opt) {
 }
 
 // ---- how many hardware queues do this process's streams really get?  (masp_hip_options::hw_queues) -------------------------------
-// One single-wave kernel per stream, all launched at once, each spinning for 2 ms of the constant 100 MHz clock and leaving its
+// One single-wave kernel per stream, all launched at once, each spinning for 2 ms of the constant wall clock and leaving its
 // [start, end): the largest number of them that overlapped = the hardware queues the streams were spread over (streams that share a
-// queue run one after the other).  Temporary streams, created and destroyed BEFORE the context creates its own.
+// queue run one after the other).
 static __global__ void k_hwq_spin(unsigned long long* out, int idx, long long ticks) {
     const long long t0 = wall_clock64();
     // (bounded: a clock that does not advance must not hang the context's creation — 2^22 polls are ~100 ms)
@@ -555,6 +528,45 @@ static __global__ void k_hwq_spin(unsigned long long* out, int idx, long long ti
     out[2 * idx] = (unsigned long long)t0;
     out[2 * idx + 1] = (unsigned long long)wall_clock64();
 }
+// ticks of wall_clock64() per millisecond on the current device (hipDeviceAttributeWallClockRate, kHz: 100 000 on gfx950); 0 if unknown
+static long long wall_clock_per_ms() {
+    int dev = 0, khz = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess) return 0;
+    return khz;
+}
+// The probe on the streams `ss`: *concurrent = the largest number of them that ran their kernel at the same time, *intervals = every
+// stream's [start, end).  The intervals are read back on ss[0], the probe's own stream: the probe waits for no other context's work.
+// MASP_HIP_E_HIP and last_hip_error() if it failed (nothing written then).
+static int measure_streams(const std::vector<hipStream_t>& ss, int* concurrent, std::vector<unsigned long long>* intervals = nullptr) {
+    const int n = (int)ss.size();
+    const long long ms = wall_clock_per_ms();
+    unsigned long long* d = nullptr;
+    HIP_TRY(dev_malloc(&d, 16 * n));
+    (void)hipGetLastError();   // (what an earlier call of this thread left behind is not the probe's failure)
+    bool ok = ms > 0;
+    for (int r = 0; r < 2 && ok; ++r) {  // (the first round loads the code object and creates the queues)
+        for (int i = 0; i < n; ++i) hipLaunchKernelGGL(k_hwq_spin, dim3(1), dim3(64), 0, ss[i], d, i, r ? 2 * ms : ms / 100);
+        for (int i = 0; i < n; ++i) ok = hipStreamSynchronize(ss[i]) == hipSuccess && ok;
+    }
+    std::vector<unsigned long long> h(2 * n);
+    ok = ok && hipGetLastError() == hipSuccess && hipMemcpyAsync(h.data(), d, 16 * n, hipMemcpyDeviceToHost, ss[0]) == hipSuccess &&
+         hipStreamSynchronize(ss[0]) == hipSuccess;
+    (void)dev_free(d);
+    if (!ok) {
+        last_hip_error() = "stream concurrency probe failed";
+        return MASP_HIP_E_HIP;
+    }
+    int best = 0;
+    for (int i = 0; i < n; ++i) {
+        int c = 0;
+        for (int j = 0; j < n; ++j) c += h[2 * j] <= h[2 * i] && h[2 * i] < h[2 * j + 1];
+        best = std::max(best, c);
+    }
+    *concurrent = best;
+    if (intervals) *intervals = std::move(h);
+    return MASP_HIP_OK;
+}
+// The probe on temporary streams, created and destroyed BEFORE the context creates its own; 0 if it failed.
 // Measured ONCE per (process, device) and remembered: the runtime fixes its queue count at the process's first HIP call, so a second
 // context has nothing new to learn — and its probe would wait behind, and share the chip with, whatever the first context is running
 // (ADVICE r05).  The probe synchronises its own streams only, and its buffer goes through dev_malloc / dev_free like every other.
@@ -568,77 +580,38 @@ static int measure_hw_queues(int device, int streams) {
     // keeps for the life of the process — the probe must not itself walk the pool into the slow regime; 21 says "more than 20")
     const int n = std::max(1, std::min(streams, (int)MASP_HIP_MAX_USEFUL_HW_QUEUES + 1));
     std::vector<hipStream_t> ss;
-    unsigned long long* d = nullptr;
-    int best = 0;
-    if (dev_malloc(&d, 16 * n) != hipSuccess) return 0;
     for (int i = 0; i < n; ++i) {
         hipStream_t s = nullptr;
         if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) break;
         ss.push_back(s);
     }
-    if ((int)ss.size() == n) {
-        bool ok = true;
-        for (int r = 0; r < 2; ++r) {  // (the first round loads the code object and creates the queues)
-            for (int i = 0; i < n; ++i) hipLaunchKernelGGL(k_hwq_spin, dim3(1), dim3(64), 0, ss[i], d, i, r ? 200000LL : 1000LL);
-            for (int i = 0; i < n; ++i) ok = hipStreamSynchronize(ss[i]) == hipSuccess && ok;
-        }
-        std::vector<unsigned long long> h(2 * n);
-        if (ok && hipGetLastError() == hipSuccess && hipMemcpyAsync(h.data(), d, 16 * n, hipMemcpyDeviceToHost, ss[0]) == hipSuccess &&
-            hipStreamSynchronize(ss[0]) == hipSuccess)
-            for (int i = 0; i < n; ++i) {
-                int c = 0;
-                for (int j = 0; j < n; ++j) c += h[2 * j] <= h[2 * i] && h[2 * i] < h[2 * j + 1];
-                best = std::max(best, c);
-            }
-    }
+    int best = 0;
+    if ((int)ss.size() == n) (void)measure_streams(ss, &best);
     for (hipStream_t s : ss) (void)hipStreamDestroy(s);
-    (void)dev_free(d);
     (void)hipGetLastError();
     if (best > 0) known[device] = best;
     return best;
 }
 
-// The same measurement on a context's OWN streams (every slot's five + the main stream): how many of them run a kernel at the same time.
-// Fewer than there are streams = two of them share a hardware queue, and kernels of one batch that could overlap wait for each other.
-static int measure_streams(const std::vector<hipStream_t>& ss, int* n_streams, int* concurrent, std::vector<unsigned long long>* intervals = nullptr);
-// mains_only: the context's own stream, the slots' main streams (the ones that carry batches) and the verifier's two
+// The streams that work side by side — the context's own, every slot's main stream (the ones that carry batches) and the verifier's
+// two —, as places in the stream table
+static std::vector<hipStream_t*> main_streams_of(StreamTable& t) {
+    std::vector<hipStream_t*> at{&t.main};
+    for (auto& row : t.slot) at.push_back(&row[0]);
+    for (hipStream_t& v : t.vk) at.push_back(&v);
+    return at;
+}
+// The same measurement on a context's OWN streams (mains_only: main_streams_of; else every distinct one): how many of them run a kernel at
+// the same time.  Fewer than there are streams = two of them share a hardware queue, and kernels that could overlap wait for each other.
 static int measure_own_streams(masp_hip_ctx* ctx, bool mains_only, int* n_streams, int* concurrent) {
     std::vector<hipStream_t> ss;
-    ss.push_back(ctx->main_stream);
-    for (size_t i = 0; i < ctx->slot_streams.size(); ++i) {
-        ss.push_back(ctx->slot_streams[i][0]);
-        if (!mains_only && slot_owns_side_streams(ctx, i))
-            for (int j = 1; j < 5; ++j) ss.push_back(ctx->slot_streams[i][j]);
-    }
-    for (hipStream_t v : ctx->vk_streams) ss.push_back(v);
-    return measure_streams(ss, n_streams, concurrent);
-}
-static int measure_streams(const std::vector<hipStream_t>& ss, int* n_streams, int* concurrent, std::vector<unsigned long long>* intervals) {
-    const int n = (int)ss.size();
-    unsigned long long* d = nullptr;
-    HIP_TRY(dev_malloc(&d, 16 * n));
-    int best = 0;
-    bool ok = true;
-    for (int r = 0; r < 2; ++r) {
-        for (int i = 0; i < n; ++i) hipLaunchKernelGGL(k_hwq_spin, dim3(1), dim3(64), 0, ss[i], d, i, r ? 200000LL : 1000LL);
-        for (int i = 0; i < n; ++i) ok = hipStreamSynchronize(ss[i]) == hipSuccess && ok;
-    }
-    std::vector<unsigned long long> h(2 * n);
-    ok = ok && hipMemcpy(h.data(), d, 16 * n, hipMemcpyDeviceToHost) == hipSuccess;
-    (void)dev_free(d);
-    if (!ok) {
-        last_hip_error() = "stream concurrency probe failed";
-        return MASP_HIP_E_HIP;
-    }
-    for (int i = 0; i < n; ++i) {
-        int c = 0;
-        for (int j = 0; j < n; ++j) c += h[2 * j] <= h[2 * i] && h[2 * i] < h[2 * j + 1];
-        best = std::max(best, c);
-    }
-    *n_streams = n;
-    *concurrent = best;
-    if (intervals) *intervals = h;
-    return MASP_HIP_OK;
+    if (mains_only)
+        for (hipStream_t* p : main_streams_of(ctx->streams)) ss.push_back(*p);
+    else
+        ss = ctx->streams.distinct();
+    const int rc = measure_streams(ss, concurrent);
+    if (rc == MASP_HIP_OK) *n_streams = (int)ss.size();
+    return rc;
 }
 
 // The streams that carry batches — the context's own and every slot's main stream — must each sit on a hardware queue of its own: two
@@ -650,23 +623,22 @@ static int measure_streams(const std::vector<hipStream_t>& ss, int* n_streams, i
 // yet.  Slot 0's main stream is never the one replaced (a lone proof runs 0.4 ms longer when its main stream was not created right in
 // front of its side streams: profiles/r06_slot_streams_creation_order.txt).
 static int separate_main_streams(masp_hip_ctx* ctx) {
+    const unsigned long long ms = (unsigned long long)wall_clock_per_ms();
     for (int attempt = 0; attempt < 8; ++attempt) {
-        std::vector<hipStream_t*> at;
-        at.push_back(&ctx->main_stream);
-        for (auto& a : ctx->slot_streams) at.push_back(&a[0]);
-        for (hipStream_t& v : ctx->vk_streams) at.push_back(&v);   // (the verifier's streams work next to the batches: the same rule)
+        const std::vector<hipStream_t*> at = main_streams_of(ctx->streams);   // (the verifier's streams work next to the batches: the same rule)
         std::vector<hipStream_t> ss;
         for (hipStream_t* p : at) ss.push_back(*p);
-        int n = 0, conc = 0;
+        const int n = (int)ss.size();
+        int conc = 0;
         std::vector<unsigned long long> h;
-        if (int rc = measure_streams(ss, &n, &conc, &h)) return rc;
+        if (int rc = measure_streams(ss, &conc, &h)) return rc;
         ctx->main_streams_concurrent = conc;
         if (conc >= n) return MASP_HIP_OK;
         unsigned long long t0 = ~0ull;
         for (int i = 0; i < n; ++i) t0 = std::min(t0, h[2 * i]);
         bool replaced = false;
         for (int i = 0; i < n; ++i) {
-            if (h[2 * i] - t0 < 100000ull) continue;          // started with the others (100 MHz clock: 1 ms)
+            if (h[2 * i] - t0 < ms) continue;                  // started with the others (within 1 ms)
             int partner = -1;                                  // the stream whose kernel ended when this one's began
             unsigned long long bestd = ~0ull;
             for (int j = 0; j < n; ++j) {
@@ -699,61 +671,31 @@ static int create_single(int device, const masp_hip_options& opt, masp_hip_ctx**
     ctx->batch_cap = (size_t)opt.batch_cap;
     ctx->slots.reserve(masp_hip_ctx::MAX_SLOTS);      // never reallocates: see the locking note on masp_hip_ctx
     ctx->slot_busy.reserve(masp_hip_ctx::MAX_SLOTS);
-    ctx->opt.hw_queues = measure_hw_queues(device, 5 * opt.slots);   // (a slot owns up to five streams)
-    if (hipStreamCreateWithFlags(&ctx->main_stream, hipStreamNonBlocking) != hipSuccess) return MASP_HIP_E_NO_DEVICE;
-    // every slot's streams now, main streams first (masp_hip_ctx::slot_streams)
-    ctx->slot_streams.assign((size_t)opt.slots, std::array<hipStream_t, 5>{});
-    ctx->slot_streams_taken.assign((size_t)opt.slots, 0);
-    bool streams_ok = true;
-    // order: slot by slot, a slot's main stream right in front of its side streams (a lone proof takes the first free slot, i.e. slot 0, and
+    ctx->opt.hw_queues = measure_hw_queues(device, 5 * opt.slots);   // (a slot has up to five streams)
+    // Every stream of the context (masp_hip_ctx::streams; on failure the table destroys what was created), in this order: the context's
+    // own; slot by slot, a slot's main stream right in front of its side streams (a lone proof takes the first free slot, i.e. slot 0, and
     // runs 0.3 - 0.4 ms longer when its side streams were not created right behind its main stream — measured three ways, not understood:
-    // profiles/r06_slot_streams_creation_order.txt); that the main streams then do not share hardware queues is measured and repaired:
+    // profiles/r06_slot_streams_creation_order.txt); the verifier's two.  From slot 2 on a slot's side streams are slot 1's, unless lone
+    // proofs are replayed from captured graphs.  That the main streams then do not share hardware queues is measured and repaired:
     // separate_main_streams
-    auto make = [&](int si, int j) {
-        if (j > 0 && !slot_owns_side_streams(ctx.get(), (size_t)si))
-            ctx->slot_streams[si][j] = ctx->slot_streams[1][j];   // (slot 1's: created before, in every order below)
-        else
-            streams_ok = streams_ok && hipStreamCreateWithFlags(&ctx->slot_streams[si][j], hipStreamNonBlocking) == hipSuccess;
-    };
-#if MASP_STREAM_ORDER == 1      // (A/B builds) every main stream first
-    for (int si = 0; si < opt.slots; ++si) make(si, 0);
-    for (int si = 0; si < opt.slots; ++si)
-        for (int j = 1; j < 5; ++j) make(si, j);
-#elif MASP_STREAM_ORDER == 2    // (A/B builds) slot by slot, as the slots created them before round 6
-    for (int si = 0; si < opt.slots; ++si)
-        for (int j = 0; j < 5; ++j) make(si, j);
-#elif MASP_STREAM_ORDER == 3    // slot 0's side streams, then every main stream (slot 0's first), then the other side streams
-    for (int j = 1; j < 5; ++j) make(0, j);
-    for (int si = 0; si < opt.slots; ++si) make(si, 0);
-    for (int si = 1; si < opt.slots; ++si)
-        for (int j = 1; j < 5; ++j) make(si, j);
-#else                           // slot 0's five, the other slots' main streams, their side streams
-    for (int j = 0; j < 5; ++j) make(0, j);
-    for (int si = 1; si < opt.slots; ++si) make(si, 0);
-    for (int si = 1; si < opt.slots; ++si)
-        for (int j = 1; j < 5; ++j) make(si, j);
-#endif
-    for (hipStream_t& v : ctx->vk_streams) streams_ok = streams_ok && hipStreamCreateWithFlags(&v, hipStreamNonBlocking) == hipSuccess;
-    if (streams_ok && separate_main_streams(ctx.get()) != MASP_HIP_OK) streams_ok = false;
-    if (!streams_ok) {
-        for (size_t si = 0; si < ctx->slot_streams.size(); ++si)
-            for (int j = 0; j < 5; ++j)
-                if (ctx->slot_streams[si][j] && (j == 0 || slot_owns_side_streams(ctx.get(), si))) hipStreamDestroy(ctx->slot_streams[si][j]);
-        for (hipStream_t v : ctx->vk_streams)
-            if (v) hipStreamDestroy(v);
-        hipStreamDestroy(ctx->main_stream);
-        return MASP_HIP_E_NO_DEVICE;
-    }
+    StreamTable& t = ctx->streams;
+    bool ok = hipStreamCreateWithFlags(&t.main, hipStreamNonBlocking) == hipSuccess;
+    t.slot.assign((size_t)opt.slots, std::array<hipStream_t, 5>{});
+    for (size_t si = 0; si < t.slot.size(); ++si)
+        for (int j = 0; j < 5; ++j) {
+            if (j > 0 && si >= 2 && !opt.lone_proof_graph)
+                t.slot[si][j] = t.slot[1][j];
+            else
+                ok = ok && hipStreamCreateWithFlags(&t.slot[si][j], hipStreamNonBlocking) == hipSuccess;
+        }
+    for (hipStream_t& v : t.vk) ok = ok && hipStreamCreateWithFlags(&v, hipStreamNonBlocking) == hipSuccess;
+    if (!ok || separate_main_streams(ctx.get()) != MASP_HIP_OK) return MASP_HIP_E_NO_DEVICE;
     *out = ctx.release();
     return MASP_HIP_OK;
 }
 
-int masp_hip_ctx_create_ex(const int* devices, int n_devices, const masp_hip_options* opt_in, masp_hip_ctx** out) {
-    if (!out || !devices || n_devices <= 0 || n_devices > 64) return MASP_HIP_E_INVALID_ARG;
-    if (opt_in && opt_in->struct_size != 0 && opt_in->struct_size < 4 * sizeof(int32_t)) return MASP_HIP_E_INVALID_ARG;
-    *out = nullptr;
-    const masp_hip_options opt = resolve_options(opt_in);
-    if (n_devices == 1) return create_single(devices[0], opt, out);
+// a multi-device front: one device context per entry of `devices`
+static int create_front(const int* devices, int n_devices, const masp_hip_options& opt, masp_hip_ctx** out) {
     std::unique_ptr<masp_hip_ctx> front(new masp_hip_ctx);
     front->device = devices[0];
     front->opt = opt;
@@ -761,8 +703,7 @@ int masp_hip_ctx_create_ex(const int* devices, int n_devices, const masp_hip_opt
     front->batch_cap = (size_t)opt.batch_cap;
     for (int i = 0; i < n_devices; ++i) {
         masp_hip_ctx* ch = nullptr;
-        int rc = create_single(devices[i], opt, &ch);
-        if (rc) {
+        if (int rc = create_single(devices[i], opt, &ch)) {
             for (masp_hip_ctx* c : front->children) masp_hip_ctx_destroy(c);
             return rc;
         }
@@ -772,6 +713,14 @@ int masp_hip_ctx_create_ex(const int* devices, int n_devices, const masp_hip_opt
     for (int i = 0; i < n_devices; ++i) front->dev_status[i] = MASP_HIP_OK;
     *out = front.release();
     return MASP_HIP_OK;
+}
+
+int masp_hip_ctx_create_ex(const int* devices, int n_devices, const masp_hip_options* opt_in, masp_hip_ctx** out) {
+    if (!out || !devices || n_devices <= 0 || n_devices > 64) return MASP_HIP_E_INVALID_ARG;
+    if (opt_in && opt_in->struct_size != 0 && opt_in->struct_size < 4 * sizeof(int32_t)) return MASP_HIP_E_INVALID_ARG;
+    *out = nullptr;
+    const masp_hip_options opt = resolve_options(opt_in);
+    return n_devices == 1 ? create_single(devices[0], opt, out) : create_front(devices, n_devices, opt, out);
 }
 
 int masp_hip_ctx_get_options(const masp_hip_ctx* ctx, masp_hip_options* out) {
@@ -816,20 +765,8 @@ int masp_hip_ctx_create(int device, masp_hip_ctx** out) {
 // or once)
 int masp_hip_ctx_create_multi(const int* devices, int n_devices, masp_hip_ctx** out) {
     if (!out || !devices || n_devices <= 0 || n_devices > 64) return MASP_HIP_E_INVALID_ARG;
-    if (n_devices > 1) return masp_hip_ctx_create_ex(devices, n_devices, nullptr, out);
     *out = nullptr;
-    std::unique_ptr<masp_hip_ctx> front(new masp_hip_ctx);
-    front->device = devices[0];
-    front->opt = resolve_options(nullptr);
-    front->batch_cap = (size_t)front->opt.batch_cap;
-    masp_hip_ctx* ch = nullptr;
-    int rc = create_single(devices[0], front->opt, &ch);
-    if (rc) return rc;
-    front->children.push_back(ch);
-    front->dev_status.reset(new std::atomic<int>[1]);
-    front->dev_status[0] = MASP_HIP_OK;
-    *out = front.release();
-    return MASP_HIP_OK;
+    return create_front(devices, n_devices, resolve_options(nullptr), out);
 }
 
 int masp_hip_ctx_device_proofs(const masp_hip_ctx* ctx, uint64_t* counts, int cap) {
@@ -900,14 +837,7 @@ void masp_hip_ctx_destroy(masp_hip_ctx* ctx) {
     ctx->slots.clear();
     for (auto& c : ctx->circ) c.reset();
     ctx->domains.clear();
-    for (size_t i = 0; i < ctx->slot_streams.size(); ++i)    // (streams of slots that were never created)
-        if (!ctx->slot_streams_taken[i])
-            for (int j = 0; j < 5; ++j)
-                if (ctx->slot_streams[i][j] && (j == 0 || slot_owns_side_streams(ctx, i))) hipStreamDestroy(ctx->slot_streams[i][j]);
-    for (hipStream_t v : ctx->vk_streams)
-        if (v) hipStreamDestroy(v);
-    if (ctx->main_stream) hipStreamDestroy(ctx->main_stream);
-    delete ctx;
+    delete ctx;   // (and with it every stream: masp_hip_ctx::streams)
     dev_free_drain();  // the context's buffers
 }
 
@@ -926,7 +856,7 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
     }
     std::unique_lock<std::shared_mutex> lock(ctx->mu);
     hipSetDevice(ctx->device);
-    hipStream_t s = ctx->main_stream;
+    hipStream_t s = ctx->streams.main;
     ParamsLayout L;
     if (!parse_params(params, params_len, L)) return MASP_HIP_E_PARAMS_FORMAT;
     std::unique_ptr<Circuit> C(new Circuit);
@@ -1212,7 +1142,7 @@ int masp_hip_prove_batch(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs, 
         if (!ctx->fault_countdown.compare_exchange_weak(left, left - 1)) continue;
         if (left == 1) {
             last_hip_error() = "injected fault (masp_hip_ctx_inject_fault): this device context's call fails as a lost GPU's would";
-            return fail_shared(ctx, MASP_HIP_E_HIP);
+            return fail(ctx, MASP_HIP_E_HIP);
         }
         break;
     }
@@ -1248,7 +1178,7 @@ int masp_hip_prove_batch(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs, 
         const Group& G = groups[o.gi];
         if (hipEventSynchronize(sl.done) != hipSuccess) {
             last_hip_error() = "event sync failed";
-            result = fail_shared(ctx, MASP_HIP_E_HIP);
+            result = fail(ctx, MASP_HIP_E_HIP);
         } else if (*sl.h_flags) {
             result = MASP_HIP_E_SCALAR_RANGE;
         } else if (result == MASP_HIP_OK) {
@@ -1267,7 +1197,7 @@ int masp_hip_prove_batch(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs, 
 #endif
         rc = slot_try_acquire(ctx, &si);
         if (rc > 0) {
-            result = fail_shared(ctx, rc);
+            result = fail(ctx, rc);
             break;
         }
         if (rc < 0) si = owned.empty() ? slot_acquire_blocking(ctx) : retire_oldest();
@@ -1290,7 +1220,7 @@ int masp_hip_prove_batch(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs, 
         bool ok = true;
         if ((rc = sl.stage_reserve(w_bytes + abc_bytes + rs_bytes + in_bytes)) || (rc = sl.w.reserve(nv * np)) || (rc = sl.inp.reserve((size_t)C.n_inputs * np)) ||
             (rc = sl.abc.reserve(has_abc ? 3 * (size_t)C.nrows * np : 1)) || (rc = sl.reserve_batch(np))) {
-            result = fail_shared(ctx, rc);
+            result = fail(ctx, rc);
             ok = false;
         }
         if (ok) {
@@ -1348,7 +1278,7 @@ int masp_hip_prove_batch(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs, 
 #endif
             if (!ok) {
                 last_hip_error() = std::string("H2D copy failed: ") + hipGetErrorString(hipGetLastError());
-                result = fail_shared(ctx, MASP_HIP_E_HIP);
+                result = fail(ctx, MASP_HIP_E_HIP);
             }
         }
         if (ok) {
@@ -1357,14 +1287,14 @@ int masp_hip_prove_batch(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs, 
                 for (int i = 0; i < 3; ++i) abc[i] = sl.abc.p + (size_t)C.nrows * np * i;
             if (hipMemsetAsync(sl.flags.p, 0, sizeof(int), sl.stream) != hipSuccess) {
                 last_hip_error() = "memset failed";
-                result = fail_shared(ctx, MASP_HIP_E_HIP);
+                result = fail(ctx, MASP_HIP_E_HIP);
                 ok = false;
             } else {
 #ifdef MASP_ENQ_TIMING   // measurement builds only (tools/jobs): how long the host takes to enqueue one group
                 const auto tq0 = std::chrono::steady_clock::now();
 #endif
                 if ((rc = enqueue_proofs_graphed(sl, C, (uint32_t)np, sl.w.p, nv, abc, sl.rs.p, sl.proof.p, jobs[G.idx[0]].aux_form == MASP_HIP_AUX_MONTGOMERY))) {
-                    result = fail_shared(ctx, rc);
+                    result = fail(ctx, rc);
                     ok = false;
                 }
 #ifdef MASP_ENQ_TIMING
@@ -1379,7 +1309,7 @@ int masp_hip_prove_batch(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs, 
                  hipEventRecord(sl.done, s) == hipSuccess;
             if (!ok) {
                 last_hip_error() = "D2H copy failed";
-                result = fail_shared(ctx, MASP_HIP_E_HIP);
+                result = fail(ctx, MASP_HIP_E_HIP);
             }
         }
         if (!ok) {
@@ -1401,10 +1331,10 @@ int masp_hip_prove_batch(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs, 
     if (result == MASP_HIP_OK) ctx->proofs_done += n;
     // a launch the runtime refused on this thread (MASP_LAUNCH keeps the first: kernel, file:line, HIP's text)
     const int launch_rc = launch_status();
-    if (launch_rc && result == MASP_HIP_OK) result = fail_shared(ctx, launch_rc);
+    if (launch_rc && result == MASP_HIP_OK) result = fail(ctx, launch_rc);
     if (hipGetLastError() != hipSuccess && result == MASP_HIP_OK) {
         last_hip_error() = "kernel launch failed";
-        result = fail_shared(ctx, MASP_HIP_E_HIP);
+        result = fail(ctx, MASP_HIP_E_HIP);
     }
     return result;
 }
@@ -1441,7 +1371,7 @@ static int msm_multi(masp_hip_ctx* ctx, const uint8_t* bases, size_t n, const ui
     if (!ctx->children.empty()) ctx = ctx->children[0];
     std::unique_lock<std::shared_mutex> lock(ctx->mu);
     hipSetDevice(ctx->device);
-    hipStream_t s = ctx->main_stream;
+    hipStream_t s = ctx->streams.main;
     for (size_t i = 0; i < n * np; ++i)
         if (!rs_in_range(scalars + 32 * i)) return MASP_HIP_E_SCALAR_RANGE;
     MsmBases<O, BYTES> B;
@@ -1484,7 +1414,7 @@ static int msm_block(masp_hip_ctx* ctx, const uint8_t* bases, const uint8_t* sca
     if (!ctx || !out || (n && (!bases || !scalars)) || n > (1u << 26)) return MASP_HIP_E_INVALID_ARG;
     std::unique_lock<std::shared_mutex> lock(ctx->mu);
     hipSetDevice(ctx->device);
-    hipStream_t s = ctx->main_stream;
+    hipStream_t s = ctx->streams.main;
     for (size_t i = 0; i < n; ++i)
         if (!rs_in_range(scalars + 32 * i)) return MASP_HIP_E_SCALAR_RANGE;
     MsmBases<O, BYTES> B;
@@ -1509,7 +1439,6 @@ static int msm_block(masp_hip_ctx* ctx, const uint8_t* bases, const uint8_t* sca
 extern "C" {
 
 // (a multi-device context runs the building blocks and the measurement hooks on its first device)
-#define FIRST_DEVICE(ctx) ((ctx) && !(ctx)->children.empty() ? (ctx)->children[0] : (ctx))
 
 int masp_hip_msm_g1(masp_hip_ctx* ctx, const uint8_t* bases, const uint8_t* scalars, size_t n, uint8_t out[96]) {
     const ApiLaunchScope api_scope;
@@ -1618,7 +1547,7 @@ int masp_hip_batch_upload(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs)
                 total += (size_t)C.n_inputs + C.n_aux;
             }
     if (B->w.reserve(total) || B->rs.reserve(16 * n)) return -fail(ctx, MASP_HIP_E_HIP);
-    hipStream_t s = ctx->main_stream;
+    hipStream_t s = ctx->streams.main;
     for (size_t k = 0; k < n; ++k) {
         const masp_hip_job& J = jobs[B->order[k]];
         Circuit& C = *ctx->circ[J.circuit];
@@ -1680,7 +1609,7 @@ int masp_hip_batch_prove_resident_steps(masp_hip_ctx* ctx, int handle, size_t st
     DevBuf<uint8_t> d_proofs;
     DevBuf<uint32_t> d_rs;
     if ((rc = d_proofs.reserve(192 * B.n * steps))) return fail(ctx, rc);
-    hipStream_t ms = ctx->main_stream;
+    hipStream_t ms = ctx->streams.main;
     if (rs) {  // step-major, STORAGE order of the jobs inside a step
         std::vector<uint8_t> tmp(64 * B.n * steps);
         for (size_t st = 0; st < steps; ++st)
