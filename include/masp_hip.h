@@ -41,6 +41,7 @@ extern "C" {
 #define MASP_HIP_E_UNEXPECTED_IDENTITY 6  /* delta_g1 / delta_g2 is the identity (bellperson SynthesisError::UnexpectedIdentity) */
 #define MASP_HIP_E_NOT_LOADED 7           /* circuit slot empty */
 #define MASP_HIP_E_SCALAR_RANGE 8         /* a scalar >= r was supplied */
+#define MASP_HIP_E_POINT_ENCODING 9       /* a Jubjub point encoding does not decode (JPoint::from_bytes, ZIP 216 rules) */
 
 #define MASP_HIP_MAX_CIRCUITS 8
 /* conventional slots for the three MASP circuits */
@@ -264,6 +265,25 @@ int masp_hip_vk_prepare(masp_hip_ctx* ctx, const uint8_t* params, size_t params_
 void masp_hip_vk_free(masp_hip_vk* vk);
 int masp_hip_verify_batch(masp_hip_ctx* ctx, masp_hip_vk* vk, size_t n, const uint8_t* proofs, const uint8_t* public_inputs,
                           uint32_t n_public, const uint8_t* z, int* all_valid);
+
+/* ---- RedJubjub batch verification on the GPU ----
+ * masp_hip_jubjub_msm — building block: out32 = the encoding of sum_i [scalars_i] points_i; points n x 32 (Jubjub encodings),
+ * scalars n x 32 (little-endian integers below 2^256).  n <= 2^22; n = 0 gives the identity.  A point that does not decode (v >= r,
+ * u^2 not a square, u = 0 with the sign bit set: what the host's JPoint::from_bytes refuses) -> MASP_HIP_E_POINT_ENCODING with
+ * *bad_index = the first such index (bad_index may be NULL; -1 otherwise).
+ * masp_hip_redjubjub_verify_batch <- redjubjub::batch::Verifier::verify as BatchValidator uses it
+ *    (masp_proofs/src/sapling/verifier/batch.rs:100-113, 188-200, 213).  n items: vk (n x 32), sig = Rbar || Sbar
+ * (n x 64), sighash (n x 32), kind (n bytes: 0 spend authorisation, basepoint spending_key_generator; 1 binding, basepoint
+ * value_commitment_randomness_generator; anything else MASP_HIP_E_INVALID_ARG) and n x 16 B of caller-supplied randomness z (bit 0 of
+ * each z_i is set, so that no item drops out).  c_i = H*(Rbar_i || vk_i || sighash_i) (BLAKE2b-512, personal "MASP__RedJubjubH",
+ * reduced mod r_J).  *all_valid = 1 iff every Rbar_i and vk_i decodes (ZIP 216), every S_i < r_J and
+ *    [8] ( sum_i [z_i] R_i + [z_i c_i] vk_i - [sum_{spend auth} z_i S_i] G_spend - [sum_{binding} z_i S_i] G_binding ) = O,
+ * i.e. (up to 2^-127) every signature verifies; 0 says at least one does not, not which.  n = 0 is valid; n <= 2^20.  H* and the
+ * coefficients are computed on the host; the 2n + 2 point decodings, scalar multiplications and the sum run on the device.
+ * Both: re-entrant next to proving and Groth16 verification calls, on the context's second verifier stream (one call at a time per context). */
+int masp_hip_jubjub_msm(masp_hip_ctx* ctx, size_t n, const uint8_t* points, const uint8_t* scalars, uint8_t out32[32], int64_t* bad_index);
+int masp_hip_redjubjub_verify_batch(masp_hip_ctx* ctx, size_t n, const uint8_t* vks, const uint8_t* sigs, const uint8_t* sighashes,
+                                    const uint8_t* kinds, const uint8_t* z, int* all_valid);
 
 /* ---- measurement hooks (bench.py): device-resident workloads, HIP-event timing on the ctx stream ---- */
 /* Keeps `n` jobs' assignments resident in HBM; returns a handle (>= 0) or a negative error code. */

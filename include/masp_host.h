@@ -87,6 +87,9 @@ void* masp_host_vk_prepare(const uint8_t* params, size_t len);   /* Parameters b
 void masp_host_vk_free(void* h);
 /* public_inputs: n_public x 32, excluding ONE.  1 valid, 0 invalid, < 0 malformed */
 int masp_host_vk_verify(const void* h, const uint8_t proof[192], const uint8_t* public_inputs, uint32_t n_public);
+/* `Proof::read` alone (sapling/verifier/batch.rs:85,125,154): 1 if the proof's three points decode as it requires (canonical, on the
+ * curve, in the prime-order subgroups, not the identity), else 0 */
+int masp_host_proof_read(const uint8_t proof[192]);
 /* n proofs, one random linear combination with the caller's z (n x 16 bytes).  1 all valid, 0 at least one is not, < 0 malformed */
 int masp_host_vk_verify_batch(const void* h, size_t n, const uint8_t* proofs, const uint8_t* public_inputs, uint32_t n_public,
                               const uint8_t* z);

@@ -6,3 +6,5 @@ extension or a GPU is missing, calls raise.
 """
 from .hip import Context, MaspHipError, library_path, load_library  # noqa: F401
 from .r1cs import R1cs  # noqa: F401
+from .verifier import (BatchValidator, Bundle, ConvertDescription, OutputDescription, SaplingVerificationContext,  # noqa: F401
+                       SpendDescription)

@@ -503,6 +503,15 @@ int masp_host_vk_verify(const void* h, const uint8_t proof[192], const uint8_t* 
     bls::Fp12 f = bls::multi_miller(pairs) * vk.alpha_beta.conj();
     return bls::final_exp(f) == bls::Fp12::one() ? 1 : 0;
 }
+// bellman `Proof::read` alone, as BatchValidator::check_bundle calls it before queueing a proof
+// (masp_proofs/src/sapling/verifier/batch.rs:85,125,154): 1 = the three points are canonical, on the curve, in the
+// prime-order subgroups and none is the identity; 0 = refused
+int masp_host_proof_read(const uint8_t proof[192]) {
+    bls::G1A a, c;
+    bls::G2A b;
+    if (!bls::g1_compressed(a, proof) || !bls::g2_compressed(b, proof + 48) || !bls::g1_compressed(c, proof + 144)) return 0;
+    return a.inf || b.inf || c.inf ? 0 : 1;
+}
 // Batched form (bellman `verify_proofs_batch`, reached from /root/reference/masp_proofs/src/sapling/verifier/batch.rs:24-31):
 // with random z_i,  prod_i e(z_i A_i, B_i) == e(alpha,beta)^(sum z_i) e(sum_i z_i acc_i, gamma) e(sum_i z_i C_i, delta).
 // proofs: n x 192 B; public_inputs: n x n_public x 32 B; z: n x 16 B of caller-supplied randomness (128-bit coefficients).

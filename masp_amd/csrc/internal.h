@@ -359,6 +359,12 @@ struct masp_hip_ctx {
     // fixed-base tables of the standard generators (parameter generation)
     DevBuf<G1Affine> fb_g1;
     DevBuf<G2Affine> fb_g2;
+    // the Jubjub entry points (k_redjubjub.hip: masp_hip_jubjub_msm, masp_hip_redjubjub_verify_batch) run next to proving calls on the
+    // verifier stream streams.vk[1], one at a time per context (jj_mu); their work buffers grow on demand and are kept
+    std::mutex jj_mu;
+    DevBuf<uint8_t> jj_points, jj_scalars, jj_partial;
+    DevBuf<int> jj_status;
+    DevBuf<uint32_t> jj_out;
 };
 
 namespace masp {

@@ -1,0 +1,217 @@
+// RedJubjub batch verification on the GPU and the Jubjub multi-scalar sum under it: the C ABI entry points masp_hip_jubjub_msm and
+// masp_hip_redjubjub_verify_batch (include/masp_hip.h).  The latter replaces `signatures.verify(rng)` of BatchValidator::validate
+// (masp_proofs/src/sapling/verifier/batch.rs:213): redjubjub::batch::Verifier over the spend-authorisation items
+// queued at batch.rs:100-113 and the binding items of :188-200.
+//
+// Device (device/jubjub.hpp): k_jj_scale decodes one point per lane with the host's ZIP 216 rules, multiplies it by its scalar and
+// sums its workgroup's products in LDS; k_jj_sum, a second launch, adds the workgroups' sums and writes the encoding of the total (or
+// of [8] total) and whether that is the identity.  Host: H* (BLAKE2b-512), the coefficients z_i c_i and -sum z_i s_i mod r_J, s_i < r_J.
+#include <mutex>
+
+#include "device/jubjub.hpp"
+#include "host/blake2b.h"
+#include "host/jubjub.h"
+#include "internal.h"
+
+using namespace masp;
+
+namespace {
+
+constexpr uint32_t JJ_BLOCK = 256;
+constexpr size_t JJ_MAX_POINTS = (size_t)1 << 22;   // masp_hip_jubjub_msm; a signature batch of 2^20 items sums 2^21 + 2 points
+
+__global__ __launch_bounds__(JJ_BLOCK) void k_jj_scale(const uint4* __restrict__ points, const uint4* __restrict__ scalars, uint32_t n,
+                                                       int* __restrict__ status, JExt* __restrict__ partial) {
+    __shared__ JExt sh[JJ_BLOCK];
+    const uint32_t t = threadIdx.x, i = blockIdx.x * JJ_BLOCK + t;
+    JExt acc = jj_identity();
+    if (i < n) {
+        const uint4 p0 = points[2 * i], p1 = points[2 * i + 1], k0 = scalars[2 * i], k1 = scalars[2 * i + 1];
+        const uint32_t w[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+        const uint32_t k[8] = {k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w};
+        JExt p;
+        const int rc = jj_decode(p, w);
+        status[i] = rc;
+        if (rc == JJ_OK) acc = jj_mul(p, k);
+    }
+    sh[t] = acc;
+    __syncthreads();
+    for (uint32_t s = JJ_BLOCK / 2; s > 0; s >>= 1) {
+        if (t < s) sh[t] = jj_add(sh[t], sh[t + s]);
+        __syncthreads();
+    }
+    if (t == 0) partial[blockIdx.x] = sh[0];
+}
+
+// out[0..7] = the encoding of the sum of nb partial sums (times 8 if `cofactor`), out[8] = 1 if that is the identity
+__global__ __launch_bounds__(JJ_BLOCK) void k_jj_sum(const JExt* __restrict__ partial, uint32_t nb, int cofactor, uint32_t* __restrict__ out) {
+    __shared__ JExt sh[JJ_BLOCK];
+    const uint32_t t = threadIdx.x;
+    JExt acc = jj_identity();
+    for (uint32_t b = t; b < nb; b += JJ_BLOCK) acc = jj_add(acc, partial[b]);
+    sh[t] = acc;
+    __syncthreads();
+    for (uint32_t s = JJ_BLOCK / 2; s > 0; s >>= 1) {
+        if (t < s) sh[t] = jj_add(sh[t], sh[t + s]);
+        __syncthreads();
+    }
+    if (t == 0) {
+        JExt r = sh[0];
+        if (cofactor) r = jj_mul_by_cofactor(r);
+        uint32_t w[8];
+        jj_encode(w, r);
+        for (int i = 0; i < 8; ++i) out[i] = w[i];
+        out[8] = jj_is_identity(r) ? 1u : 0u;
+    }
+}
+
+// sum_i [scalars_i] points_i over m >= 1 points (m x 32 bytes each) on the context's verifier stream.  status (m): 0 or why point i
+// does not decode (its product is left out of the sum); out9: the encoding of the sum, or of [8] sum with `cofactor`, and the identity flag.
+// Caller: ctx->mu shared, ctx->jj_mu held.
+int jj_msm_run(masp_hip_ctx* ctx, size_t m, const uint8_t* points, const uint8_t* scalars, int cofactor, std::vector<int>& status, uint32_t out9[9]) {
+    hipStream_t s = ctx->streams.vk[1];
+    const uint32_t mm = (uint32_t)m, nb = (mm + JJ_BLOCK - 1) / JJ_BLOCK;
+    int rc;
+    if ((rc = ctx->jj_points.upload(points, 32 * m, s)) || (rc = ctx->jj_scalars.upload(scalars, 32 * m, s)) || (rc = ctx->jj_status.reserve(m)) ||
+        (rc = ctx->jj_partial.reserve(sizeof(JExt) * nb)) || (rc = ctx->jj_out.reserve(9)))
+        return fail(ctx, rc);
+    MASP_LAUNCH(k_jj_scale, dim3(nb), dim3(JJ_BLOCK), 0, s, (const uint4*)ctx->jj_points.p, (const uint4*)ctx->jj_scalars.p, mm, ctx->jj_status.p,
+                (JExt*)ctx->jj_partial.p);
+    MASP_LAUNCH(k_jj_sum, dim3(1), dim3(JJ_BLOCK), 0, s, (const JExt*)ctx->jj_partial.p, nb, cofactor, ctx->jj_out.p);
+    status.resize(m);
+    if (hipMemcpyAsync(status.data(), ctx->jj_status.p, sizeof(int) * m, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(out9, ctx->jj_out.p, 9 * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        last_hip_error() = std::string("jubjub multi-scalar sum failed: ") + hipGetErrorString(hipGetLastError());
+        return fail(ctx, MASP_HIP_E_HIP);
+    }
+    if (launch_status() != MASP_HIP_OK) return fail(ctx, MASP_HIP_E_HIP);  // a refused launch: the buffers read back mean nothing
+    return MASP_HIP_OK;
+}
+
+// ---- the Jubjub scalar field (order r_J of the prime-order subgroup), host-side Montgomery arithmetic through field.hpp's host forms ----
+struct RjCfg {
+    static constexpr int N = 8;
+    static constexpr uint32_t MOD[8] = {0xd6f72cb7u, 0xd0970e5eu, 0xccc81082u, 0xa6682093u, 0x01343b00u, 0x06673b01u, 0x6533afa9u, 0x0e7db4eau};
+    static constexpr uint32_t R2[8] = {0x95e57731u, 0x67719aa4u, 0x9ce3fc26u, 0x51b0cef0u, 0xc026e9a5u, 0x69dab7fau, 0x8d127688u, 0x04f6547bu};   // 2^512 mod r_J
+    static constexpr uint32_t INV = 0xef788ef9u;   // -r_J^-1 mod 2^32
+};
+typedef Fe<RjCfg> Rj;
+
+Rj rj_words(const uint8_t* le32) {
+    Rj a;
+    memcpy(a.v, le32, 32);   // (little-endian host)
+    return a;
+}
+// any 256-bit integer -> the Montgomery form of its residue (a < 2^256 = R and R2 < r_J keep CIOS below 2 r_J)
+Rj rj_mont(const uint8_t* le32) {
+    Rj r2;
+    memcpy(r2.v, RjCfg::R2, 32);
+    return fe_mul(rj_words(le32), r2);
+}
+void rj_store(uint8_t* le32, const Rj& mont) {
+    Rj one = fe_zero<RjCfg>();
+    one.v[0] = 1;
+    const Rj c = fe_mul(mont, one);
+    memcpy(le32, c.v, 32);
+}
+// c = H*(Rbar || vk || sighash) = BLAKE2b-512 personalised "MASP__RedJubjubH", the 512-bit digest reduced mod r_J (Montgomery form)
+Rj h_star(const uint8_t* rbar, const uint8_t* vk, const uint8_t* sighash) {
+    masp_host::Blake2b h((const uint8_t*)"MASP__RedJubjubH");
+    h.update(rbar, 32);
+    h.update(vk, 32);
+    h.update(sighash, 32);
+    uint8_t d[64];
+    h.finalize(d);
+    Rj r2;
+    memcpy(r2.v, RjCfg::R2, 32);
+    return fe_add(rj_mont(d), fe_mul(rj_mont(d + 32), r2));   // lo + hi 2^256: mont(hi 2^256) = mont(hi) R^2 / R
+}
+
+// the two basepoints' encodings: spending_key_generator, value_commitment_randomness_generator
+const uint8_t* basepoints() {
+    static const std::array<uint8_t, 64> b = [] {
+        std::array<uint8_t, 64> x;
+        masp_host::generators().spending_key.to_bytes(x.data());
+        masp_host::generators().value_commitment_randomness.to_bytes(x.data() + 32);
+        return x;
+    }();
+    return b.data();
+}
+
+}  // namespace
+
+extern "C" {
+
+int masp_hip_jubjub_msm(masp_hip_ctx* ctx, size_t n, const uint8_t* points, const uint8_t* scalars, uint8_t out32[32], int64_t* bad_index) {
+    if (bad_index) *bad_index = -1;
+    if (!ctx || !out32 || (n && (!points || !scalars)) || n > JJ_MAX_POINTS) return MASP_HIP_E_INVALID_ARG;
+    if (n == 0) {
+        memset(out32, 0, 32);
+        out32[0] = 1;   // the identity (0, 1)
+        return MASP_HIP_OK;
+    }
+    const ApiLaunchScope api_scope;
+    ctx = FIRST_DEVICE(ctx);
+    std::shared_lock<std::shared_mutex> lock(ctx->mu);   // concurrent with provers and verifiers
+    std::lock_guard<std::mutex> jlock(ctx->jj_mu);
+    hipSetDevice(ctx->device);
+    std::vector<int> status;
+    uint32_t out9[9];
+    int rc = jj_msm_run(ctx, n, points, scalars, 0, status, out9);
+    if (rc) return rc;
+    for (size_t i = 0; i < n; ++i)
+        if (status[i]) {
+            if (bad_index) *bad_index = (int64_t)i;
+            return MASP_HIP_E_POINT_ENCODING;
+        }
+    memcpy(out32, out9, 32);
+    return MASP_HIP_OK;
+}
+
+int masp_hip_redjubjub_verify_batch(masp_hip_ctx* ctx, size_t n, const uint8_t* vks, const uint8_t* sigs, const uint8_t* sighashes,
+                                    const uint8_t* kinds, const uint8_t* z, int* all_valid) {
+    if (!ctx || !all_valid || (n && (!vks || !sigs || !sighashes || !kinds || !z)) || n > (1u << 20)) return MASP_HIP_E_INVALID_ARG;
+    *all_valid = 0;
+    for (size_t i = 0; i < n; ++i)
+        if (kinds[i] > 1) return MASP_HIP_E_INVALID_ARG;
+    if (n == 0) {
+        *all_valid = 1;
+        return MASP_HIP_OK;
+    }
+    // host: points R_0 .. R_n-1, vk_0 .. vk_n-1, G_spend_auth, G_binding with scalars z_i, z_i c_i, -sum z_i s_i per basepoint
+    const size_t m = 2 * n + 2;
+    std::vector<uint8_t> pts(32 * m), sc(32 * m, 0);
+    Rj acc[2] = {fe_zero<RjCfg>(), fe_zero<RjCfg>()};
+    for (size_t i = 0; i < n; ++i) {
+        const uint8_t *sig = sigs + 64 * i, *vk = vks + 32 * i;
+        const Rj s = rj_words(sig + 32);
+        if (fe_canonical_ge_mod(s)) return MASP_HIP_OK;   // S >= r_J: not a signature (*all_valid stays 0)
+        uint8_t zi[32] = {0};
+        memcpy(zi, z + 16 * i, 16);
+        zi[0] |= 1;   // never zero (as masp_hip_verify_batch): an item with z = 0 would drop out of the check
+        const Rj zm = rj_mont(zi);
+        memcpy(&pts[32 * i], sig, 32);
+        memcpy(&pts[32 * (n + i)], vk, 32);
+        memcpy(&sc[32 * i], zi, 32);
+        rj_store(&sc[32 * (n + i)], fe_mul(zm, h_star(sig, vk, sighashes + 32 * i)));
+        acc[kinds[i]] = fe_add(acc[kinds[i]], fe_mul(zm, rj_mont(sig + 32)));
+    }
+    memcpy(&pts[32 * 2 * n], basepoints(), 64);
+    rj_store(&sc[32 * 2 * n], fe_neg(acc[0]));
+    rj_store(&sc[32 * (2 * n + 1)], fe_neg(acc[1]));
+    const ApiLaunchScope api_scope;
+    ctx = FIRST_DEVICE(ctx);
+    std::shared_lock<std::shared_mutex> lock(ctx->mu);
+    std::lock_guard<std::mutex> jlock(ctx->jj_mu);
+    hipSetDevice(ctx->device);
+    std::vector<int> status;
+    uint32_t out9[9];
+    int rc = jj_msm_run(ctx, m, pts.data(), sc.data(), 1, status, out9);
+    if (rc) return rc;
+    for (int st : status)
+        if (st) return MASP_HIP_OK;   // an R or vk that does not decode: not valid
+    *all_valid = out9[8] == 1;
+    return MASP_HIP_OK;
+}
+
+}  // extern "C"

@@ -9,7 +9,9 @@ _lib = None
 
 ERRORS = {1: "invalid argument", 2: "Parameters bytes are malformed", 3: "Parameters do not match the circuit shape",
           4: "no usable HIP device (there is no CPU fallback)", 5: "HIP runtime error", 6: "UnexpectedIdentity",
-          7: "circuit slot is empty", 8: "scalar is not a canonical field element"}
+          7: "circuit slot is empty", 8: "scalar is not a canonical field element", 9: "a Jubjub point encoding does not decode"}
+E_POINT_ENCODING = 9
+SPEND_AUTH, BINDING = 0, 1      # masp_hip_redjubjub_verify_batch kinds
 
 SPEND, OUTPUT, CONVERT = 0, 1, 2
 
@@ -119,6 +121,9 @@ def load_library():
     L.masp_hip_vk_free.argtypes = [vp]
     L.masp_hip_vk_free.restype = None
     L.masp_hip_verify_batch.argtypes = [vp, vp, sz, vp, vp, u32, vp, C.POINTER(C.c_int)]
+    if hasattr(L, "masp_hip_redjubjub_verify_batch"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
+        L.masp_hip_jubjub_msm.argtypes = [vp, sz, vp, vp, vp, C.POINTER(C.c_int64)]
+        L.masp_hip_redjubjub_verify_batch.argtypes = [vp, sz, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int)]
     L.masp_hip_batch_upload.argtypes = [vp, sz, vp]
     L.masp_hip_batch_prove_resident.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.masp_hip_batch_prove_resident_steps.argtypes = [vp, C.c_int, sz, vp, vp, C.POINTER(C.c_float)]
@@ -320,6 +325,45 @@ class Context:
     def prepare_verifying_key(self, params):
         """-> GpuVerifyingKey (= PreparedVerifyingKey, masp_proofs/src/lib.rs:391-393, for masp_hip_verify_batch)"""
         return GpuVerifyingKey(self, params)
+
+    # ---- RedJubjub batch verification on the GPU ----
+    def redjubjub_verify_batch(self, items, randomness=None):
+        """items: (vk[32], sig[64] = Rbar || Sbar, sighash[32], kind) with kind SPEND_AUTH (basepoint spending_key_generator) or BINDING
+        (value_commitment_randomness_generator) -> True iff every signature verifies (up to 2^-127): redjubjub::batch::Verifier::verify
+        (masp_hip_redjubjub_verify_batch).  randomness: 16 bytes per item (default: from `secrets`)."""
+        import secrets
+        items = list(items)
+        n = len(items)
+        if n == 0:
+            return True
+        vks, sigs, sighashes = (b"".join(bytes(it[k]) for it in items) for k in range(3))
+        if len(vks) != 32 * n or len(sigs) != 64 * n or len(sighashes) != 32 * n:
+            return False
+        kinds = bytes(int(it[3]) for it in items)
+        z = randomness if randomness is not None else secrets.token_bytes(16 * n)
+        assert len(z) == 16 * n
+        ok = C.c_int(0)
+        self._check(self._L.masp_hip_redjubjub_verify_batch(self._h, n, vks, sigs, sighashes, kinds, bytes(z), C.byref(ok)))
+        return ok.value == 1
+
+    def jubjub_msm(self, points, scalars):
+        """sum_i [scalars_i] points_i over Jubjub (masp_hip_jubjub_msm): points = 32-byte encodings, scalars = ints below 2^256 or 32-byte
+        little-endian values -> the 32-byte encoding of the sum.  A point that does not decode raises MaspHipError (code 9) with
+        `.bad_index` set to the first such index."""
+        n = len(points)
+        assert len(scalars) == n
+        pts = np.frombuffer(b"".join(bytes(p) for p in points), dtype=np.uint8)
+        sc = np.frombuffer(b"".join(_scalar32(s) for s in scalars), dtype=np.uint8)
+        assert pts.size == 32 * n and sc.size == 32 * n
+        out = np.zeros(32, dtype=np.uint8)
+        bad = C.c_int64(-1)
+        rc = self._L.masp_hip_jubjub_msm(self._h, n, _p(pts), _p(sc), _p(out), C.byref(bad))
+        if rc == E_POINT_ENCODING:
+            e = MaspHipError(rc, "point %d" % bad.value)
+            e.bad_index = bad.value
+            raise e
+        self._check(rc)
+        return out.tobytes()
 
     # ---- building blocks ----
     def msm_g1(self, bases, scalars):

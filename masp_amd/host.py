@@ -60,6 +60,7 @@ def load_library():
         L.masp_host_vk_free.argtypes = [vp]
         L.masp_host_vk_verify.argtypes = [vp, cp, cp, C.c_uint32]
         L.masp_host_vk_verify_batch.argtypes = [vp, C.c_size_t, cp, cp, C.c_uint32, cp]
+        L.masp_host_proof_read.argtypes = [cp]
         L.masp_host_point_uv.argtypes = [cp, cp]
         L.masp_host_jubjub_add.argtypes = [cp, cp, C.c_int, cp]
         L.masp_host_jubjub_sum.argtypes = [cp, cp, C.c_size_t, cp, cp]
@@ -298,6 +299,12 @@ class PreparedVerifyingKey:
         if getattr(self, "_h", None):
             self._L.masp_host_vk_free(self._h)
             self._h = None
+
+
+def proof_read(proof):
+    """bellman `Proof::read` alone (masp_host_proof_read): True if the 192 bytes are three points it accepts."""
+    proof = bytes(proof)
+    return len(proof) == 192 and load_library().masp_host_proof_read(proof) == 1
 
 
 # ---- native primitives ----

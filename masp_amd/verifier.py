@@ -1,0 +1,238 @@
+"""Node-side validation of MASP bundles: the verifier half of the `masp_proofs` API.
+
+    SaplingVerificationContextInner   masp_proofs/src/sapling/verifier.rs:20-204
+    SaplingVerificationContext        masp_proofs/src/sapling/verifier/single.rs
+    BatchValidator                    masp_proofs/src/sapling/verifier/batch.rs:40-239
+
+Types cross this API in their wire encodings, as in prover.py: Jubjub points as 32-byte `to_bytes()` encodings, field elements as
+ints or 32-byte little-endian values, proofs as 192 bytes, RedJubjub signatures as 64 bytes Rbar || Sbar.  A cv, rk or epk that does
+not decode (ZIP 216 rules) makes its bundle invalid, as the reference's deserialisation of the bundle would.  The consensus checks are
+host-side; `BatchValidator.validate` makes one RedJubjub batch call on the GPU (masp_hip_redjubjub_verify_batch) and one Groth16 batch
+call per non-empty circuit batch (masp_hip_verify_batch).
+"""
+import secrets
+from dataclasses import dataclass
+
+from . import host as H
+from . import redjubjub as RJS
+from .hip import BINDING, SPEND_AUTH
+
+I128_MIN, I128_MAX = -(1 << 127), (1 << 127) - 1
+
+
+@dataclass
+class SpendDescription:
+    cv: bytes
+    anchor: object            # bls12_381::Scalar: int or 32 bytes LE
+    nullifier: bytes
+    rk: bytes
+    zkproof: bytes
+    spend_auth_sig: bytes
+
+
+@dataclass
+class ConvertDescription:
+    cv: bytes
+    anchor: object
+    zkproof: bytes
+
+
+@dataclass
+class OutputDescription:
+    cv: bytes
+    cmu: object               # bls12_381::Scalar: int or 32 bytes LE
+    ephemeral_key: bytes
+    zkproof: bytes
+
+
+@dataclass
+class Bundle:
+    spends: list
+    converts: list
+    outputs: list
+    value_balance: list       # [(asset identifier[32], i128)]: the components of the reference's I128Sum, as binding_sig takes them
+    binding_sig: bytes
+
+
+def spending_key_generator():
+    return H.point_bytes(*H.generator_uv(4))
+
+
+def value_commitment_randomness_generator():
+    return H.point_bytes(*H.generator_uv(3))
+
+
+def _int(x):
+    return x if isinstance(x, int) else int.from_bytes(bytes(x), "little")
+
+
+def decodes(p):
+    """ExtendedPoint::from_bytes succeeds (canonical v, u^2 a square, no negative zero)."""
+    try:
+        H.point_uv(bytes(p))
+        return True
+    except ValueError:
+        return False
+
+
+def is_small_order(p):
+    return H.jubjub_mul(bytes(p), 8) == H.JUBJUB_IDENTITY
+
+
+def spend_public_inputs(cv, anchor, nullifier, rk):
+    """verifier.rs:71-95: rk.u, rk.v, cv.u, cv.v, anchor, the nullifier multipacked into two 254-bit chunks."""
+    return list(H.point_uv(bytes(rk))) + list(H.point_uv(bytes(cv))) + [_int(anchor)] + H.multipack(bytes(nullifier))
+
+
+def convert_public_inputs(cv, anchor):
+    """verifier.rs:120-128: cv.u, cv.v, anchor."""
+    return list(H.point_uv(bytes(cv))) + [_int(anchor)]
+
+
+def output_public_inputs(cv, cmu, epk):
+    """verifier.rs:151-165: cv.u, cv.v, epk.u, epk.v, cmu."""
+    return list(H.point_uv(bytes(cv))) + list(H.point_uv(bytes(epk))) + [_int(cmu)]
+
+
+class _Inner:
+    """SaplingVerificationContextInner (verifier.rs:20-204): cv_sum and the consensus checks; the signature and proof checks are the
+    caller's callbacks, as in the reference."""
+
+    def __init__(self):
+        self.cv_sum = H.JUBJUB_IDENTITY
+
+    def check_spend(self, cv, anchor, nullifier, rk, sighash, spend_auth_sig, zkproof, sig_check, proof_check):
+        if is_small_order(cv) or is_small_order(rk):
+            return False
+        self.cv_sum = H.jubjub_add(self.cv_sum, cv)
+        if not sig_check(rk, bytes(rk) + bytes(sighash), spend_auth_sig):
+            return False
+        return proof_check(zkproof, spend_public_inputs(cv, anchor, nullifier, rk))
+
+    def check_convert(self, cv, anchor, zkproof, proof_check):
+        if is_small_order(cv):
+            return False
+        self.cv_sum = H.jubjub_add(self.cv_sum, cv)
+        return proof_check(zkproof, convert_public_inputs(cv, anchor))
+
+    def check_output(self, cv, cmu, epk, zkproof, proof_check):
+        if is_small_order(cv) or is_small_order(epk):
+            return False
+        self.cv_sum = H.jubjub_add(self.cv_sum, cv, subtract=True)
+        return proof_check(zkproof, output_public_inputs(cv, cmu, epk))
+
+    def bvk(self, value_balance):
+        """cv_sum - sum of [value] value_commitment_generator(asset) (masp_compute_value_balance, sapling/mod.rs:14-38); None when a
+        value has no absolute value in i128 (i128::MIN) or an asset identifier has no generator."""
+        bvk = self.cv_sum
+        for asset, value in value_balance:
+            value = int(value)
+            if not I128_MIN < value <= I128_MAX:
+                return None
+            try:
+                vb = H.jubjub_mul(H.jubjub_mul(H.asset_generator(asset), 8), abs(value))
+            except ValueError:
+                return None
+            bvk = H.jubjub_add(bvk, vb, subtract=value >= 0)
+        return bvk
+
+    def final_check(self, value_balance, sighash, binding_sig, sig_check):
+        bvk = self.bvk(value_balance)
+        if bvk is None:
+            return False
+        return sig_check(bvk, bvk + bytes(sighash), binding_sig)
+
+
+class SaplingVerificationContext:
+    """= SaplingVerificationContext (verifier/single.rs), ZIP 216 on: signatures by `redjubjub.verify` and proofs by a verifying key's
+    `verify(proof, public_inputs)` (host.PreparedVerifyingKey), one at a time on the host.  Points that do not decode are refused."""
+
+    def __init__(self):
+        self._inner = _Inner()
+
+    @property
+    def cv_sum(self):
+        return self._inner.cv_sum
+
+    def check_spend(self, cv, anchor, nullifier, rk, sighash, spend_auth_sig, zkproof, verifying_key):
+        if not (decodes(cv) and decodes(rk)):
+            return False
+        g = spending_key_generator()
+        return self._inner.check_spend(cv, anchor, nullifier, rk, sighash, spend_auth_sig, zkproof,
+                                       lambda vk, msg, sig: RJS.verify(vk, msg, bytes(sig), g),
+                                       lambda proof, pi: verifying_key.verify(proof, pi))
+
+    def check_convert(self, cv, anchor, zkproof, verifying_key):
+        if not decodes(cv):
+            return False
+        return self._inner.check_convert(cv, anchor, zkproof, lambda proof, pi: verifying_key.verify(proof, pi))
+
+    def check_output(self, cv, cmu, epk, zkproof, verifying_key):
+        if not (decodes(cv) and decodes(epk)):
+            return False
+        return self._inner.check_output(cv, cmu, epk, zkproof, lambda proof, pi: verifying_key.verify(proof, pi))
+
+    def final_check(self, value_balance, sighash, binding_sig):
+        g = value_commitment_randomness_generator()
+        return self._inner.final_check(value_balance, sighash, binding_sig, lambda vk, msg, sig: RJS.verify(vk, msg, bytes(sig), g))
+
+
+class BatchValidator:
+    """= BatchValidator (verifier/batch.rs:40-239) over one `hip.Context`: check_bundle runs the consensus checks on the host and queues
+    proofs (per circuit) and signatures; validate verifies everything queued in one RedJubjub batch and one Groth16 batch per circuit on
+    the GPU.  Several validators may share a context and run in different threads."""
+
+    def __init__(self, context):
+        self._ctx = context
+        self._bundles_added = False
+        self._proofs = {"spend": ([], []), "convert": ([], []), "output": ([], [])}
+        self._signatures = []            # (vk, sig, sighash, kind)
+
+    def _queue_proof(self, kind, proof, public_inputs):
+        self._proofs[kind][0].append(bytes(proof))
+        self._proofs[kind][1].append(public_inputs)
+        return True
+
+    def _queue_sig(self, vk, sig, sighash, kind):
+        self._signatures.append((bytes(vk), bytes(sig), bytes(sighash), kind))
+        return True
+
+    def check_bundle(self, bundle, sighash):
+        """batch.rs:78-193.  False if the bundle breaks a consensus rule checked here (a proof `Proof::read` refuses, a cv / rk / epk that
+        does not decode or has small order, a bad value balance); what was queued before that stays queued, as in the reference."""
+        self._bundles_added = True
+        sighash = bytes(sighash)
+        ctx = _Inner()
+        for d in bundle.spends:
+            if not (decodes(d.cv) and decodes(d.rk)) or not H.proof_read(d.zkproof):
+                return False
+            if not ctx.check_spend(d.cv, d.anchor, d.nullifier, d.rk, sighash, d.spend_auth_sig, d.zkproof,
+                                   lambda vk, msg, sig: self._queue_sig(vk, sig, sighash, SPEND_AUTH),
+                                   lambda proof, pi: self._queue_proof("spend", proof, pi)):
+                return False
+        for d in bundle.converts:
+            if not decodes(d.cv) or not H.proof_read(d.zkproof):
+                return False
+            if not ctx.check_convert(d.cv, d.anchor, d.zkproof, lambda proof, pi: self._queue_proof("convert", proof, pi)):
+                return False
+        for d in bundle.outputs:
+            if not (decodes(d.cv) and decodes(d.ephemeral_key)) or not H.proof_read(d.zkproof):
+                return False
+            if not ctx.check_output(d.cv, d.cmu, d.ephemeral_key, d.zkproof, lambda proof, pi: self._queue_proof("output", proof, pi)):
+                return False
+        return ctx.final_check(bundle.value_balance, sighash, bundle.binding_sig,
+                               lambda vk, msg, sig: self._queue_sig(vk, sig, sighash, BINDING))
+
+    def validate(self, spend_vk, convert_vk, output_vk, rng=None):
+        """batch.rs:201-239.  The vks are hip.GpuVerifyingKey objects; rng(k) -> k random bytes (default: secrets.token_bytes).  True when
+        no bundle was added; otherwise True iff every queued signature and proof verifies."""
+        if not self._bundles_added:
+            return True
+        rng = rng or secrets.token_bytes
+        if self._signatures and not self._ctx.redjubjub_verify_batch(self._signatures, randomness=rng(16 * len(self._signatures))):
+            return False
+        for kind, vk in (("spend", spend_vk), ("convert", convert_vk), ("output", output_vk)):
+            proofs, inputs = self._proofs[kind]
+            if proofs and not vk.verify_batch(proofs, inputs, randomness=rng(16 * len(proofs))):
+                return False
+        return True

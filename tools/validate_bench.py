@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""RedJubjub batch verification and bundle validation on one GPU -> one JSON line.
+
+    python tools/validate_bench.py [--sizes 1,64,1024,16384] [--bundles 8] [--reps 5] [--host-subset 64]
+
+redjubjub_verify_batch: wall time of Context.redjubjub_verify_batch at each n (median of --reps after one warm-up call), split into
+`device_ms` = Context.jubjub_msm over the same 2n + 2 points and scalars (upload, the two kernels, read-back; the scalars are computed
+beforehand in Python) and `host_ms` = the rest (H*, the coefficients mod r_J, packing the arguments).  `host_verify_ms_per_sig`:
+masp_amd.redjubjub.verify one signature at a time on a subset.  Bundles: B bundles of two Spends, one Convert and two Outputs built as
+tests/test_gpu_batch_validator.py builds them; `check_bundle_ms` per bundle (host) and `validate_ms` for all B (one signature batch and
+three Groth16 batches on the GPU)."""
+import argparse
+import json
+import os
+import random
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+from masp_amd import host as H  # noqa: E402
+from masp_amd import redjubjub as RJS  # noqa: E402
+from masp_amd.hip import Context  # noqa: E402
+
+RJ = H.JUBJUB_ORDER
+GENS = [H.point_bytes(*H.generator_uv(4)), H.point_bytes(*H.generator_uv(3))]
+
+
+def signatures(rng, n):
+    items = []
+    for i in range(n):
+        kind = i % 2
+        sk = rng.randrange(1, RJ)
+        vk = RJS.public_key(sk, GENS[kind])
+        sighash = bytes(rng.getrandbits(8) for _ in range(32))
+        items.append((vk, RJS.sign(sk, vk + sighash, GENS[kind], rng=lambda k: bytes(rng.getrandbits(8) for _ in range(k))), sighash, kind))
+    return items
+
+
+def msm_arguments(items, z):
+    """the 2n + 2 points and scalars masp_hip_redjubjub_verify_batch hands to the device"""
+    pts, sc, acc = [], [], [0, 0]
+    for i, (vk, sig, sighash, kind) in enumerate(items):
+        zi = int.from_bytes(z[16 * i:16 * i + 16], "little") | 1
+        pts.append(sig[:32])
+        sc.append(zi)
+        acc[kind] = (acc[kind] + zi * int.from_bytes(sig[32:], "little")) % RJ
+    for i, (vk, sig, sighash, kind) in enumerate(items):
+        zi = int.from_bytes(z[16 * i:16 * i + 16], "little") | 1
+        pts.append(vk)
+        sc.append(zi * RJS.h_star(sig[:32], vk + sighash) % RJ)
+    return pts + GENS, sc + [(-acc[0]) % RJ, (-acc[1]) % RJ]
+
+
+def timed(fn, reps):
+    fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        out = fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ts), out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="1,64,1024,16384")
+    ap.add_argument("--bundles", type=int, default=8)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--host-subset", type=int, default=64)
+    a = ap.parse_args()
+    rng = random.Random(1)
+    sizes = [int(x) for x in a.sizes.split(",")]
+    items = signatures(rng, max(sizes))
+    ctx = Context(0)
+    res = {"metric": "redjubjub_validate", "redjubjub_verify_batch": {}}
+    for n in sizes:
+        batch = items[:n]
+        z = bytes(rng.getrandbits(8) for _ in range(16 * n))
+        total, ok = timed(lambda: ctx.redjubjub_verify_batch(batch, randomness=z), a.reps)
+        pts, sc = msm_arguments(batch, z)
+        dev, enc = timed(lambda: ctx.jubjub_msm(pts, sc), a.reps)
+        assert ok is True and H.jubjub_mul(enc, 8) == H.JUBJUB_IDENTITY
+        res["redjubjub_verify_batch"][str(n)] = {"total_ms": round(total, 3), "device_ms": round(dev, 3), "host_ms": round(total - dev, 3),
+                                                 "us_per_sig": round(1e3 * total / n, 2)}
+    sub = items[:a.host_subset]
+    t0 = time.perf_counter()
+    assert all(RJS.verify(vk, vk + sh, sig, GENS[k]) for vk, sig, sh, k in sub)
+    res["host_verify_ms_per_sig"] = round((time.perf_counter() - t0) * 1e3 / len(sub), 3)
+    res["host_verify_subset"] = len(sub)
+    ctx.close()
+    if a.bundles:
+        from masp_amd import prover as P
+        from masp_amd import verifier as V
+        from test_gpu_batch_validator import _prepare_bundle
+        lp = P.LocalTxProver.with_synthetic_parameters(seed=11)
+        prepared = [_prepare_bundle(lp, rng) for _ in range(a.bundles)]
+        jobs = [j for js, _ in prepared for j in js]
+        proofs = lp.prove_prepared(jobs)
+        lp._aux_give(jobs)
+        bundles = [finish(proofs[5 * i:5 * i + 5]) for i, (_, finish) in enumerate(prepared)]
+        vks = (lp._gpu_vk["spend"], lp._gpu_vk["convert"], lp._ctx.prepare_verifying_key(lp.parameters["output"]))
+        checks, vals = [], []
+        for _ in range(a.reps + 1):
+            bv = V.BatchValidator(lp._ctx)
+            t0 = time.perf_counter()
+            assert all(bv.check_bundle(b, s) for b, s, _ in bundles)
+            t1 = time.perf_counter()
+            assert bv.validate(*vks) is True
+            t2 = time.perf_counter()
+            checks.append((t1 - t0) * 1e3 / len(bundles))
+            vals.append((t2 - t1) * 1e3)
+        res["bundles"] = {"B": len(bundles), "shape": "2 spends, 1 convert, 2 outputs", "check_bundle_ms": round(statistics.median(checks[1:]), 3),
+                          "validate_ms": round(statistics.median(vals[1:]), 3)}
+        vks[2].close()
+        lp.close()
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
