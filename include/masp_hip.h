@@ -42,6 +42,7 @@ extern "C" {
 #define MASP_HIP_E_NOT_LOADED 7           /* circuit slot empty */
 #define MASP_HIP_E_SCALAR_RANGE 8         /* a scalar >= r was supplied */
 #define MASP_HIP_E_POINT_ENCODING 9       /* a Jubjub point encoding does not decode (JPoint::from_bytes, ZIP 216 rules) */
+#define MASP_HIP_E_CAPACITY 10            /* an output buffer of the caller is too small: the call says how much it needs */
 
 #define MASP_HIP_MAX_CIRCUITS 8
 /* conventional slots for the three MASP circuits */
@@ -284,6 +285,33 @@ int masp_hip_verify_batch(masp_hip_ctx* ctx, masp_hip_vk* vk, size_t n, const ui
 int masp_hip_jubjub_msm(masp_hip_ctx* ctx, size_t n, const uint8_t* points, const uint8_t* scalars, uint8_t out32[32], int64_t* bad_index);
 int masp_hip_redjubjub_verify_batch(masp_hip_ctx* ctx, size_t n, const uint8_t* vks, const uint8_t* sigs, const uint8_t* sighashes,
                                     const uint8_t* kinds, const uint8_t* z, int* all_valid);
+
+/* ---- Batch trial decryption of Sapling notes on the GPU ----
+ * masp_hip_sapling_trial_decrypt <- the device half of masp_note_encryption::batch::try_note_decryption over SaplingDomain
+ *    (masp_note_encryption/src/batch.rs:43-86): for each of the n_out x n_ivk (output, ivk) pairs the key agreement [8 ivk] epk, the KDF
+ * (BLAKE2b-256, personal "MASP__SaplingKDF", over the secret's encoding and the epk bytes) and the Poly1305 tag of the AEAD over the
+ * ciphertext.  ivks: n_ivk x 32, canonical scalars below r_J, anything else MASP_HIP_E_INVALID_ARG (a SaplingIvk is a canonical scalar);
+ * epks: n_out x 32; enc_ciphertexts: n_out x 612 (596 bytes under ChaCha20, then the tag).  n_ivk <= 4096, n_out <= 2^26.
+ * epk_status (n_out bytes, may be NULL): 0, or why output i's epk does not decode (1 v >= r, 2 not on the curve, 3 u = 0 with the sign bit
+ * set: Domain::epk gives None, ZIP 216); such an output takes no part and has no hit.
+ * Result: *n_hits pairs whose tag verifies, sorted by (output, ivk): hit_output[i], hit_ivk[i], and the symmetric key hit_keys[32 i ..].
+ * The device does NOT decrypt: a hit goes on to masp_host_sapling_finish_note_decryption (include/masp_host.h) with its key, which decrypts,
+ * parses and checks the commitment; of an output's hits the first whose finish succeeds is the reference's answer.  If *n_hits >
+ * hit_capacity the call returns MASP_HIP_E_CAPACITY with *n_hits = the number of pairs found and writes no hit (nothing is dropped
+ * silently: call again with room; n_out x n_ivk always suffices).  n_ivk = 0 or n_out = 0: no hits, no GPU work (epk_status all 0).
+ * The result is deterministic.  Large calls are cut into chunks of outputs whose upload overlaps the chunk before's kernels.  Re-entrant next
+ * to proving and verification calls, on the context's two verifier streams (one scan at a time per context); on a multi-device context the
+ * scan runs on the first device.
+ * masp_hip_note_scan_configure — measurement knobs, kept because the A/B they serve is repeated on every new compiler: signed_digits 1 = the
+ * ivks' non-adjacent forms (a third fewer additions), 0 = their plain bits; inversion 0 = the divstep inverse, 1 = the binary-gcd inverse
+ * for the encoding of the shared secret.  Results do not depend on either.  KERNELS.md records what was measured and the defaults.
+ * masp_hip_note_scan_last_timing — of the last scan of this context, summed over its chunks from HIP events on their streams: ms[0] the
+ * host-to-device copies, ms[1] the kernels (with two chunks in flight a chunk's kernels may wait for the other's: stream time). */
+int masp_hip_sapling_trial_decrypt(masp_hip_ctx* ctx, size_t n_ivk, const uint8_t* ivks, size_t n_out, const uint8_t* epks,
+                                   const uint8_t* enc_ciphertexts, uint8_t* epk_status, size_t hit_capacity, uint32_t* hit_output,
+                                   uint32_t* hit_ivk, uint8_t* hit_keys, size_t* n_hits);
+int masp_hip_note_scan_configure(masp_hip_ctx* ctx, int signed_digits, int inversion);
+int masp_hip_note_scan_last_timing(masp_hip_ctx* ctx, double ms[2]);
 
 /* ---- measurement hooks (bench.py): device-resident workloads, HIP-event timing on the ctx stream ---- */
 /* Keeps `n` jobs' assignments resident in HBM; returns a handle (>= 0) or a negative error code. */

@@ -27,6 +27,7 @@ extern "C" {
 #define MASP_HOST_E_DIVERSIFIER 2   /* the diversifier has no group hash: the reference's Err(()) at sapling/prover.rs:84 */
 #define MASP_HOST_E_SYNTHESIS 3     /* bellperson's SynthesisError */
 #define MASP_HOST_E_UNSATISFIED 4   /* check & 1: a constraint does not hold */
+#define MASP_HOST_E_NO_NOTE 5       /* trial decryption: the output is not a note of this key (the reference's None) */
 
 /* `kind` everywhere: 0 Spend, 1 Output, 2 Convert (= MASP_HIP_SPEND / _OUTPUT / _CONVERT) */
 
@@ -121,6 +122,42 @@ int masp_host_spend_leaf(const uint8_t ak[32], const uint8_t nsk[32], const uint
 int masp_host_allowed_conversion(size_t n, const uint8_t* identifiers, const uint8_t* values, uint8_t generator_out[32]);
 /* leaf of the convert tree (convert.rs:39-64) */
 int masp_host_convert_cmu(const uint8_t generator[32], uint8_t out32[32]);
+
+/* ---- Sapling note encryption and trial decryption (masp_note_encryption, masp_primitives/src/sapling/note_encryption.rs).
+ * A note plaintext is 596 bytes: lead byte (1: rcm follows, 2: a ZIP 212 rseed follows) | diversifier 11 | value u64 LE | asset identifier 32 |
+ * rcm or rseed 32 | memo 512; enc_ciphertext is those 596 bytes under ChaCha20-Poly1305 (all-zero nonce, no associated data) and the
+ * 16-byte tag.  ivk, esk: canonical scalars below r_J, else MASP_HOST_E_INVALID.  Out of scope: out_ciphertext, recovery with an ovk. ---- */
+/* sapling_ka_agree: [8 sk] P as 32 bytes */
+int masp_host_sapling_ka_agree(const uint8_t sk[32], const uint8_t p32[32], uint8_t out32[32]);
+/* Diversifier::g_d as 32 bytes; MASP_HOST_E_DIVERSIFIER if the diversifier has none (pk_d = [ivk] g_d makes a payment address) */
+int masp_host_diversifier_base(const uint8_t diversifier[11], uint8_t out32[32]);
+/* kdf_sapling: BLAKE2b-256 personalised "MASP__SaplingKDF" over secret | epk */
+void masp_host_kdf_sapling(const uint8_t secret[32], const uint8_t epk[32], uint8_t key32[32]);
+/* PRF^expand: BLAKE2b-512 personalised "MASP__ExpandSeed" over sk | t */
+void masp_host_prf_expand(const uint8_t* sk, size_t sklen, const uint8_t* t, size_t tlen, uint8_t out64[64]);
+/* PRF^expand(rseed, [domain]) reduced mod r_J: domain 4 = rcm, 5 = esk of a ZIP 212 note */
+void masp_host_sapling_rseed_scalar(const uint8_t rseed[32], int domain, uint8_t out32[32]);
+/* the AEAD alone (RFC 8439, no associated data); decrypt: MASP_HOST_E_NO_NOTE if the tag does not verify */
+void masp_host_chacha20poly1305_encrypt(const uint8_t key[32], const uint8_t nonce[12], const uint8_t* plaintext, size_t n, uint8_t* ciphertext,
+                                        uint8_t tag[16]);
+int masp_host_chacha20poly1305_decrypt(const uint8_t key[32], const uint8_t nonce[12], const uint8_t* ciphertext, size_t n, const uint8_t tag[16],
+                                       uint8_t* plaintext);
+/* epk = [esk] g_d, enc_ciphertext under kdf([8 esk] pk_d, epk).  esk is an argument (the reference draws or derives it): deterministic */
+int masp_host_sapling_note_encrypt(const uint8_t esk[32], const uint8_t diversifier[11], const uint8_t pk_d[32], const uint8_t plaintext[596],
+                                   uint8_t epk_out[32], uint8_t enc_out[612]);
+/* try_sapling_note_decryption for one ivk and one output (epk, cmu, enc_ciphertext).  lead_byte: the one the consensus rules expect at the
+ * output's height (1 or 2).  MASP_HOST_OK: plaintext_out and pk_d_out = [ivk] g_d are written; MASP_HOST_E_NO_NOTE: every refusal of the
+ * reference (epk does not decode, tag, lead byte, asset identifier, rcm, diversifier, pk_d, commitment, the esk check of lead byte 2) */
+int masp_host_sapling_try_note_decryption(const uint8_t ivk[32], const uint8_t epk[32], const uint8_t cmu[32], const uint8_t enc[612], int lead_byte,
+                                          uint8_t plaintext_out[596], uint8_t pk_d_out[32]);
+/* the same from the symmetric key on (try_note_decryption_inner): the second half of masp_hip_sapling_trial_decrypt's hits */
+int masp_host_sapling_finish_note_decryption(const uint8_t key[32], const uint8_t ivk[32], const uint8_t epk[32], const uint8_t cmu[32],
+                                             const uint8_t enc[612], int lead_byte, uint8_t plaintext_out[596], uint8_t pk_d_out[32]);
+/* batch::try_note_decryption on `threads` host threads: hit_ivk[o] = the first ivk index that decrypts output o, or -1; plaintexts
+ * (n_out x 596) and pk_ds (n_out x 32) are written for the hits */
+int masp_host_sapling_try_note_decryption_batch(size_t n_ivk, const uint8_t* ivks, size_t n_out, const uint8_t* epks, const uint8_t* cmus,
+                                                const uint8_t* encs, int lead_byte, int threads, int32_t* hit_ivk, uint8_t* plaintexts,
+                                                uint8_t* pk_ds);
 
 #ifdef __cplusplus
 }

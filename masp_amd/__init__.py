@@ -8,3 +8,6 @@ from .hip import Context, MaspHipError, library_path, load_library  # noqa: F401
 from .r1cs import R1cs  # noqa: F401
 from .verifier import (BatchValidator, Bundle, ConvertDescription, OutputDescription, SaplingVerificationContext,  # noqa: F401
                        SpendDescription)
+from . import note_encryption  # noqa: F401
+from .note_encryption import (Note, PaymentAddress, Rseed, ShieldedOutput, sapling_note_encrypt,  # noqa: F401
+                              try_sapling_note_decryption)

@@ -4,11 +4,14 @@
 // nullifier derivation, then synthesis of the circuit into (input_assignment, aux_assignment).
 // It also exports the static R1CS of each circuit (what bellperson's KeypairAssembly collects) and the
 // native primitives, so that tests can pin them against the reference's vectors.
+#include <atomic>
 #include <memory>
+#include <thread>
 
 #include "../../../include/masp_host.h"   // the declarations of everything defined here: a mismatch does not compile
 #include "circuits.h"
 #include "groth16_vk.h"
+#include "note_encryption.h"
 #include "pairing_prog.h"
 #include "pairing.h"
 
@@ -734,5 +737,82 @@ int masp_host_convert_cmu(const uint8_t generator[32], uint8_t out32[32]) {
     g.to_bytes(b);
     pedersen_hash({true, 0}, bytes_to_bits_le(b, 32)).to_affine().u.to_bytes(out32);
     return 0;
+}
+// ---- Sapling note encryption and trial decryption (note_encryption.h) --------------------------------
+int masp_host_sapling_ka_agree(const uint8_t sk[32], const uint8_t p32[32], uint8_t out32[32]) {
+    JPoint p;
+    if (!JPoint::from_bytes(p, p32)) return MASP_HOST_E_INVALID;
+    ka_agree(sk, p).to_bytes(out32);
+    return MASP_HOST_OK;
+}
+// Diversifier::g_d: the group hash of a diversifier (personal "MASP__gd"), the base of its payment addresses
+int masp_host_diversifier_base(const uint8_t diversifier[11], uint8_t out32[32]) {
+    JPoint gd;
+    if (!group_hash(gd, diversifier, 11, "MASP__gd")) return MASP_HOST_E_DIVERSIFIER;
+    gd.to_bytes(out32);
+    return MASP_HOST_OK;
+}
+void masp_host_kdf_sapling(const uint8_t secret[32], const uint8_t epk[32], uint8_t key32[32]) { kdf_sapling(key32, secret, epk); }
+void masp_host_prf_expand(const uint8_t* sk, size_t sklen, const uint8_t* t, size_t tlen, uint8_t out64[64]) { prf_expand(out64, sk, sklen, t, tlen); }
+void masp_host_sapling_rseed_scalar(const uint8_t rseed[32], int domain, uint8_t out32[32]) { rseed_scalar(out32, rseed, (uint8_t)domain); }
+void masp_host_chacha20poly1305_encrypt(const uint8_t key[32], const uint8_t nonce[12], const uint8_t* plaintext, size_t n, uint8_t* ciphertext,
+                                        uint8_t tag[16]) {
+    aead_encrypt(ciphertext, tag, key, nonce, plaintext, n);
+}
+int masp_host_chacha20poly1305_decrypt(const uint8_t key[32], const uint8_t nonce[12], const uint8_t* ciphertext, size_t n, const uint8_t tag[16],
+                                       uint8_t* plaintext) {
+    return aead_decrypt(plaintext, key, nonce, ciphertext, n, tag) ? MASP_HOST_OK : MASP_HOST_E_NO_NOTE;
+}
+int masp_host_sapling_note_encrypt(const uint8_t esk[32], const uint8_t diversifier[11], const uint8_t pk_d[32], const uint8_t plaintext[596],
+                                   uint8_t epk_out[32], uint8_t enc_out[612]) {
+    if (!rj_is_canonical(esk)) return MASP_HOST_E_INVALID;
+    JPoint gd;
+    if (!group_hash(gd, diversifier, 11, "MASP__gd")) return MASP_HOST_E_DIVERSIFIER;
+    return note_encrypt(esk, diversifier, pk_d, plaintext, epk_out, enc_out) ? MASP_HOST_OK : MASP_HOST_E_INVALID;
+}
+int masp_host_sapling_try_note_decryption(const uint8_t ivk[32], const uint8_t epk[32], const uint8_t cmu[32], const uint8_t enc[612], int lead_byte,
+                                          uint8_t plaintext_out[596], uint8_t pk_d_out[32]) {
+    if (!rj_is_canonical(ivk)) return MASP_HOST_E_INVALID;
+    return try_note_decryption(ivk, epk, cmu, enc, lead_byte, plaintext_out, pk_d_out) ? MASP_HOST_OK : MASP_HOST_E_NO_NOTE;
+}
+int masp_host_sapling_finish_note_decryption(const uint8_t key[32], const uint8_t ivk[32], const uint8_t epk[32], const uint8_t cmu[32],
+                                             const uint8_t enc[612], int lead_byte, uint8_t plaintext_out[596], uint8_t pk_d_out[32]) {
+    if (!rj_is_canonical(ivk)) return MASP_HOST_E_INVALID;
+    return finish_note_decryption(key, ivk, epk, cmu, enc, lead_byte, plaintext_out, pk_d_out) ? MASP_HOST_OK : MASP_HOST_E_NO_NOTE;
+}
+// batch::try_note_decryption on `threads` host threads: per output the first ivk of the list that decrypts it
+int masp_host_sapling_try_note_decryption_batch(size_t n_ivk, const uint8_t* ivks, size_t n_out, const uint8_t* epks, const uint8_t* cmus,
+                                                const uint8_t* encs, int lead_byte, int threads, int32_t* hit_ivk, uint8_t* plaintexts,
+                                                uint8_t* pk_ds) {
+    for (size_t k = 0; k < n_ivk; ++k)
+        if (!rj_is_canonical(ivks + 32 * k)) return MASP_HOST_E_INVALID;
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (;;) {
+            const size_t o = next.fetch_add(1);
+            if (o >= n_out) return;
+            hit_ivk[o] = -1;
+            JPoint e;
+            if (!JPoint::from_bytes(e, epks + 32 * o)) continue;
+            for (size_t k = 0; k < n_ivk; ++k) {
+                uint8_t secret[32], key[32];
+                ka_agree(ivks + 32 * k, e).to_bytes(secret);
+                kdf_sapling(key, secret, epks + 32 * o);
+                if (finish_note_decryption(key, ivks + 32 * k, epks + 32 * o, cmus + 32 * o, encs + ENC_CIPHERTEXT_SIZE * o, lead_byte,
+                                           plaintexts + NOTE_PLAINTEXT_SIZE * o, pk_ds + 32 * o)) {
+                    hit_ivk[o] = (int32_t)k;
+                    break;
+                }
+            }
+        }
+    };
+    (void)generators();          // the lazily built tables, before the threads race for them
+    (void)pedersen_windows();
+    const int nt = std::max(1, std::min<int>(threads, 256));
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nt; ++t) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+    return MASP_HOST_OK;
 }
 }  // extern "C"

@@ -365,6 +365,17 @@ struct masp_hip_ctx {
     DevBuf<uint8_t> jj_points, jj_scalars, jj_partial;
     DevBuf<int> jj_status;
     DevBuf<uint32_t> jj_out;
+    // the note scan (k_note_scan.hip: masp_hip_sapling_trial_decrypt), one at a time per context (ns_mu): chunks of outputs alternate between
+    // the two verifier streams, each with a buffer set of its own; the buffers grow on demand and are kept
+    struct NoteScanSet {
+        DevBuf<uint8_t> epk, raw, ct, pts, status, hit_keys;
+        DevBuf<uint32_t> count, hit_idx;
+    };
+    std::mutex ns_mu;
+    NoteScanSet ns[2];
+    DevBuf<uint32_t> ns_digits;
+    std::atomic<int> ns_signed_digits{1}, ns_inversion{0};   // masp_hip_note_scan_configure; the defaults are the measured winners (KERNELS.md)
+    double ns_last_ms[2] = {0, 0};                           // masp_hip_note_scan_last_timing (under slot_mu)
 };
 
 namespace masp {

@@ -1,0 +1,376 @@
+// Batch trial decryption of Sapling notes on the GPU: the C ABI entry point masp_hip_sapling_trial_decrypt (include/masp_hip.h), the
+// device half of masp_note_encryption::batch::try_note_decryption over SaplingDomain (masp_note_encryption/src/batch.rs:43-86).
+//
+// For every (output, ivk) pair the device does what is done for EVERY pair: the key agreement [8 ivk] epk, the KDF (one BLAKE2b
+// compression), ChaCha20 block 0 for the Poly1305 key and Poly1305 over the ciphertext, compared with the tag.  It does not decrypt:
+// the tag is over the ciphertext, so the pairs that fail it (all but the caller's own notes) are finished, and the rare pair that
+// passes goes back to the host with its symmetric key, where masp_host_sapling_finish_note_decryption decrypts, parses and checks the
+// commitment.
+//
+// Kernels:  k_ns_decode   one lane per output: jj_decode of epk once, not once per ivk, stored in the affine form (v - u, v + u, 2d u v)
+//                         that makes the ladder's additions mixed ones of 7 products, and a status byte;
+//           k_ns_repitch  the 612-byte ciphertext rows into 16-byte columns (KERNELS.md: why);
+//           k_ns_trial    one lane per pair, the ivk constant across the workgroup (blockIdx.y): the scalar's digits are wave-uniform, so the
+//                         `if (digit)` of the double-and-add is a uniform branch, the scalar lives in SGPRs and no lane needs a table.
+#include <mutex>
+
+#include "device/blake2b.hpp"
+#include "device/chacha20.hpp"
+#include "device/jubjub.hpp"
+#include "device/poly1305.hpp"
+#include "internal.h"
+
+using namespace masp;
+
+namespace {
+
+constexpr uint32_t NS_BLOCK = 256;
+constexpr size_t NS_ENC = 612;            // enc_ciphertext: 596 bytes of note plaintext under ChaCha20, the 16-byte tag
+constexpr uint32_t NS_ENC_WORDS = 153;
+constexpr uint32_t NS_COLS = 39;          // 16-byte columns of a repitched row (156 words: three of padding)
+constexpr size_t NS_MAX_IVKS = 4096;
+constexpr size_t NS_MAX_OUTPUTS = (size_t)1 << 26;
+constexpr size_t NS_CHUNK_PAIRS = (size_t)1 << 18;   // pairs per launch: one lane each, four waves on every SIMD of the chip
+
+struct JNiels {
+    Fr vmu, vpu, t2d;   // v - u, v + u, 2 d u v of an affine point
+};
+
+// p + q (negated if `negate`), q affine in Niels form: 7 products.  `negate` is wave-uniform in k_ns_trial.
+__device__ __forceinline__ JExt jj_add_niels(const JExt& p, const JNiels& q, bool negate) {
+    const Fr A = fe_mul(fe_sub(p.V, p.U), negate ? q.vpu : q.vmu);
+    const Fr B = fe_mul(fe_add(p.V, p.U), negate ? q.vmu : q.vpu);
+    Fr C = fe_mul(p.T, q.t2d);
+    if (negate) C = fe_neg(C);
+    const Fr D = fe_dbl(p.Z);
+    const Fr E = fe_sub(B, A), F = fe_sub(D, C), G = fe_add(D, C), H = fe_add(B, A);
+    return {fe_mul(E, F), fe_mul(G, H), fe_mul(F, G), fe_mul(E, H)};
+}
+
+// fe_inv (field.hpp) inlined: the out-of-line form takes its operand through scratch and, at 161 VGPRs, would set the kernel's register
+// count (a kernel is given the registers of its largest callee)
+__device__ __forceinline__ Fr fe_inv_divsteps_inline(const Fr& a) {
+    Fr r, r2;
+    FeDivsteps<FrCfg>::invert(r.v, a.v);   // (a R)^-1
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r2.v[i] = FrCfg::R2[i];
+    return fe_mul_nc(fe_mul_nc(r, r2), r2);
+}
+
+__global__ __launch_bounds__(NS_BLOCK) void k_ns_decode(const uint4* __restrict__ epks, uint32_t n, uint8_t* __restrict__ status,
+                                                        JNiels* __restrict__ pts) {
+    const uint32_t o = blockIdx.x * NS_BLOCK + threadIdx.x;
+    if (o >= n) return;
+    const uint4 p0 = epks[2 * o], p1 = epks[2 * o + 1];
+    const uint32_t w[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+    JExt p;
+    const int rc = jj_decode(p, w);
+    status[o] = (uint8_t)rc;
+    if (rc != JJ_OK) return;
+    pts[o] = {fe_sub(p.V, p.U), fe_add(p.V, p.U), fe_mul(p.T, fr_lit(JubjubCfg::D2))};   // (Z = 1: T = u v)
+}
+
+// raw: n rows of 153 words; ct4[c * n_pad + o] = words 4c .. 4c + 3 of row o (zero beyond the row).  Lanes run along o: the writes and
+// k_ns_trial's reads are whole 1 KiB lines per wave, the strided reads happen here, once per output instead of once per pair.
+__global__ __launch_bounds__(NS_BLOCK) void k_ns_repitch(const uint32_t* __restrict__ raw, uint32_t n, uint32_t n_pad, uint4* __restrict__ ct4) {
+    const uint32_t o = blockIdx.x * NS_BLOCK + threadIdx.x, c = blockIdx.y;
+    if (o >= n) return;
+    const uint32_t* row = raw + (size_t)o * NS_ENC_WORDS;
+    uint4 v;
+    v.x = row[4 * c];   // (4 * 38 = 152: the last column holds one word)
+    v.y = 4 * c + 1 < NS_ENC_WORDS ? row[4 * c + 1] : 0u;
+    v.z = 4 * c + 2 < NS_ENC_WORDS ? row[4 * c + 2] : 0u;
+    v.w = 4 * c + 3 < NS_ENC_WORDS ? row[4 * c + 3] : 0u;
+    ct4[(size_t)c * n_pad + o] = v;
+}
+
+constexpr uint64_t le64_of(const char* s) {
+    uint64_t x = 0;
+    for (int i = 7; i >= 0; --i) x = (x << 8) | (uint8_t)s[i];
+    return x;
+}
+
+// digits: per ivk 16 words, [0..7] the mask of non-zero digits of its (plain or signed) binary recoding, [8..15] the mask of negative ones.
+// hits: count[0] pairs verified their tag; pair i < cap is (hit_idx[i] = output, ivk) with its key in hit_keys[2 i], [2 i + 1].
+// inversion: 0 the divstep inverse, 1 the binary-gcd one (field.hpp), for the one inversion of the encoding.
+__global__ __launch_bounds__(NS_BLOCK) void k_ns_trial(const uint32_t* __restrict__ digits, const JNiels* __restrict__ pts,
+                                                       const uint8_t* __restrict__ status, const uint4* __restrict__ epks,
+                                                       const uint4* __restrict__ ct4, uint32_t n, uint32_t n_pad, uint32_t out_base, int inversion,
+                                                       uint32_t* __restrict__ count, uint32_t cap, uint2* __restrict__ hit_idx,
+                                                       uint4* __restrict__ hit_keys) {
+    const uint32_t o = blockIdx.x * NS_BLOCK + threadIdx.x, k = blockIdx.y;
+    if (o >= n || status[o] != JJ_OK) return;
+    const JNiels q = pts[o];
+    const uint32_t* dg = digits + 16 * k;   // wave-uniform: scalar loads
+    JExt r = jj_identity();
+    bool started = false;
+#pragma unroll 1
+    for (int w = 7; w >= 0; --w) {
+        const uint32_t nz = dg[w], ng = dg[8 + w];
+#pragma unroll 1
+        for (int b = 31; b >= 0; --b) {
+            if (started) r = jj_dbl(r);
+            if ((nz >> b) & 1u) {
+                r = jj_add_niels(r, q, (ng >> b) & 1u);   // (the first one adds to the identity: the law is complete)
+                started = true;
+            }
+        }
+    }
+    r = jj_mul_by_cofactor(r);
+    // encode(secret) || epk -> the key
+    uint64_t m[16], h[8];
+    {
+        const Fr zi = inversion == 1 ? fe_inv_bingcd(r.Z) : fe_inv_divsteps_inline(r.Z);
+        const Fr u = fe_from_mont(fe_mul(r.U, zi)), v = fe_from_mont(fe_mul(r.V, zi));
+        const uint32_t top = v.v[7] | ((u.v[0] & 1u) << 31);
+        m[0] = v.v[0] | ((uint64_t)v.v[1] << 32);
+        m[1] = v.v[2] | ((uint64_t)v.v[3] << 32);
+        m[2] = v.v[4] | ((uint64_t)v.v[5] << 32);
+        m[3] = v.v[6] | ((uint64_t)top << 32);
+    }
+    {
+        const uint4 e0 = epks[2 * o], e1 = epks[2 * o + 1];
+        m[4] = e0.x | ((uint64_t)e0.y << 32);
+        m[5] = e0.z | ((uint64_t)e0.w << 32);
+        m[6] = e1.x | ((uint64_t)e1.y << 32);
+        m[7] = e1.z | ((uint64_t)e1.w << 32);
+    }
+#pragma unroll
+    for (int i = 8; i < 16; ++i) m[i] = 0;
+    blake2b_one_block(h, m, 64, 32, le64_of("MASP__Sa"), le64_of("plingKDF"));
+    const uint32_t key[8] = {(uint32_t)h[0], (uint32_t)(h[0] >> 32), (uint32_t)h[1], (uint32_t)(h[1] >> 32),
+                             (uint32_t)h[2], (uint32_t)(h[2] >> 32), (uint32_t)h[3], (uint32_t)(h[3] >> 32)};
+    const uint32_t nonce[3] = {0, 0, 0};
+    uint32_t b0[16];
+    chacha20_block(b0, key, 0, nonce);
+    Poly1305State st;
+    poly1305_init(st, b0);
+    const uint4* col = ct4 + o;
+#pragma unroll 4
+    for (uint32_t c = 0; c < 37; ++c) {
+        const uint4 x = col[(size_t)c * n_pad];
+        poly1305_block(st, x.x, x.y, x.z, x.w);
+    }
+    const uint4 x37 = col[(size_t)37 * n_pad], x38 = col[(size_t)38 * n_pad];
+    poly1305_block(st, x37.x, 0, 0, 0);     // bytes 592 .. 595, zero-padded to the block (the AEAD's pad16: a whole block)
+    poly1305_block(st, 0, 0, 596, 0);       // the lengths: no associated data, 596 bytes of ciphertext
+    uint32_t tag[4];
+    poly1305_finish(st, b0 + 4, tag);
+    if (tag[0] != x37.y || tag[1] != x37.z || tag[2] != x37.w || tag[3] != x38.x) return;
+    const uint32_t slot = atomicAdd(count, 1u);
+    if (slot >= cap) return;   // (cap is the launch's pair count: cannot happen; the count still tells)
+    hit_idx[slot] = make_uint2(out_base + o, k);
+    hit_keys[2 * slot] = make_uint4(key[0], key[1], key[2], key[3]);
+    hit_keys[2 * slot + 1] = make_uint4(key[4], key[5], key[6], key[7]);
+}
+
+// r_J, the order of the prime-order subgroup (a SaplingIvk is a canonical scalar below it)
+constexpr uint32_t RJ[8] = {0xd6f72cb7u, 0xd0970e5eu, 0xccc81082u, 0xa6682093u, 0x01343b00u, 0x06673b01u, 0x6533afa9u, 0x0e7db4eau};
+
+bool below_rj(const uint32_t* k) {
+    for (int i = 7; i >= 0; --i)
+        if (k[i] != RJ[i]) return k[i] < RJ[i];
+    return false;
+}
+
+// the digit masks of k_ns_trial for one ivk.  signed_digits: the non-adjacent form (digits -1, 0, 1, no two neighbours non-zero: a third
+// of the positions instead of half, at most 253 of them for k < 2^252); otherwise the plain binary digits.
+void recode(uint32_t out[16], const uint32_t k_in[8], bool signed_digits) {
+    memset(out, 0, 64);
+    if (!signed_digits) {
+        memcpy(out, k_in, 32);
+        return;
+    }
+    uint32_t k[8];
+    memcpy(k, k_in, 32);
+    for (int pos = 0; pos < 256; ++pos) {
+        if (k[0] & 1u) {
+            out[pos >> 5] |= 1u << (pos & 31);
+            if ((k[0] & 3u) == 3u) {   // digit -1: k += 1 (k < 2^253: no overflow)
+                out[8 + (pos >> 5)] |= 1u << (pos & 31);
+                for (int i = 0; i < 8 && ++k[i] == 0; ++i) {
+                }
+            } else {
+                k[0] &= ~1u;
+            }
+        }
+        for (int i = 0; i < 7; ++i) k[i] = (k[i] >> 1) | (k[i + 1] << 31);
+        k[7] >>= 1;
+    }
+}
+
+struct Hit {
+    uint32_t output, ivk;
+    uint8_t key[32];
+};
+
+struct ChunkInFlight {
+    size_t o0 = 0, n = 0;
+    int set = 0;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // before the upload, behind it, behind the kernels
+};
+
+// enqueues one chunk of outputs on its stream: upload, decode, repitch, trials, and the count's way back
+int enqueue_chunk(masp_hip_ctx* ctx, ChunkInFlight& c, size_t n_ivk, const uint8_t* epks, const uint8_t* encs, uint32_t* h_count) {
+    masp_hip_ctx::NoteScanSet& b = ctx->ns[c.set];
+    hipStream_t s = ctx->streams.vk[c.set];
+    const uint32_t n = (uint32_t)c.n, nb = (n + NS_BLOCK - 1) / NS_BLOCK, n_pad = nb * NS_BLOCK;
+    const size_t cap = c.n * n_ivk;
+    int rc;
+    if ((rc = b.epk.reserve(32 * (size_t)n_pad)) || (rc = b.raw.reserve(NS_ENC * (size_t)n_pad)) || (rc = b.ct.reserve(16 * (size_t)NS_COLS * n_pad)) ||
+        (rc = b.pts.reserve(sizeof(JNiels) * (size_t)n_pad)) || (rc = b.status.reserve(n_pad)) || (rc = b.count.reserve(1)) ||
+        (rc = b.hit_idx.reserve(2 * cap)) || (rc = b.hit_keys.reserve(32 * cap)))
+        return rc;
+    for (hipEvent_t& e : c.ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(c.ev[0], s));
+    HIP_TRY(hipMemcpyAsync(b.epk.p, epks + 32 * c.o0, 32 * c.n, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(b.raw.p, encs + NS_ENC * c.o0, NS_ENC * c.n, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(b.count.p, 0, sizeof(uint32_t), s));
+    HIP_TRY(hipEventRecord(c.ev[1], s));
+    MASP_LAUNCH(k_ns_decode, dim3(nb), dim3(NS_BLOCK), 0, s, (const uint4*)b.epk.p, n, b.status.p, (JNiels*)b.pts.p);
+    MASP_LAUNCH(k_ns_repitch, dim3(nb, NS_COLS), dim3(NS_BLOCK), 0, s, (const uint32_t*)b.raw.p, n, n_pad, (uint4*)b.ct.p);
+    MASP_LAUNCH(k_ns_trial, dim3(nb, (uint32_t)n_ivk), dim3(NS_BLOCK), 0, s, (const uint32_t*)ctx->ns_digits.p, (const JNiels*)b.pts.p,
+                (const uint8_t*)b.status.p, (const uint4*)b.epk.p, (const uint4*)b.ct.p, n, n_pad, (uint32_t)c.o0, ctx->ns_inversion.load(),
+                b.count.p, (uint32_t)cap, (uint2*)b.hit_idx.p, (uint4*)b.hit_keys.p);
+    HIP_TRY(hipEventRecord(c.ev[2], s));
+    HIP_TRY(hipMemcpyAsync(h_count, b.count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    return MASP_HIP_OK;
+}
+
+// waits for a chunk and takes its statuses and hits
+int collect_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, size_t n_ivk, const uint32_t* h_count, uint8_t* epk_status, std::vector<Hit>& hits,
+                  double ms[3]) {
+    masp_hip_ctx::NoteScanSet& b = ctx->ns[c.set];
+    hipStream_t s = ctx->streams.vk[c.set];
+    HIP_TRY(hipStreamSynchronize(s));
+    if (launch_status() != MASP_HIP_OK) return MASP_HIP_E_HIP;   // a refused launch: the buffers mean nothing
+    const size_t nh = *h_count;
+    if (nh > c.n * n_ivk) {
+        last_hip_error() = "note scan: hit count beyond the chunk's pairs";
+        return MASP_HIP_E_HIP;
+    }
+    if (epk_status) HIP_TRY(hipMemcpyAsync(epk_status + c.o0, b.status.p, c.n, hipMemcpyDeviceToHost, s));
+    std::vector<uint32_t> idx(2 * nh);
+    std::vector<uint8_t> keys(32 * nh);
+    if (nh) {
+        HIP_TRY(hipMemcpyAsync(idx.data(), b.hit_idx.p, 8 * nh, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(keys.data(), b.hit_keys.p, 32 * nh, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t i = 0; i < nh; ++i) {
+        Hit h;
+        h.output = idx[2 * i];
+        h.ivk = idx[2 * i + 1];
+        memcpy(h.key, &keys[32 * i], 32);
+        hits.push_back(h);
+    }
+    float up = 0, kern = 0;
+    HIP_TRY(hipEventElapsedTime(&up, c.ev[0], c.ev[1]));
+    HIP_TRY(hipEventElapsedTime(&kern, c.ev[1], c.ev[2]));
+    ms[0] += up;
+    ms[1] += kern;
+    return MASP_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int masp_hip_sapling_trial_decrypt(masp_hip_ctx* ctx, size_t n_ivk, const uint8_t* ivks, size_t n_out, const uint8_t* epks,
+                                   const uint8_t* enc_ciphertexts, uint8_t* epk_status, size_t hit_capacity, uint32_t* hit_output, uint32_t* hit_ivk,
+                                   uint8_t* hit_keys, size_t* n_hits) {
+    if (!ctx || !n_hits || (n_ivk && !ivks) || (n_out && (!epks || !enc_ciphertexts)) || n_ivk > NS_MAX_IVKS || n_out > NS_MAX_OUTPUTS ||
+        (hit_capacity && (!hit_output || !hit_ivk || !hit_keys)))
+        return MASP_HIP_E_INVALID_ARG;
+    *n_hits = 0;
+    std::vector<uint32_t> digits(16 * n_ivk);
+    for (size_t k = 0; k < n_ivk; ++k) {
+        uint32_t w[8];
+        memcpy(w, ivks + 32 * k, 32);   // (little-endian host)
+        if (!below_rj(w)) return MASP_HIP_E_INVALID_ARG;
+        recode(&digits[16 * k], w, FIRST_DEVICE(ctx)->ns_signed_digits.load() != 0);
+    }
+    if (n_ivk == 0 || n_out == 0) {
+        if (epk_status && n_out) memset(epk_status, 0, n_out);   // (not looked at: no key asked for them)
+        return MASP_HIP_OK;
+    }
+    const ApiLaunchScope api_scope;
+    ctx = FIRST_DEVICE(ctx);
+    std::shared_lock<std::shared_mutex> lock(ctx->mu);   // concurrent with provers and verifiers
+    std::lock_guard<std::mutex> nlock(ctx->ns_mu);
+    hipSetDevice(ctx->device);
+    int rc;
+    if ((rc = ctx->ns_digits.upload(digits.data(), digits.size(), ctx->streams.vk[0]))) return fail(ctx, rc);
+    if (hipStreamSynchronize(ctx->streams.vk[0]) != hipSuccess) {   // both streams read the digits
+        last_hip_error() = std::string("note scan: upload failed: ") + hipGetErrorString(hipGetLastError());
+        return fail(ctx, MASP_HIP_E_HIP);
+    }
+    // Chunks of outputs, alternately on the two verifier streams with a buffer set each: a chunk's upload runs beside the chunk before's kernels.
+    size_t per = std::max<size_t>(NS_BLOCK, NS_CHUNK_PAIRS / n_ivk / NS_BLOCK * NS_BLOCK);
+    std::vector<Hit> hits;
+    double ms[3] = {0, 0, 0};
+    ChunkInFlight fly[2];
+    uint32_t h_count[2] = {0, 0};
+    bool pending[2] = {false, false};
+    rc = MASP_HIP_OK;
+    int set = 0;
+    for (size_t o0 = 0; o0 < n_out && !rc; o0 += per, set ^= 1) {
+        if (pending[set]) {   // the set's previous chunk, two chunks back
+            rc = collect_chunk(ctx, fly[set], n_ivk, &h_count[set], epk_status, hits, ms);
+            pending[set] = false;
+            if (rc) break;
+        }
+        fly[set].o0 = o0;
+        fly[set].n = std::min(per, n_out - o0);
+        fly[set].set = set;
+        rc = enqueue_chunk(ctx, fly[set], n_ivk, epks, enc_ciphertexts, &h_count[set]);
+        pending[set] = rc == MASP_HIP_OK;
+    }
+    for (int i = 0; i < 2; ++i) {   // (set: the older of the two first)
+        const int s2 = set ^ i;
+        if (!pending[s2]) continue;
+        if (!rc)
+            rc = collect_chunk(ctx, fly[s2], n_ivk, &h_count[s2], epk_status, hits, ms);
+        else
+            (void)hipStreamSynchronize(ctx->streams.vk[s2]);   // nothing of this call stays in flight
+    }
+    for (ChunkInFlight& c : fly)
+        for (hipEvent_t e : c.ev)
+            if (e) (void)hipEventDestroy(e);
+    if (rc) return fail(ctx, rc);
+    // the order lanes reached the counter in is not an order: by (output, ivk)
+    std::sort(hits.begin(), hits.end(), [](const Hit& a, const Hit& b) { return a.output != b.output ? a.output < b.output : a.ivk < b.ivk; });
+    {
+        std::lock_guard<std::mutex> g(ctx->slot_mu);
+        ctx->ns_last_ms[0] = ms[0];
+        ctx->ns_last_ms[1] = ms[1];
+    }
+    *n_hits = hits.size();
+    if (hits.size() > hit_capacity) return MASP_HIP_E_CAPACITY;   // nothing written: the caller comes back with room for *n_hits
+    for (size_t i = 0; i < hits.size(); ++i) {
+        hit_output[i] = hits[i].output;
+        hit_ivk[i] = hits[i].ivk;
+        memcpy(hit_keys + 32 * i, hits[i].key, 32);
+    }
+    return MASP_HIP_OK;
+}
+
+int masp_hip_note_scan_configure(masp_hip_ctx* ctx, int signed_digits, int inversion) {
+    if (!ctx || signed_digits < 0 || signed_digits > 1 || inversion < 0 || inversion > 1) return MASP_HIP_E_INVALID_ARG;
+    ctx = FIRST_DEVICE(ctx);
+    ctx->ns_signed_digits.store(signed_digits);
+    ctx->ns_inversion.store(inversion);
+    return MASP_HIP_OK;
+}
+
+int masp_hip_note_scan_last_timing(masp_hip_ctx* ctx, double ms[2]) {
+    if (!ctx || !ms) return MASP_HIP_E_INVALID_ARG;
+    ctx = FIRST_DEVICE(ctx);
+    std::lock_guard<std::mutex> g(ctx->slot_mu);
+    ms[0] = ctx->ns_last_ms[0];
+    ms[1] = ctx->ns_last_ms[1];
+    return MASP_HIP_OK;
+}
+
+}  // extern "C"

@@ -465,6 +465,8 @@ const char* masp_hip_strerror(int code) {
         case MASP_HIP_E_UNEXPECTED_IDENTITY: return "delta is the identity (UnexpectedIdentity)";
         case MASP_HIP_E_NOT_LOADED: return "circuit slot is empty";
         case MASP_HIP_E_SCALAR_RANGE: return "scalar is not a canonical field element";
+        case MASP_HIP_E_POINT_ENCODING: return "a Jubjub point encoding does not decode";
+        case MASP_HIP_E_CAPACITY: return "an output buffer is too small";
         default: return "unknown error";
     }
 }

@@ -9,8 +9,10 @@ _lib = None
 
 ERRORS = {1: "invalid argument", 2: "Parameters bytes are malformed", 3: "Parameters do not match the circuit shape",
           4: "no usable HIP device (there is no CPU fallback)", 5: "HIP runtime error", 6: "UnexpectedIdentity",
-          7: "circuit slot is empty", 8: "scalar is not a canonical field element", 9: "a Jubjub point encoding does not decode"}
+          7: "circuit slot is empty", 8: "scalar is not a canonical field element", 9: "a Jubjub point encoding does not decode",
+          10: "an output buffer is too small"}
 E_POINT_ENCODING = 9
+E_CAPACITY = 10
 SPEND_AUTH, BINDING = 0, 1      # masp_hip_redjubjub_verify_batch kinds
 
 SPEND, OUTPUT, CONVERT = 0, 1, 2
@@ -124,6 +126,10 @@ def load_library():
     if hasattr(L, "masp_hip_redjubjub_verify_batch"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
         L.masp_hip_jubjub_msm.argtypes = [vp, sz, vp, vp, vp, C.POINTER(C.c_int64)]
         L.masp_hip_redjubjub_verify_batch.argtypes = [vp, sz, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int)]
+    if hasattr(L, "masp_hip_sapling_trial_decrypt"):
+        L.masp_hip_sapling_trial_decrypt.argtypes = [vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, C.POINTER(sz)]
+        L.masp_hip_note_scan_configure.argtypes = [vp, C.c_int, C.c_int]
+        L.masp_hip_note_scan_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
     L.masp_hip_batch_upload.argtypes = [vp, sz, vp]
     L.masp_hip_batch_prove_resident.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.masp_hip_batch_prove_resident_steps.argtypes = [vp, C.c_int, sz, vp, vp, C.POINTER(C.c_float)]
@@ -364,6 +370,42 @@ class Context:
             raise e
         self._check(rc)
         return out.tobytes()
+
+    # ---- batch trial decryption of Sapling notes on the GPU ----
+    def sapling_trial_decrypt(self, ivks, epks, enc_ciphertexts, hit_capacity=None):
+        """The device half of batch::try_note_decryption (masp_hip_sapling_trial_decrypt): ivks n_ivk x 32, epks n_out x 32, enc_ciphertexts
+        n_out x 612 (bytes or uint8 arrays) -> (epk_status uint8[n_out], hit_output uint32[h], hit_ivk uint32[h], hit_keys uint8[h, 32]): the
+        pairs whose tag verifies, sorted by (output, ivk), each with its symmetric key.  hit_capacity: room for that many hits (default: grown
+        to what the call asks for)."""
+        ivks, epks, encs = _u8(ivks, 32), _u8(epks, 32), _u8(enc_ciphertexts, 612)
+        n_ivk, n_out = ivks.shape[0], epks.shape[0]
+        assert encs.shape[0] == n_out
+        status = np.zeros(n_out, dtype=np.uint8)
+        cap = max(16, n_out // 64) if hit_capacity is None else int(hit_capacity)
+        while True:
+            ho, hi, hk = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros((cap, 32), np.uint8)
+            nh = C.c_size_t(0)
+            rc = self._L.masp_hip_sapling_trial_decrypt(self._h, n_ivk, _p(ivks), n_out, _p(epks), _p(encs), _p(status), cap, _p(ho), _p(hi),
+                                                        _p(hk), C.byref(nh))
+            if rc == E_CAPACITY and hit_capacity is None:
+                cap = nh.value
+                continue
+            if rc == E_CAPACITY:
+                e = MaspHipError(rc, "%d hits" % nh.value)
+                e.needed = nh.value
+                raise e
+            self._check(rc)
+            return status, ho[:nh.value], hi[:nh.value], hk[:nh.value]
+
+    def note_scan_configure(self, signed_digits=1, inversion=0):
+        """measurement knobs of the note scan (masp_hip_note_scan_configure); results do not depend on them"""
+        self._check(self._L.masp_hip_note_scan_configure(self._h, int(signed_digits), int(inversion)))
+
+    def note_scan_last_timing(self):
+        """(upload ms, kernel ms) of the last scan, HIP events summed over its chunks"""
+        ms = (C.c_double * 2)()
+        self._check(self._L.masp_hip_note_scan_last_timing(self._h, ms))
+        return ms[0], ms[1]
 
     # ---- building blocks ----
     def msm_g1(self, bases, scalars):

@@ -15,7 +15,10 @@ KINDS = {"spend": SPEND, "output": OUTPUT, "convert": CONVERT}
 JUBJUB_ORDER = 6554484396890773809930967563523245729705921265872317281365359162392183254199
 FR_MODULUS = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
 TREE_DEPTH = 32
-ERRORS = {1: "invalid encoding", 2: "invalid diversifier", 3: "synthesis error", 4: "assignment does not satisfy the circuit"}
+ERRORS = {1: "invalid encoding", 2: "invalid diversifier", 3: "synthesis error", 4: "assignment does not satisfy the circuit",
+          5: "not a note of this key"}
+E_NO_NOTE = 5
+NOTE_PLAINTEXT_SIZE, ENC_CIPHERTEXT_SIZE = 596, 612
 
 
 class HostError(RuntimeError):
@@ -66,6 +69,21 @@ def load_library():
         L.masp_host_jubjub_sum.argtypes = [cp, cp, C.c_size_t, cp, cp]
         L.masp_host_spend_leaf.argtypes = [cp, cp, cp, cp, cp, u64, cp, cp]
         L.masp_host_allowed_conversion.argtypes = [C.c_size_t, cp, cp, cp]
+        L.masp_host_sapling_ka_agree.argtypes = [cp, cp, cp]
+        L.masp_host_diversifier_base.argtypes = [cp, cp]
+        L.masp_host_kdf_sapling.argtypes = [cp, cp, cp]
+        L.masp_host_kdf_sapling.restype = None
+        L.masp_host_prf_expand.argtypes = [cp, C.c_size_t, cp, C.c_size_t, cp]
+        L.masp_host_prf_expand.restype = None
+        L.masp_host_sapling_rseed_scalar.argtypes = [cp, C.c_int, cp]
+        L.masp_host_sapling_rseed_scalar.restype = None
+        L.masp_host_chacha20poly1305_encrypt.argtypes = [cp, cp, cp, C.c_size_t, cp, cp]
+        L.masp_host_chacha20poly1305_encrypt.restype = None
+        L.masp_host_chacha20poly1305_decrypt.argtypes = [cp, cp, cp, C.c_size_t, cp, cp]
+        L.masp_host_sapling_note_encrypt.argtypes = [cp, cp, cp, cp, cp, cp]
+        L.masp_host_sapling_try_note_decryption.argtypes = [cp, cp, cp, cp, C.c_int, cp, cp]
+        L.masp_host_sapling_finish_note_decryption.argtypes = [cp, cp, cp, cp, cp, C.c_int, cp, cp]
+        L.masp_host_sapling_try_note_decryption_batch.argtypes = [C.c_size_t, vp, C.c_size_t, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -467,3 +485,98 @@ def merkle_root(leaf, path_siblings, position):
     for i, sib in enumerate(path_siblings):
         cur = merkle_hash(i, _b(sib), cur) if (position >> i) & 1 else merkle_hash(i, cur, _b(sib))
     return cur
+
+
+# ---- Sapling note encryption and trial decryption (csrc/host/note_encryption.h) ----
+def sapling_ka_agree(sk, point):
+    """[8 sk] P as 32 bytes (sapling_ka_agree)"""
+    out = C.create_string_buffer(32)
+    _check(load_library().masp_host_sapling_ka_agree(_b(sk), _b(point), out))
+    return out.raw
+
+
+def diversifier_base(diversifier):
+    """Diversifier::g_d as 32 bytes; HostError(2) if the diversifier has none"""
+    out = C.create_string_buffer(32)
+    _check(load_library().masp_host_diversifier_base(_b(diversifier, 11), out))
+    return out.raw
+
+
+def kdf_sapling(secret, epk):
+    out = C.create_string_buffer(32)
+    load_library().masp_host_kdf_sapling(_b(secret), _b(epk), out)
+    return out.raw
+
+
+def prf_expand(sk, t):
+    out = C.create_string_buffer(64)
+    sk, t = bytes(sk), bytes(t)
+    load_library().masp_host_prf_expand(sk, len(sk), t, len(t), out)
+    return out.raw
+
+
+def sapling_rseed_scalar(rseed, domain):
+    """PRF^expand(rseed, [domain]) mod r_J as 32 bytes: domain 4 = rcm, 5 = esk"""
+    out = C.create_string_buffer(32)
+    load_library().masp_host_sapling_rseed_scalar(_b(rseed), domain, out)
+    return out.raw
+
+
+def chacha20poly1305_encrypt(key, nonce, plaintext):
+    """-> (ciphertext, tag); no associated data"""
+    plaintext = bytes(plaintext)
+    ct, tag = C.create_string_buffer(max(1, len(plaintext))), C.create_string_buffer(16)
+    load_library().masp_host_chacha20poly1305_encrypt(_b(key), _b(nonce, 12), plaintext, len(plaintext), ct, tag)
+    return ct.raw[:len(plaintext)], tag.raw
+
+
+def chacha20poly1305_decrypt(key, nonce, ciphertext, tag):
+    """-> plaintext, or None if the tag does not verify"""
+    ciphertext = bytes(ciphertext)
+    pt = C.create_string_buffer(max(1, len(ciphertext)))
+    rc = load_library().masp_host_chacha20poly1305_decrypt(_b(key), _b(nonce, 12), ciphertext, len(ciphertext), _b(tag, 16), pt)
+    return pt.raw[:len(ciphertext)] if rc == 0 else None
+
+
+def sapling_note_encrypt(esk, diversifier, pk_d, plaintext):
+    """-> (epk, enc_ciphertext) of a 596-byte note plaintext under the given esk"""
+    epk, enc = C.create_string_buffer(32), C.create_string_buffer(ENC_CIPHERTEXT_SIZE)
+    _check(load_library().masp_host_sapling_note_encrypt(_b(esk), _b(diversifier, 11), _b(pk_d), _b(plaintext, NOTE_PLAINTEXT_SIZE), epk, enc))
+    return epk.raw, enc.raw
+
+
+def sapling_try_note_decryption(ivk, epk, cmu, enc_ciphertext, lead_byte=2):
+    """-> (plaintext[596], pk_d[32]) or None"""
+    pt, pk = C.create_string_buffer(NOTE_PLAINTEXT_SIZE), C.create_string_buffer(32)
+    rc = load_library().masp_host_sapling_try_note_decryption(_b(ivk), _b(epk), _b(cmu), _b(enc_ciphertext, ENC_CIPHERTEXT_SIZE), lead_byte, pt, pk)
+    if rc == E_NO_NOTE:
+        return None
+    _check(rc)
+    return pt.raw, pk.raw
+
+
+def sapling_finish_note_decryption(key, ivk, epk, cmu, enc_ciphertext, lead_byte=2):
+    """the same from the symmetric key on -> (plaintext[596], pk_d[32]) or None"""
+    pt, pk = C.create_string_buffer(NOTE_PLAINTEXT_SIZE), C.create_string_buffer(32)
+    rc = load_library().masp_host_sapling_finish_note_decryption(_b(key), _b(ivk), _b(epk), _b(cmu), _b(enc_ciphertext, ENC_CIPHERTEXT_SIZE),
+                                                                 lead_byte, pt, pk)
+    if rc == E_NO_NOTE:
+        return None
+    _check(rc)
+    return pt.raw, pk.raw
+
+
+def sapling_try_note_decryption_batch(ivks, epks, cmus, enc_ciphertexts, lead_byte=2, threads=None):
+    """batch::try_note_decryption on host threads: (hit_ivk int32[n_out] (-1: none), plaintexts uint8[n_out, 596], pk_ds uint8[n_out, 32])"""
+    def arr(x, w):
+        a = np.frombuffer(b"".join(bytes(i) for i in x), dtype=np.uint8) if isinstance(x, (list, tuple)) else np.ascontiguousarray(x, dtype=np.uint8)
+        return a.reshape(-1, w)
+    ivks, epks, cmus, encs = arr(ivks, 32), arr(epks, 32), arr(cmus, 32), arr(enc_ciphertexts, ENC_CIPHERTEXT_SIZE)
+    n = epks.shape[0]
+    assert cmus.shape[0] == n and encs.shape[0] == n
+    hit = np.full(n, -1, np.int32)
+    pts, pks = np.zeros((n, NOTE_PLAINTEXT_SIZE), np.uint8), np.zeros((n, 32), np.uint8)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(load_library().masp_host_sapling_try_note_decryption_batch(ivks.shape[0], vp(ivks), n, vp(epks), vp(cmus), vp(encs), lead_byte,
+                                                                       threads or effective_cpus(), vp(hit), vp(pts), vp(pks)))
+    return hit, pts, pks

@@ -1,0 +1,91 @@
+"""Sapling note encryption and trial decryption for MASP: the mirror of `masp_note_encryption` over
+`masp_primitives::sapling::note_encryption::SaplingDomain`.
+
+`sapling_note_encrypt` and `try_sapling_note_decryption` run on the host (libmasp_host.so); `batch.try_note_decryption` scans
+outputs x ivks on the GPU (masp_hip_sapling_trial_decrypt: key agreement, KDF and the AEAD's tag for every pair) and finishes the pairs
+whose tag verifies on the host (masp_host_sapling_finish_note_decryption: decryption, parsing, the commitment, the esk check).
+Outgoing ciphertexts and recovery with an ovk are not mirrored."""
+from collections import namedtuple
+
+import numpy as np
+
+from . import host as H
+
+NOTE_PLAINTEXT_SIZE = H.NOTE_PLAINTEXT_SIZE
+ENC_CIPHERTEXT_SIZE = H.ENC_CIPHERTEXT_SIZE
+MEMO_SIZE = 512
+
+PaymentAddress = namedtuple("PaymentAddress", "diversifier pk_d")             # 11 bytes, 32 bytes
+Rseed = namedtuple("Rseed", "lead_byte bytes")                                # 1: BeforeZip212(rcm), 2: AfterZip212(rseed)
+Note = namedtuple("Note", "asset_identifier value pk_d rseed")                # 32 bytes, int, 32 bytes, Rseed
+ShieldedOutput = namedtuple("ShieldedOutput", "epk cmu enc_ciphertext")       # ephemeral_key, cmstar_bytes, enc_ciphertext
+EMPTY_MEMO = b"\xf6" + bytes(MEMO_SIZE - 1)
+
+
+def note_rcm(note):
+    """Note::rcm as 32 bytes"""
+    return bytes(note.rseed.bytes) if note.rseed.lead_byte == 1 else H.sapling_rseed_scalar(note.rseed.bytes, 4)
+
+
+def note_derive_esk(note):
+    """Note::derive_esk: None before ZIP 212"""
+    return None if note.rseed.lead_byte == 1 else H.sapling_rseed_scalar(note.rseed.bytes, 5)
+
+
+def note_cmu(note, to):
+    return H.note_cmu(note.asset_identifier, note.value, to.diversifier, note.pk_d, note_rcm(note))
+
+
+def note_plaintext_bytes(note, to, memo=EMPTY_MEMO):
+    """SaplingDomain::note_plaintext_bytes"""
+    memo = bytes(memo)
+    assert len(memo) == MEMO_SIZE and note.rseed.lead_byte in (1, 2)
+    pt = bytes([note.rseed.lead_byte]) + bytes(to.diversifier) + int(note.value).to_bytes(8, "little") + bytes(note.asset_identifier) + \
+        bytes(note.rseed.bytes) + memo
+    assert len(pt) == NOTE_PLAINTEXT_SIZE
+    return pt
+
+
+def _parse(plaintext, pk_d):
+    lead, d, value = plaintext[0], plaintext[1:12], int.from_bytes(plaintext[12:20], "little")
+    note = Note(plaintext[20:52], value, pk_d, Rseed(lead, plaintext[52:84]))
+    return note, PaymentAddress(d, pk_d), plaintext[84:]
+
+
+def sapling_note_encrypt(note, to, memo=EMPTY_MEMO, esk=None):
+    """-> ShieldedOutput.  esk: 32 bytes; default the note's derived one (ZIP 212), which a lead-byte-1 note does not have."""
+    esk = esk if esk is not None else note_derive_esk(note)
+    assert esk is not None, "a note before ZIP 212 needs an esk"
+    epk, enc = H.sapling_note_encrypt(esk, to.diversifier, to.pk_d, note_plaintext_bytes(note, to, memo))
+    return ShieldedOutput(epk, note_cmu(note, to), enc)
+
+
+def try_sapling_note_decryption(ivk, output, lead_byte=2):
+    """-> (Note, PaymentAddress, memo) or None.  ivk: 32 bytes or an int below r_J; lead_byte: the one valid at the output's height."""
+    r = H.sapling_try_note_decryption(ivk, output.epk, output.cmu, output.enc_ciphertext, lead_byte)
+    return None if r is None else _parse(*r)
+
+
+class batch:
+    """masp_note_encryption::batch"""
+
+    @staticmethod
+    def try_note_decryption(ivks, outputs, ctx, lead_byte=2):
+        """One entry per output, in order: None or ((Note, PaymentAddress, memo), index of the first ivk of the list for which the whole
+        check succeeds).  ctx: a masp_amd.Context; the scan runs on its GPU."""
+        outputs = list(outputs)
+        ivks = [H._b(k) for k in ivks]
+        result = [None] * len(outputs)
+        if not ivks or not outputs:
+            return result
+        epks = np.frombuffer(b"".join(bytes(o.epk) for o in outputs), dtype=np.uint8)
+        encs = np.frombuffer(b"".join(bytes(o.enc_ciphertext) for o in outputs), dtype=np.uint8)
+        _, hit_output, hit_ivk, hit_keys = ctx.sapling_trial_decrypt(b"".join(ivks), epks, encs)
+        for o, k, key in zip(hit_output.tolist(), hit_ivk.tolist(), hit_keys):   # sorted by (output, ivk): the first success wins
+            if result[o] is not None:
+                continue
+            out = outputs[o]
+            r = H.sapling_finish_note_decryption(key.tobytes(), ivks[k], out.epk, out.cmu, out.enc_ciphertext, lead_byte)
+            if r is not None:
+                result[o] = (_parse(*r), k)
+        return result
