@@ -313,6 +313,29 @@ int masp_hip_sapling_trial_decrypt(masp_hip_ctx* ctx, size_t n_ivk, const uint8_
 int masp_hip_note_scan_configure(masp_hip_ctx* ctx, int signed_digits, int inversion);
 int masp_hip_note_scan_last_timing(masp_hip_ctx* ctx, double ms[2]);
 
+/* ---- Compact (ZIP 307) batch trial decryption of Sapling notes on the GPU ----
+ * masp_hip_sapling_compact_trial_decrypt <- masp_note_encryption::batch::try_compact_note_decryption over SaplingDomain
+ *    (masp_note_encryption/src/batch.rs:35, lib.rs:589-624), ALL of it.  A compact output carries epk, cmu and the first 84 bytes of
+ * enc_ciphertext (the note plaintext without its memo) and so no tag: the only cheap test of a pair is the lead byte, which one pair of noise
+ * in 256 passes.  Stage 1 does for every pair the key agreement, the KDF and ChaCha20 block 1 and compares decrypted byte 0 with lead_byte;
+ * stage 2 does for the pairs that pass (the candidates) everything else the reference does: decryption of the 84 bytes, parsing,
+ * AssetType::from_identifier, a canonical rcm for lead byte 1, g_d, pk_d = [ivk] g_d != identity, the Pedersen note commitment against cmu
+ * and, for lead byte 2, [esk] g_d against epk.
+ * ivks, epks, epk_status, n_ivk / n_out limits, hit_capacity / MASP_HIP_E_CAPACITY, the (output, ivk) order, empty lists, determinism, streams
+ * and locking: as masp_hip_sapling_trial_decrypt (the two scans of a context exclude each other).  cmus: n_out x 32; enc_compact: n_out x 84;
+ * lead_byte: 1 or 2, the one valid at the outputs' height, anything else MASP_HIP_E_INVALID_ARG.
+ * Result: *n_hits pairs for which the WHOLE check succeeds: hit_output[i], hit_ivk[i], the note plaintext hit_plaintexts[84 i ..] and
+ * pk_d hit_pk_d[32 i ..].  The hits are final: the host finishes nothing, and of an output's hits the first is the reference's answer.
+ * *n_candidates (may be NULL): the pairs whose epk decodes and whose decrypted byte 0 equals lead_byte
+ * (= masp_host_sapling_try_compact_note_decryption_batch's count).
+ * masp_hip_note_scan_compact_last_timing - of the last compact scan of this context, summed over its chunks from HIP events on their streams:
+ * ms[0] the host-to-device copies, ms[1] stage 1 (decode and trial), ms[2] stage 2. */
+int masp_hip_sapling_compact_trial_decrypt(masp_hip_ctx* ctx, size_t n_ivk, const uint8_t* ivks, size_t n_out, const uint8_t* epks,
+                                           const uint8_t* cmus, const uint8_t* enc_compact, int lead_byte, uint8_t* epk_status,
+                                           size_t hit_capacity, uint32_t* hit_output, uint32_t* hit_ivk, uint8_t* hit_plaintexts,
+                                           uint8_t* hit_pk_d, size_t* n_hits, size_t* n_candidates);
+int masp_hip_note_scan_compact_last_timing(masp_hip_ctx* ctx, double ms[3]);
+
 /* ---- measurement hooks (bench.py): device-resident workloads, HIP-event timing on the ctx stream ---- */
 /* Keeps `n` jobs' assignments resident in HBM; returns a handle (>= 0) or a negative error code. */
 int masp_hip_batch_upload(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs);

@@ -158,6 +158,18 @@ int masp_host_sapling_finish_note_decryption(const uint8_t key[32], const uint8_
 int masp_host_sapling_try_note_decryption_batch(size_t n_ivk, const uint8_t* ivks, size_t n_out, const uint8_t* epks, const uint8_t* cmus,
                                                 const uint8_t* encs, int lead_byte, int threads, int32_t* hit_ivk, uint8_t* plaintexts,
                                                 uint8_t* pk_ds);
+/* The compact (ZIP 307) form, try_sapling_compact_note_decryption (masp_note_encryption/src/lib.rs:589-624): a compact output carries
+ * epk, cmu and the first 84 bytes of enc_ciphertext (the note plaintext without its memo), so there is no tag: the 84 bytes are decrypted with
+ * the keystream from block 1 and everything after decryption is what the full form does (the same refusals, the tag apart).
+ * MASP_HOST_OK: plaintext84_out and pk_d_out are written; MASP_HOST_E_NO_NOTE otherwise. */
+int masp_host_sapling_try_compact_note_decryption(const uint8_t ivk[32], const uint8_t epk[32], const uint8_t cmu[32], const uint8_t enc84[84],
+                                                  int lead_byte, uint8_t plaintext84_out[84], uint8_t pk_d_out[32]);
+/* batch::try_compact_note_decryption on `threads` host threads, results as in the full batch form (plaintexts84: n_out x 84).  n_candidates
+ * (may be NULL): the number of (output, ivk) pairs whose epk decodes and whose decrypted byte 0 equals lead_byte: the pairs that pass the
+ * compact form's only cheap filter, what masp_hip_sapling_compact_trial_decrypt's candidate count is compared with */
+int masp_host_sapling_try_compact_note_decryption_batch(size_t n_ivk, const uint8_t* ivks, size_t n_out, const uint8_t* epks, const uint8_t* cmus,
+                                                        const uint8_t* encs84, int lead_byte, int threads, int32_t* hit_ivk, uint8_t* plaintexts84,
+                                                        uint8_t* pk_ds, uint64_t* n_candidates);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,22 @@ MASP_HD JExt jj_add(const JExt& p, const JExt& q) {
     return {fe_mul(E, F), fe_mul(G, H), fe_mul(F, G), fe_mul(E, H)};
 }
 
+// an affine point as (v - u, v + u, 2 d u v): the second operand of a mixed addition
+struct JNiels {
+    Fr vmu, vpu, t2d;
+};
+
+// p + q (negated if `negate`), q affine in Niels form: 7 products.  (`negate` is wave-uniform in the note scan's ladder.)
+MASP_HD JExt jj_add_niels(const JExt& p, const JNiels& q, bool negate) {
+    const Fr A = fe_mul(fe_sub(p.V, p.U), negate ? q.vpu : q.vmu);
+    const Fr B = fe_mul(fe_add(p.V, p.U), negate ? q.vmu : q.vpu);
+    Fr C = fe_mul(p.T, q.t2d);
+    if (negate) C = fe_neg(C);
+    const Fr D = fe_dbl(p.Z);
+    const Fr E = fe_sub(B, A), F = fe_sub(D, C), G = fe_add(D, C), H = fe_add(B, A);
+    return {fe_mul(E, F), fe_mul(G, H), fe_mul(F, G), fe_mul(E, H)};
+}
+
 // 2p for a = -1: 4 squarings + 4 products (= jj_add(p, p))
 MASP_HD JExt jj_dbl(const JExt& p) {
     const Fr A = fe_sqr(p.U), B = fe_sqr(p.V), C = fe_dbl(fe_sqr(p.Z));

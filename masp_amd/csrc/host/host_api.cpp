@@ -815,4 +815,53 @@ int masp_host_sapling_try_note_decryption_batch(size_t n_ivk, const uint8_t* ivk
     for (auto& t : pool) t.join();
     return MASP_HOST_OK;
 }
+int masp_host_sapling_try_compact_note_decryption(const uint8_t ivk[32], const uint8_t epk[32], const uint8_t cmu[32], const uint8_t enc84[84],
+                                                  int lead_byte, uint8_t plaintext84_out[84], uint8_t pk_d_out[32]) {
+    if (!rj_is_canonical(ivk)) return MASP_HOST_E_INVALID;
+    return try_compact_note_decryption(ivk, epk, cmu, enc84, lead_byte, plaintext84_out, pk_d_out) ? MASP_HOST_OK : MASP_HOST_E_NO_NOTE;
+}
+// batch::try_compact_note_decryption on `threads` host threads: per output the first ivk of the list for which the whole check succeeds;
+// n_candidates (may be null): the pairs whose epk decodes and whose decrypted byte 0 is lead_byte
+int masp_host_sapling_try_compact_note_decryption_batch(size_t n_ivk, const uint8_t* ivks, size_t n_out, const uint8_t* epks, const uint8_t* cmus,
+                                                        const uint8_t* encs84, int lead_byte, int threads, int32_t* hit_ivk, uint8_t* plaintexts84,
+                                                        uint8_t* pk_ds, uint64_t* n_candidates) {
+    for (size_t k = 0; k < n_ivk; ++k)
+        if (!rj_is_canonical(ivks + 32 * k)) return MASP_HOST_E_INVALID;
+    std::atomic<size_t> next{0};
+    std::atomic<uint64_t> candidates{0};
+    auto work = [&] {
+        uint64_t mine = 0;
+        for (;;) {
+            const size_t o = next.fetch_add(1);
+            if (o >= n_out) break;
+            hit_ivk[o] = -1;
+            JPoint e;
+            if (!JPoint::from_bytes(e, epks + 32 * o)) continue;
+            for (size_t k = 0; k < n_ivk; ++k) {   // (every ivk: the count is over all pairs, the result the first success)
+                uint8_t secret[32], key[32], pt[COMPACT_NOTE_SIZE], pk[32];
+                ka_agree(ivks + 32 * k, e).to_bytes(secret);
+                kdf_sapling(key, secret, epks + 32 * o);
+                bool cand = false;
+                const bool ok = finish_compact_note_decryption(key, ivks + 32 * k, epks + 32 * o, cmus + 32 * o, encs84 + COMPACT_NOTE_SIZE * o,
+                                                               lead_byte, pt, pk, &cand);
+                mine += cand;
+                if (ok && hit_ivk[o] < 0) {
+                    hit_ivk[o] = (int32_t)k;
+                    memcpy(plaintexts84 + COMPACT_NOTE_SIZE * o, pt, COMPACT_NOTE_SIZE);
+                    memcpy(pk_ds + 32 * o, pk, 32);
+                }
+            }
+        }
+        candidates += mine;
+    };
+    (void)generators();          // the lazily built tables, before the threads race for them
+    (void)pedersen_windows();
+    const int nt = std::max(1, std::min<int>(threads, 256));
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nt; ++t) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+    if (n_candidates) *n_candidates = candidates.load();
+    return MASP_HOST_OK;
+}
 }  // extern "C"

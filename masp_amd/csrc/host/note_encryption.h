@@ -1,7 +1,8 @@
 // Sapling note encryption for MASP on the host: key agreement, KDF, the AEAD, note-plaintext parsing and the full trial decryption of
 // `try_sapling_note_decryption` (masp_note_encryption/src/lib.rs:492-577 over masp_primitives/src/sapling/note_encryption.rs:62-86,
 // :112-150, :194-260).  The single-output API of the product, the finisher of the GPU scan's hits (k_note_scan.hip stops at the
-// tag) and what that scan is tested against.  Outgoing ciphertexts and ovk recovery are not here.
+// tag) and what that scan is tested against; and the compact (ZIP 307) form of lib.rs:589-624, which has no tag and which the GPU's
+// compact scan (k_note_scan_compact.hip) is tested and measured against.  Outgoing ciphertexts and ovk recovery are not here.
 #pragma once
 #include "blake2b.h"
 #include "chacha20poly1305.h"
@@ -86,11 +87,12 @@ inline bool note_encrypt(const uint8_t esk[32], const uint8_t diversifier[11], c
     return true;
 }
 
-// try_note_decryption_inner: everything after the KDF.  On success the 596-byte plaintext and pk_d = [ivk] g_d are written.
-inline bool finish_note_decryption(const uint8_t key[32], const uint8_t ivk[32], const uint8_t epk[32], const uint8_t cmu[32], const uint8_t* enc,
-                                   int lead_byte, uint8_t* plaintext_out, uint8_t pk_d_out[32]) {
-    uint8_t pt[NOTE_PLAINTEXT_SIZE];
-    if (!aead_decrypt(pt, key, NOTE_NONCE, enc, NOTE_PLAINTEXT_SIZE, enc + NOTE_PLAINTEXT_SIZE)) return false;
+// Everything after decryption, shared by the full and the compact path: sapling_parse_note_plaintext_without_memo (the lead byte,
+// AssetType::from_identifier, a canonical rcm for lead byte 1, g_d, pk_d = [ivk] g_d != identity) and check_note_validity (the commitment,
+// then for lead byte 2 the ephemeral key the rseed implies).  pt: the first 84 bytes of the note plaintext.
+constexpr size_t COMPACT_NOTE_SIZE = 1 + 11 + 8 + 32 + 32;   // the note plaintext without its memo: what a compact output carries
+inline bool check_note_plaintext(const uint8_t* pt, const uint8_t ivk[32], const uint8_t epk[32], const uint8_t cmu[32], int lead_byte,
+                                 uint8_t pk_d_out[32]) {
     // sapling_parse_note_plaintext_without_memo
     if (pt[0] != (uint8_t)lead_byte || (lead_byte != 1 && lead_byte != 2)) return false;
     const uint8_t *diversifier = pt + 1, *asset = pt + 20, *r = pt + 52;
@@ -116,8 +118,33 @@ inline bool finish_note_decryption(const uint8_t key[32], const uint8_t ivk[32],
         gd.mul(esk).to_bytes(got);
         if (memcmp(got, epk, 32) != 0) return false;
     }
-    memcpy(plaintext_out, pt, NOTE_PLAINTEXT_SIZE);
     pk.to_bytes(pk_d_out);
+    return true;
+}
+
+// try_note_decryption_inner: everything after the KDF.  On success the 596-byte plaintext and pk_d = [ivk] g_d are written.
+inline bool finish_note_decryption(const uint8_t key[32], const uint8_t ivk[32], const uint8_t epk[32], const uint8_t cmu[32], const uint8_t* enc,
+                                   int lead_byte, uint8_t* plaintext_out, uint8_t pk_d_out[32]) {
+    uint8_t pt[NOTE_PLAINTEXT_SIZE], pk[32];
+    if (!aead_decrypt(pt, key, NOTE_NONCE, enc, NOTE_PLAINTEXT_SIZE, enc + NOTE_PLAINTEXT_SIZE)) return false;
+    if (!check_note_plaintext(pt, ivk, epk, cmu, lead_byte, pk)) return false;
+    memcpy(plaintext_out, pt, NOTE_PLAINTEXT_SIZE);
+    memcpy(pk_d_out, pk, 32);
+    return true;
+}
+
+// try_compact_note_decryption_inner (masp_note_encryption/src/lib.rs:607-624): no tag to check: the keystream from block 1 over the 84
+// bytes, then the same parsing and validity check.  candidate (may be null): whether decrypted byte 0 equals lead_byte, the only
+// cheap filter the compact form has.
+inline bool finish_compact_note_decryption(const uint8_t key[32], const uint8_t ivk[32], const uint8_t epk[32], const uint8_t cmu[32],
+                                           const uint8_t* enc84, int lead_byte, uint8_t* plaintext84_out, uint8_t pk_d_out[32],
+                                           bool* candidate = nullptr) {
+    uint8_t pt[COMPACT_NOTE_SIZE], pk[32];
+    chacha20_xor(pt, enc84, COMPACT_NOTE_SIZE, key, 1, NOTE_NONCE);
+    if (candidate) *candidate = pt[0] == (uint8_t)lead_byte;
+    if (!check_note_plaintext(pt, ivk, epk, cmu, lead_byte, pk)) return false;
+    memcpy(plaintext84_out, pt, COMPACT_NOTE_SIZE);
+    memcpy(pk_d_out, pk, 32);
     return true;
 }
 
@@ -130,6 +157,17 @@ inline bool try_note_decryption(const uint8_t ivk[32], const uint8_t epk[32], co
     ka_agree(ivk, e).to_bytes(secret);
     kdf_sapling(key, secret, epk);
     return finish_note_decryption(key, ivk, epk, cmu, enc, lead_byte, plaintext_out, pk_d_out);
+}
+
+// try_compact_note_decryption for one ivk and one compact output (masp_note_encryption/src/lib.rs:589-624)
+inline bool try_compact_note_decryption(const uint8_t ivk[32], const uint8_t epk[32], const uint8_t cmu[32], const uint8_t* enc84, int lead_byte,
+                                        uint8_t* plaintext84_out, uint8_t pk_d_out[32]) {
+    JPoint e;
+    if (!JPoint::from_bytes(e, epk)) return false;   // Domain::epk
+    uint8_t secret[32], key[32];
+    ka_agree(ivk, e).to_bytes(secret);
+    kdf_sapling(key, secret, epk);
+    return finish_compact_note_decryption(key, ivk, epk, cmu, enc84, lead_byte, plaintext84_out, pk_d_out);
 }
 
 }  // namespace masp_host

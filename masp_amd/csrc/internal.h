@@ -376,6 +376,17 @@ struct masp_hip_ctx {
     DevBuf<uint32_t> ns_digits;
     std::atomic<int> ns_signed_digits{1}, ns_inversion{0};   // masp_hip_note_scan_configure; the defaults are the measured winners (KERNELS.md)
     double ns_last_ms[2] = {0, 0};                           // masp_hip_note_scan_last_timing (under slot_mu)
+    // the compact note scan (k_note_scan_compact.hip: masp_hip_sapling_compact_trial_decrypt) runs under ns_mu too, on the same two streams,
+    // and decodes the epks into ns[set].epk / pts / status; what it has beyond that: per set the cmus, the 84-byte rows, the candidate list
+    // of stage 1 and the per-candidate state of stage 2 (sized for the launch's pair count), the survivor lists and the final hits
+    struct NoteScanCompactSet {
+        DevBuf<uint8_t> cmu, enc, cand, state, hit_idx, hit_data;
+        DevBuf<uint32_t> count, list;
+    };
+    NoteScanCompactSet nsc[2];
+    DevBuf<uint8_t> nsc_ivks;         // the ivks as they come: stage 2's per-lane scalars
+    DevBuf<uint8_t> nsc_table;        // the Pedersen Niels table and G_ncr behind it, uploaded at the first compact scan
+    double nsc_last_ms[3] = {0, 0, 0};   // masp_hip_note_scan_compact_last_timing: upload, stage 1, stage 2 (under slot_mu)
 };
 
 namespace masp {
@@ -402,6 +413,16 @@ static inline int get_domain(masp_hip_ctx* ctx, uint32_t logm, NttDomain** out) 
     *out = it->second.get();
     return MASP_HIP_OK;
 }
+
+// the note scan's geometry and the pieces its two units share (defined in k_note_scan.hip)
+constexpr uint32_t NS_BLOCK = 256;
+constexpr size_t NS_MAX_IVKS = 4096;
+constexpr size_t NS_MAX_OUTPUTS = (size_t)1 << 26;
+constexpr size_t NS_CHUNK_PAIRS = (size_t)1 << 18;   // pairs per launch: one lane each, four waves on every SIMD of the chip
+// the digit masks of the trial kernels for n_ivk ivks (16 words each); MASP_HIP_E_INVALID_ARG if one is not below r_J
+int ns_recode_ivks(std::vector<uint32_t>& digits, size_t n_ivk, const uint8_t* ivks, bool signed_digits);
+// k_ns_decode over n epks of 32 bytes: a status byte and the Niels form (96 bytes) per output
+void launch_ns_decode(hipStream_t s, const uint8_t* epks, uint32_t n, uint8_t* status, uint8_t* pts);
 
 static inline uint32_t log2_ceil(uint32_t n) {
     uint32_t k = 0;

@@ -10,6 +10,7 @@
 // Kernels:  k_ns_decode   one lane per output: jj_decode of epk once, not once per ivk, stored in the affine form (v - u, v + u, 2d u v)
 //                         that makes the ladder's additions mixed ones of 7 products, and a status byte;
 //           k_ns_repitch  the 612-byte ciphertext rows into 16-byte columns (KERNELS.md: why);
+//                         (also the first kernel of the compact scan, k_note_scan_compact.hip);
 //           k_ns_trial    one lane per pair, the ivk constant across the workgroup (blockIdx.y): the scalar's digits are wave-uniform, so the
 //                         `if (digit)` of the double-and-add is a uniform branch, the scalar lives in SGPRs and no lane needs a table.
 #include <mutex>
@@ -17,6 +18,7 @@
 #include "device/blake2b.hpp"
 #include "device/chacha20.hpp"
 #include "device/jubjub.hpp"
+#include "device/note_scan.hpp"
 #include "device/poly1305.hpp"
 #include "internal.h"
 
@@ -24,38 +26,9 @@ using namespace masp;
 
 namespace {
 
-constexpr uint32_t NS_BLOCK = 256;
 constexpr size_t NS_ENC = 612;            // enc_ciphertext: 596 bytes of note plaintext under ChaCha20, the 16-byte tag
 constexpr uint32_t NS_ENC_WORDS = 153;
 constexpr uint32_t NS_COLS = 39;          // 16-byte columns of a repitched row (156 words: three of padding)
-constexpr size_t NS_MAX_IVKS = 4096;
-constexpr size_t NS_MAX_OUTPUTS = (size_t)1 << 26;
-constexpr size_t NS_CHUNK_PAIRS = (size_t)1 << 18;   // pairs per launch: one lane each, four waves on every SIMD of the chip
-
-struct JNiels {
-    Fr vmu, vpu, t2d;   // v - u, v + u, 2 d u v of an affine point
-};
-
-// p + q (negated if `negate`), q affine in Niels form: 7 products.  `negate` is wave-uniform in k_ns_trial.
-__device__ __forceinline__ JExt jj_add_niels(const JExt& p, const JNiels& q, bool negate) {
-    const Fr A = fe_mul(fe_sub(p.V, p.U), negate ? q.vpu : q.vmu);
-    const Fr B = fe_mul(fe_add(p.V, p.U), negate ? q.vmu : q.vpu);
-    Fr C = fe_mul(p.T, q.t2d);
-    if (negate) C = fe_neg(C);
-    const Fr D = fe_dbl(p.Z);
-    const Fr E = fe_sub(B, A), F = fe_sub(D, C), G = fe_add(D, C), H = fe_add(B, A);
-    return {fe_mul(E, F), fe_mul(G, H), fe_mul(F, G), fe_mul(E, H)};
-}
-
-// fe_inv (field.hpp) inlined: the out-of-line form takes its operand through scratch and, at 161 VGPRs, would set the kernel's register
-// count (a kernel is given the registers of its largest callee)
-__device__ __forceinline__ Fr fe_inv_divsteps_inline(const Fr& a) {
-    Fr r, r2;
-    FeDivsteps<FrCfg>::invert(r.v, a.v);   // (a R)^-1
-#pragma unroll
-    for (int i = 0; i < 8; ++i) r2.v[i] = FrCfg::R2[i];
-    return fe_mul_nc(fe_mul_nc(r, r2), r2);
-}
 
 __global__ __launch_bounds__(NS_BLOCK) void k_ns_decode(const uint4* __restrict__ epks, uint32_t n, uint8_t* __restrict__ status,
                                                         JNiels* __restrict__ pts) {
@@ -84,12 +57,6 @@ __global__ __launch_bounds__(NS_BLOCK) void k_ns_repitch(const uint32_t* __restr
     ct4[(size_t)c * n_pad + o] = v;
 }
 
-constexpr uint64_t le64_of(const char* s) {
-    uint64_t x = 0;
-    for (int i = 7; i >= 0; --i) x = (x << 8) | (uint8_t)s[i];
-    return x;
-}
-
 // digits: per ivk 16 words, [0..7] the mask of non-zero digits of its (plain or signed) binary recoding, [8..15] the mask of negative ones.
 // hits: count[0] pairs verified their tag; pair i < cap is (hit_idx[i] = output, ivk) with its key in hit_keys[2 i], [2 i + 1].
 // inversion: 0 the divstep inverse, 1 the binary-gcd one (field.hpp), for the one inversion of the encoding.
@@ -101,45 +68,8 @@ __global__ __launch_bounds__(NS_BLOCK) void k_ns_trial(const uint32_t* __restric
     const uint32_t o = blockIdx.x * NS_BLOCK + threadIdx.x, k = blockIdx.y;
     if (o >= n || status[o] != JJ_OK) return;
     const JNiels q = pts[o];
-    const uint32_t* dg = digits + 16 * k;   // wave-uniform: scalar loads
-    JExt r = jj_identity();
-    bool started = false;
-#pragma unroll 1
-    for (int w = 7; w >= 0; --w) {
-        const uint32_t nz = dg[w], ng = dg[8 + w];
-#pragma unroll 1
-        for (int b = 31; b >= 0; --b) {
-            if (started) r = jj_dbl(r);
-            if ((nz >> b) & 1u) {
-                r = jj_add_niels(r, q, (ng >> b) & 1u);   // (the first one adds to the identity: the law is complete)
-                started = true;
-            }
-        }
-    }
-    r = jj_mul_by_cofactor(r);
-    // encode(secret) || epk -> the key
-    uint64_t m[16], h[8];
-    {
-        const Fr zi = inversion == 1 ? fe_inv_bingcd(r.Z) : fe_inv_divsteps_inline(r.Z);
-        const Fr u = fe_from_mont(fe_mul(r.U, zi)), v = fe_from_mont(fe_mul(r.V, zi));
-        const uint32_t top = v.v[7] | ((u.v[0] & 1u) << 31);
-        m[0] = v.v[0] | ((uint64_t)v.v[1] << 32);
-        m[1] = v.v[2] | ((uint64_t)v.v[3] << 32);
-        m[2] = v.v[4] | ((uint64_t)v.v[5] << 32);
-        m[3] = v.v[6] | ((uint64_t)top << 32);
-    }
-    {
-        const uint4 e0 = epks[2 * o], e1 = epks[2 * o + 1];
-        m[4] = e0.x | ((uint64_t)e0.y << 32);
-        m[5] = e0.z | ((uint64_t)e0.w << 32);
-        m[6] = e1.x | ((uint64_t)e1.y << 32);
-        m[7] = e1.z | ((uint64_t)e1.w << 32);
-    }
-#pragma unroll
-    for (int i = 8; i < 16; ++i) m[i] = 0;
-    blake2b_one_block(h, m, 64, 32, le64_of("MASP__Sa"), le64_of("plingKDF"));
-    const uint32_t key[8] = {(uint32_t)h[0], (uint32_t)(h[0] >> 32), (uint32_t)h[1], (uint32_t)(h[1] >> 32),
-                             (uint32_t)h[2], (uint32_t)(h[2] >> 32), (uint32_t)h[3], (uint32_t)(h[3] >> 32)};
+    uint32_t key[8];
+    ns_pair_key(key, digits + 16 * k, q, epks + 2 * o, inversion);   // (digits: wave-uniform, scalar loads)
     const uint32_t nonce[3] = {0, 0, 0};
     uint32_t b0[16];
     chacha20_block(b0, key, 0, nonce);
@@ -228,7 +158,7 @@ int enqueue_chunk(masp_hip_ctx* ctx, ChunkInFlight& c, size_t n_ivk, const uint8
     HIP_TRY(hipMemcpyAsync(b.raw.p, encs + NS_ENC * c.o0, NS_ENC * c.n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(b.count.p, 0, sizeof(uint32_t), s));
     HIP_TRY(hipEventRecord(c.ev[1], s));
-    MASP_LAUNCH(k_ns_decode, dim3(nb), dim3(NS_BLOCK), 0, s, (const uint4*)b.epk.p, n, b.status.p, (JNiels*)b.pts.p);
+    launch_ns_decode(s, b.epk.p, n, b.status.p, b.pts.p);
     MASP_LAUNCH(k_ns_repitch, dim3(nb, NS_COLS), dim3(NS_BLOCK), 0, s, (const uint32_t*)b.raw.p, n, n_pad, (uint4*)b.ct.p);
     MASP_LAUNCH(k_ns_trial, dim3(nb, (uint32_t)n_ivk), dim3(NS_BLOCK), 0, s, (const uint32_t*)ctx->ns_digits.p, (const JNiels*)b.pts.p,
                 (const uint8_t*)b.status.p, (const uint4*)b.epk.p, (const uint4*)b.ct.p, n, n_pad, (uint32_t)c.o0, ctx->ns_inversion.load(),
@@ -275,6 +205,25 @@ int collect_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, size_t n_ivk, const
 
 }  // namespace
 
+namespace masp {
+
+int ns_recode_ivks(std::vector<uint32_t>& digits, size_t n_ivk, const uint8_t* ivks, bool signed_digits) {
+    digits.assign(16 * n_ivk, 0);
+    for (size_t k = 0; k < n_ivk; ++k) {
+        uint32_t w[8];
+        memcpy(w, ivks + 32 * k, 32);   // (little-endian host)
+        if (!below_rj(w)) return MASP_HIP_E_INVALID_ARG;
+        recode(&digits[16 * k], w, signed_digits);
+    }
+    return MASP_HIP_OK;
+}
+
+void launch_ns_decode(hipStream_t s, const uint8_t* epks, uint32_t n, uint8_t* status, uint8_t* pts) {
+    MASP_LAUNCH(k_ns_decode, dim3((n + NS_BLOCK - 1) / NS_BLOCK), dim3(NS_BLOCK), 0, s, (const uint4*)epks, n, status, (JNiels*)pts);
+}
+
+}  // namespace masp
+
 extern "C" {
 
 int masp_hip_sapling_trial_decrypt(masp_hip_ctx* ctx, size_t n_ivk, const uint8_t* ivks, size_t n_out, const uint8_t* epks,
@@ -284,13 +233,8 @@ int masp_hip_sapling_trial_decrypt(masp_hip_ctx* ctx, size_t n_ivk, const uint8_
         (hit_capacity && (!hit_output || !hit_ivk || !hit_keys)))
         return MASP_HIP_E_INVALID_ARG;
     *n_hits = 0;
-    std::vector<uint32_t> digits(16 * n_ivk);
-    for (size_t k = 0; k < n_ivk; ++k) {
-        uint32_t w[8];
-        memcpy(w, ivks + 32 * k, 32);   // (little-endian host)
-        if (!below_rj(w)) return MASP_HIP_E_INVALID_ARG;
-        recode(&digits[16 * k], w, FIRST_DEVICE(ctx)->ns_signed_digits.load() != 0);
-    }
+    std::vector<uint32_t> digits;
+    if (ns_recode_ivks(digits, n_ivk, ivks, FIRST_DEVICE(ctx)->ns_signed_digits.load() != 0)) return MASP_HIP_E_INVALID_ARG;
     if (n_ivk == 0 || n_out == 0) {
         if (epk_status && n_out) memset(epk_status, 0, n_out);   // (not looked at: no key asked for them)
         return MASP_HIP_OK;

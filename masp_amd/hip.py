@@ -130,6 +130,9 @@ def load_library():
         L.masp_hip_sapling_trial_decrypt.argtypes = [vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, C.POINTER(sz)]
         L.masp_hip_note_scan_configure.argtypes = [vp, C.c_int, C.c_int]
         L.masp_hip_note_scan_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
+    if hasattr(L, "masp_hip_sapling_compact_trial_decrypt"):
+        L.masp_hip_sapling_compact_trial_decrypt.argtypes = [vp, sz, vp, sz, vp, vp, vp, C.c_int, vp, sz, vp, vp, vp, vp, C.POINTER(sz), C.POINTER(sz)]
+        L.masp_hip_note_scan_compact_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
     L.masp_hip_batch_upload.argtypes = [vp, sz, vp]
     L.masp_hip_batch_prove_resident.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.masp_hip_batch_prove_resident_steps.argtypes = [vp, C.c_int, sz, vp, vp, C.POINTER(C.c_float)]
@@ -406,6 +409,39 @@ class Context:
         ms = (C.c_double * 2)()
         self._check(self._L.masp_hip_note_scan_last_timing(self._h, ms))
         return ms[0], ms[1]
+
+    def sapling_compact_trial_decrypt(self, ivks, epks, cmus, enc_compact, lead_byte=2, hit_capacity=None, count_candidates=True):
+        """batch::try_compact_note_decryption on the GPU, all of it (masp_hip_sapling_compact_trial_decrypt): ivks n_ivk x 32, epks and cmus
+        n_out x 32, enc_compact n_out x 84 (bytes or uint8 arrays) -> (epk_status uint8[n_out], hit_output uint32[h], hit_ivk uint32[h],
+        hit_plaintexts uint8[h, 84], hit_pk_d uint8[h, 32], n_candidates): the pairs for which the whole check succeeds, sorted by
+        (output, ivk); n_candidates: the pairs that passed the lead-byte test (None with count_candidates=False: a NULL pointer)."""
+        ivks, epks, cmus, encs = _u8(ivks, 32), _u8(epks, 32), _u8(cmus, 32), _u8(enc_compact, 84)
+        n_ivk, n_out = ivks.shape[0], epks.shape[0]
+        assert encs.shape[0] == n_out and cmus.shape[0] == n_out
+        status = np.zeros(n_out, dtype=np.uint8)
+        cap = max(16, n_out // 64) if hit_capacity is None else int(hit_capacity)
+        while True:
+            ho, hi = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+            hp, hk = np.zeros((cap, 84), np.uint8), np.zeros((cap, 32), np.uint8)
+            nh, nc = C.c_size_t(0), C.c_size_t(0)
+            rc = self._L.masp_hip_sapling_compact_trial_decrypt(self._h, n_ivk, _p(ivks), n_out, _p(epks), _p(cmus), _p(encs), int(lead_byte),
+                                                                _p(status), cap, _p(ho), _p(hi), _p(hp), _p(hk), C.byref(nh),
+                                                                C.byref(nc) if count_candidates else None)
+            if rc == E_CAPACITY and hit_capacity is None:
+                cap = nh.value
+                continue
+            if rc == E_CAPACITY:
+                e = MaspHipError(rc, "%d hits" % nh.value)
+                e.needed = nh.value
+                raise e
+            self._check(rc)
+            return status, ho[:nh.value], hi[:nh.value], hp[:nh.value], hk[:nh.value], (nc.value if count_candidates else None)
+
+    def note_scan_compact_last_timing(self):
+        """(upload ms, stage 1 ms, stage 2 ms) of the last compact scan, HIP events summed over its chunks"""
+        ms = (C.c_double * 3)()
+        self._check(self._L.masp_hip_note_scan_compact_last_timing(self._h, ms))
+        return ms[0], ms[1], ms[2]
 
     # ---- building blocks ----
     def msm_g1(self, bases, scalars):

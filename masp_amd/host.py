@@ -19,6 +19,7 @@ ERRORS = {1: "invalid encoding", 2: "invalid diversifier", 3: "synthesis error",
           5: "not a note of this key"}
 E_NO_NOTE = 5
 NOTE_PLAINTEXT_SIZE, ENC_CIPHERTEXT_SIZE = 596, 612
+COMPACT_NOTE_SIZE = 84     # the note plaintext without its memo: what a compact (ZIP 307) output carries of enc_ciphertext
 
 
 class HostError(RuntimeError):
@@ -84,6 +85,9 @@ def load_library():
         L.masp_host_sapling_try_note_decryption.argtypes = [cp, cp, cp, cp, C.c_int, cp, cp]
         L.masp_host_sapling_finish_note_decryption.argtypes = [cp, cp, cp, cp, cp, C.c_int, cp, cp]
         L.masp_host_sapling_try_note_decryption_batch.argtypes = [C.c_size_t, vp, C.c_size_t, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
+        L.masp_host_sapling_try_compact_note_decryption.argtypes = [cp, cp, cp, cp, C.c_int, cp, cp]
+        L.masp_host_sapling_try_compact_note_decryption_batch.argtypes = [C.c_size_t, vp, C.c_size_t, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp,
+                                                                         C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -580,3 +584,32 @@ def sapling_try_note_decryption_batch(ivks, epks, cmus, enc_ciphertexts, lead_by
     _check(load_library().masp_host_sapling_try_note_decryption_batch(ivks.shape[0], vp(ivks), n, vp(epks), vp(cmus), vp(encs), lead_byte,
                                                                        threads or effective_cpus(), vp(hit), vp(pts), vp(pks)))
     return hit, pts, pks
+
+
+def sapling_try_compact_note_decryption(ivk, epk, cmu, enc_compact, lead_byte=2):
+    """the compact (ZIP 307) form: enc_compact = the first 84 bytes of enc_ciphertext -> (plaintext[84], pk_d[32]) or None"""
+    pt, pk = C.create_string_buffer(COMPACT_NOTE_SIZE), C.create_string_buffer(32)
+    rc = load_library().masp_host_sapling_try_compact_note_decryption(_b(ivk), _b(epk), _b(cmu), _b(enc_compact, COMPACT_NOTE_SIZE), lead_byte, pt, pk)
+    if rc == E_NO_NOTE:
+        return None
+    _check(rc)
+    return pt.raw, pk.raw
+
+
+def sapling_try_compact_note_decryption_batch(ivks, epks, cmus, enc_compacts, lead_byte=2, threads=None):
+    """batch::try_compact_note_decryption on host threads: (hit_ivk int32[n_out] (-1: none), plaintexts uint8[n_out, 84], pk_ds uint8[n_out, 32],
+    the number of pairs whose epk decodes and whose decrypted byte 0 is lead_byte)"""
+    def arr(x, w):
+        a = np.frombuffer(b"".join(bytes(i) for i in x), dtype=np.uint8) if isinstance(x, (list, tuple)) else np.ascontiguousarray(x, dtype=np.uint8)
+        return a.reshape(-1, w)
+    ivks, epks, cmus, encs = arr(ivks, 32), arr(epks, 32), arr(cmus, 32), arr(enc_compacts, COMPACT_NOTE_SIZE)
+    n = epks.shape[0]
+    assert cmus.shape[0] == n and encs.shape[0] == n
+    hit = np.full(n, -1, np.int32)
+    pts, pks = np.zeros((n, COMPACT_NOTE_SIZE), np.uint8), np.zeros((n, 32), np.uint8)
+    cand = C.c_uint64(0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(load_library().masp_host_sapling_try_compact_note_decryption_batch(ivks.shape[0], vp(ivks), n, vp(epks), vp(cmus), vp(encs), lead_byte,
+                                                                               threads or effective_cpus(), vp(hit), vp(pts), vp(pks),
+                                                                               C.byref(cand)))
+    return hit, pts, pks, cand.value

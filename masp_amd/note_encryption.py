@@ -4,6 +4,11 @@
 `sapling_note_encrypt` and `try_sapling_note_decryption` run on the host (libmasp_host.so); `batch.try_note_decryption` scans
 outputs x ivks on the GPU (masp_hip_sapling_trial_decrypt: key agreement, KDF and the AEAD's tag for every pair) and finishes the pairs
 whose tag verifies on the host (masp_host_sapling_finish_note_decryption: decryption, parsing, the commitment, the esk check).
+
+The compact (ZIP 307) form, what a light wallet runs: a `CompactShieldedOutput` carries the first 84 bytes of enc_ciphertext (the note
+without its memo) and no tag.  `try_sapling_compact_note_decryption` runs on the host; `batch.try_compact_note_decryption` runs the WHOLE
+check on the GPU (masp_hip_sapling_compact_trial_decrypt: the lead byte for every pair, then parsing, group hashes, pk_d, the Pedersen
+note commitment and the esk check for the pairs that pass it), so its hits are final and the host finishes nothing.
 Outgoing ciphertexts and recovery with an ovk are not mirrored."""
 from collections import namedtuple
 
@@ -19,7 +24,14 @@ PaymentAddress = namedtuple("PaymentAddress", "diversifier pk_d")             # 
 Rseed = namedtuple("Rseed", "lead_byte bytes")                                # 1: BeforeZip212(rcm), 2: AfterZip212(rseed)
 Note = namedtuple("Note", "asset_identifier value pk_d rseed")                # 32 bytes, int, 32 bytes, Rseed
 ShieldedOutput = namedtuple("ShieldedOutput", "epk cmu enc_ciphertext")       # ephemeral_key, cmstar_bytes, enc_ciphertext
+CompactShieldedOutput = namedtuple("CompactShieldedOutput", "epk cmu enc_ciphertext")   # CompactOutputDescription: enc_ciphertext[84]
+COMPACT_NOTE_SIZE = H.COMPACT_NOTE_SIZE
 EMPTY_MEMO = b"\xf6" + bytes(MEMO_SIZE - 1)
+
+
+def compact_output(output):
+    """CompactOutputDescription::from(OutputDescription): the first 84 bytes of enc_ciphertext"""
+    return CompactShieldedOutput(bytes(output.epk), bytes(output.cmu), bytes(output.enc_ciphertext)[:COMPACT_NOTE_SIZE])
 
 
 def note_rcm(note):
@@ -66,6 +78,17 @@ def try_sapling_note_decryption(ivk, output, lead_byte=2):
     return None if r is None else _parse(*r)
 
 
+def _parse_compact(plaintext, pk_d):
+    note, to, _ = _parse(plaintext, pk_d)
+    return note, to
+
+
+def try_sapling_compact_note_decryption(ivk, output, lead_byte=2):
+    """-> (Note, PaymentAddress) or None, on the host.  output: a CompactShieldedOutput."""
+    r = H.sapling_try_compact_note_decryption(ivk, output.epk, output.cmu, output.enc_ciphertext, lead_byte)
+    return None if r is None else _parse_compact(*r)
+
+
 class batch:
     """masp_note_encryption::batch"""
 
@@ -88,4 +111,20 @@ class batch:
             r = H.sapling_finish_note_decryption(key.tobytes(), ivks[k], out.epk, out.cmu, out.enc_ciphertext, lead_byte)
             if r is not None:
                 result[o] = (_parse(*r), k)
+        return result
+
+    @staticmethod
+    def try_compact_note_decryption(ivks, outputs, ctx, lead_byte=2):
+        """One entry per CompactShieldedOutput, in order: None or ((Note, PaymentAddress), index of the first ivk of the list for which the
+        whole check succeeds).  The whole check runs on ctx's GPU: nothing is finished on the host."""
+        outputs = list(outputs)
+        ivks = [H._b(k) for k in ivks]
+        result = [None] * len(outputs)
+        if not ivks or not outputs:
+            return result
+        epks, cmus, encs = (np.frombuffer(b"".join(bytes(getattr(o, f)) for o in outputs), dtype=np.uint8) for f in ("epk", "cmu", "enc_ciphertext"))
+        _, hit_output, hit_ivk, hit_pt, hit_pk, _ = ctx.sapling_compact_trial_decrypt(b"".join(ivks), epks, cmus, encs, lead_byte)
+        for o, k, pt, pk in zip(hit_output.tolist(), hit_ivk.tolist(), hit_pt, hit_pk):   # sorted by (output, ivk): the first success wins
+            if result[o] is None:
+                result[o] = (_parse_compact(pt.tobytes(), pk.tobytes()), k)
         return result
