@@ -336,6 +336,25 @@ int masp_hip_sapling_compact_trial_decrypt(masp_hip_ctx* ctx, size_t n_ivk, cons
                                            uint8_t* hit_pk_d, size_t* n_hits, size_t* n_candidates);
 int masp_hip_note_scan_compact_last_timing(masp_hip_ctx* ctx, double ms[3]);
 
+/* ---- Batch output recovery with outgoing viewing keys on the GPU ----
+ * masp_hip_sapling_output_recovery_scan <- the device half of try_sapling_output_recovery
+ *    (masp_primitives/src/sapling/note_encryption.rs:539-551 over masp_note_encryption/src/lib.rs:635-718) for n_out outputs x n_ovk ovks:
+ * for each (output, ovk) pair PRF^ock (BLAKE2b-256, personal "MASP__Derive_ock", over ovk | cv | cmu | epk) and the Poly1305 tag of the
+ * AEAD over the 64 ciphertext bytes of out_ciphertext.  No decryption and no curve arithmetic on the device.
+ * ovks: n_ovk x 32, any bytes (an OutgoingViewingKey has no range); cvs, epks, cmus: n_out x 32, as they stand in the output descriptions;
+ * out_ciphertexts: n_out x 80.
+ * Result: *n_hits pairs whose tag verifies, sorted by (output, ovk): hit_output[i], hit_ovk[i] and the pair's ock in hit_ocks[32 i ..],
+ * ready for masp_host_sapling_try_output_recovery_with_ock, which decides.  A pair that is not reported is not a note sent under that ovk;
+ * of an output's reported pairs the first the host accepts is try_sapling_output_recovery's answer for the first such ovk of the list.
+ * n_ovk / n_out limits, hit_capacity / MASP_HIP_E_CAPACITY (*n_hits set, nothing written), empty lists (MASP_HIP_OK, no hits), determinism,
+ * chunks, streams and locking: as masp_hip_sapling_trial_decrypt (a context runs one scan of any kind at a time).
+ * masp_hip_out_recovery_last_timing - of the last such scan of this context, summed over its chunks from HIP events on their streams:
+ * ms[0] the host-to-device copies, ms[1] the kernels. */
+int masp_hip_sapling_output_recovery_scan(masp_hip_ctx* ctx, size_t n_ovk, const uint8_t* ovks, size_t n_out, const uint8_t* cvs,
+                                          const uint8_t* epks, const uint8_t* cmus, const uint8_t* out_ciphertexts, size_t hit_capacity,
+                                          uint32_t* hit_output, uint32_t* hit_ovk, uint8_t* hit_ocks, size_t* n_hits);
+int masp_hip_out_recovery_last_timing(masp_hip_ctx* ctx, double ms[2]);
+
 /* ---- measurement hooks (bench.py): device-resident workloads, HIP-event timing on the ctx stream ---- */
 /* Keeps `n` jobs' assignments resident in HBM; returns a handle (>= 0) or a negative error code. */
 int masp_hip_batch_upload(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs);

@@ -126,7 +126,7 @@ int masp_host_convert_cmu(const uint8_t generator[32], uint8_t out32[32]);
 /* ---- Sapling note encryption and trial decryption (masp_note_encryption, masp_primitives/src/sapling/note_encryption.rs).
  * A note plaintext is 596 bytes: lead byte (1: rcm follows, 2: a ZIP 212 rseed follows) | diversifier 11 | value u64 LE | asset identifier 32 |
  * rcm or rseed 32 | memo 512; enc_ciphertext is those 596 bytes under ChaCha20-Poly1305 (all-zero nonce, no associated data) and the
- * 16-byte tag.  ivk, esk: canonical scalars below r_J, else MASP_HOST_E_INVALID.  Out of scope: out_ciphertext, recovery with an ovk. ---- */
+ * 16-byte tag.  ivk, esk: canonical scalars below r_J, else MASP_HOST_E_INVALID. ---- */
 /* sapling_ka_agree: [8 sk] P as 32 bytes */
 int masp_host_sapling_ka_agree(const uint8_t sk[32], const uint8_t p32[32], uint8_t out32[32]);
 /* Diversifier::g_d as 32 bytes; MASP_HOST_E_DIVERSIFIER if the diversifier has none (pk_d = [ivk] g_d makes a payment address) */
@@ -170,6 +170,32 @@ int masp_host_sapling_try_compact_note_decryption(const uint8_t ivk[32], const u
 int masp_host_sapling_try_compact_note_decryption_batch(size_t n_ivk, const uint8_t* ivks, size_t n_out, const uint8_t* epks, const uint8_t* cmus,
                                                         const uint8_t* encs84, int lead_byte, int threads, int32_t* hit_ivk, uint8_t* plaintexts84,
                                                         uint8_t* pk_ds, uint64_t* n_candidates);
+
+/* ---- The sender's side: out_ciphertext and recovery with an outgoing viewing key (masp_note_encryption/src/lib.rs:450-481, :626-718;
+ * masp_primitives/src/sapling/note_encryption.rs:90-110, :517-551).  out_ciphertext is the 64 bytes op = pk_d | esk under
+ * ChaCha20-Poly1305 (all-zero nonce, no associated data) keyed by the ock, and the 16-byte tag: 80 bytes. ---- */
+/* PRF^ock: BLAKE2b-256 personalised "MASP__Derive_ock" over ovk | cv | cmu | epk.  cv: the 32 bytes as they stand in the output description
+ * (the reference re-encodes a decoded cv; decoding accepts canonical encodings only, so the bytes are the same) */
+void masp_host_prf_ock(const uint8_t ovk[32], const uint8_t cv[32], const uint8_t cmu[32], const uint8_t epk[32], uint8_t ock_out[32]);
+/* encrypt_outgoing_plaintext from the ock on: c_out = AEAD(ock, pk_d | esk).  The ovk = none case is the caller's: a random ock and random
+ * bytes in the place of pk_d | esk */
+void masp_host_sapling_encrypt_outgoing(const uint8_t ock[32], const uint8_t pk_d[32], const uint8_t esk[32], uint8_t c_out[80]);
+/* try_sapling_output_recovery_with_ock for one output (epk, cmu, enc_ciphertext, out_ciphertext), in the reference's order: c_out's tag and
+ * decryption; pk_d a canonical point of the prime-order subgroup; esk a canonical scalar; [8 esk] pk_d, the KDF, enc's tag and decryption;
+ * the lead byte, asset identifier, rcm, g_d, [esk] g_d = epk, pk_d != identity; for lead byte 2 the derived esk = op's; the commitment and the
+ * esk check.  MASP_HOST_OK: plaintext_out and pk_d_out are written; MASP_HOST_E_NO_NOTE: every refusal of the reference.  The second half
+ * of masp_hip_sapling_output_recovery_scan's hits. */
+int masp_host_sapling_try_output_recovery_with_ock(const uint8_t ock[32], const uint8_t epk[32], const uint8_t cmu[32], const uint8_t enc[612],
+                                                   const uint8_t c_out[80], int lead_byte, uint8_t plaintext_out[596], uint8_t pk_d_out[32]);
+/* try_sapling_output_recovery: PRF^ock, then the function above */
+int masp_host_sapling_try_output_recovery(const uint8_t ovk[32], const uint8_t cv[32], const uint8_t epk[32], const uint8_t cmu[32],
+                                          const uint8_t enc[612], const uint8_t c_out[80], int lead_byte, uint8_t plaintext_out[596],
+                                          uint8_t pk_d_out[32]);
+/* the same over n_out outputs x n_ovk ovks on `threads` host threads: hit_ovk[o] = the first ovk index that recovers output o, or -1;
+ * plaintexts (n_out x 596) and pk_ds (n_out x 32) are written for the hits */
+int masp_host_sapling_try_output_recovery_batch(size_t n_ovk, const uint8_t* ovks, size_t n_out, const uint8_t* cvs, const uint8_t* epks,
+                                                const uint8_t* cmus, const uint8_t* encs, const uint8_t* c_outs, int lead_byte, int threads,
+                                                int32_t* hit_ovk, uint8_t* plaintexts, uint8_t* pk_ds);
 
 #ifdef __cplusplus
 }

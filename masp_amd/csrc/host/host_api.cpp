@@ -864,4 +864,47 @@ int masp_host_sapling_try_compact_note_decryption_batch(size_t n_ivk, const uint
     if (n_candidates) *n_candidates = candidates.load();
     return MASP_HOST_OK;
 }
+// ---- the sender's side: out_ciphertext and recovery with an ovk (note_encryption.h) --------------------------------
+void masp_host_prf_ock(const uint8_t ovk[32], const uint8_t cv[32], const uint8_t cmu[32], const uint8_t epk[32], uint8_t ock_out[32]) {
+    prf_ock(ock_out, ovk, cv, cmu, epk);
+}
+void masp_host_sapling_encrypt_outgoing(const uint8_t ock[32], const uint8_t pk_d[32], const uint8_t esk[32], uint8_t c_out[80]) {
+    encrypt_outgoing(c_out, ock, pk_d, esk);
+}
+int masp_host_sapling_try_output_recovery_with_ock(const uint8_t ock[32], const uint8_t epk[32], const uint8_t cmu[32], const uint8_t enc[612],
+                                                   const uint8_t c_out[80], int lead_byte, uint8_t plaintext_out[596], uint8_t pk_d_out[32]) {
+    return try_output_recovery_with_ock(ock, epk, cmu, enc, c_out, lead_byte, plaintext_out, pk_d_out) ? MASP_HOST_OK : MASP_HOST_E_NO_NOTE;
+}
+int masp_host_sapling_try_output_recovery(const uint8_t ovk[32], const uint8_t cv[32], const uint8_t epk[32], const uint8_t cmu[32],
+                                          const uint8_t enc[612], const uint8_t c_out[80], int lead_byte, uint8_t plaintext_out[596],
+                                          uint8_t pk_d_out[32]) {
+    return try_output_recovery(ovk, cv, epk, cmu, enc, c_out, lead_byte, plaintext_out, pk_d_out) ? MASP_HOST_OK : MASP_HOST_E_NO_NOTE;
+}
+// try_sapling_output_recovery over outputs x ovks on `threads` host threads: per output the first ovk of the list that recovers it
+int masp_host_sapling_try_output_recovery_batch(size_t n_ovk, const uint8_t* ovks, size_t n_out, const uint8_t* cvs, const uint8_t* epks,
+                                                const uint8_t* cmus, const uint8_t* encs, const uint8_t* c_outs, int lead_byte, int threads,
+                                                int32_t* hit_ovk, uint8_t* plaintexts, uint8_t* pk_ds) {
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (;;) {
+            const size_t o = next.fetch_add(1);
+            if (o >= n_out) return;
+            hit_ovk[o] = -1;
+            for (size_t k = 0; k < n_ovk; ++k)
+                if (try_output_recovery(ovks + 32 * k, cvs + 32 * o, epks + 32 * o, cmus + 32 * o, encs + ENC_CIPHERTEXT_SIZE * o,
+                                        c_outs + OUT_CIPHERTEXT_SIZE * o, lead_byte, plaintexts + NOTE_PLAINTEXT_SIZE * o, pk_ds + 32 * o)) {
+                    hit_ovk[o] = (int32_t)k;
+                    break;
+                }
+        }
+    };
+    (void)generators();          // the lazily built tables, before the threads race for them
+    (void)pedersen_windows();
+    const int nt = std::max(1, std::min<int>(threads, 256));
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nt; ++t) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+    return MASP_HOST_OK;
+}
 }  // extern "C"

@@ -171,6 +171,13 @@ struct JPoint {
     }
     JPoint mul_by_cofactor() const { return dbl().dbl().dbl(); }
     bool is_identity() const { return U.is_zero() && V == Z; }
+    // in the prime-order subgroup: [r_J] P is the identity (jubjub's is_torsion_free; the identity itself is)
+    bool is_torsion_free() const {
+        static const uint64_t rj[4] = {0xd0970e5ed6f72cb7ull, 0xa6682093ccc81082ull, 0x06673b0101343b00ull, 0x0e7db4ea6533afa9ull};
+        uint8_t s[32];
+        for (int i = 0; i < 32; ++i) s[i] = (uint8_t)(rj[i / 8] >> (8 * (i % 8)));
+        return mul(s).is_identity();
+    }
     JAffine to_affine() const {
         Fr zi;
         Z.invert(zi);

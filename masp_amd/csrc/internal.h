@@ -387,6 +387,15 @@ struct masp_hip_ctx {
     DevBuf<uint8_t> nsc_ivks;         // the ivks as they come: stage 2's per-lane scalars
     DevBuf<uint8_t> nsc_table;        // the Pedersen Niels table and G_ncr behind it, uploaded at the first compact scan
     double nsc_last_ms[3] = {0, 0, 0};   // masp_hip_note_scan_compact_last_timing: upload, stage 1, stage 2 (under slot_mu)
+    // the output recovery scan (k_out_recovery.hip: masp_hip_sapling_output_recovery_scan) runs under ns_mu too, on the same two streams;
+    // per set the rows as they come (cv, cmu, epk 32 bytes each, out_ciphertext 80), their eleven 16-byte columns, and the hits
+    struct OutRecoverySet {
+        DevBuf<uint8_t> cv, cmu, epk, cout, cols, hit_ocks;
+        DevBuf<uint32_t> count, hit_idx;
+    };
+    OutRecoverySet orc[2];
+    DevBuf<uint32_t> orc_ovks;           // the ovks, eight words each: the kernel's wave-uniform message words
+    double orc_last_ms[2] = {0, 0};      // masp_hip_out_recovery_last_timing: upload, kernels (under slot_mu)
 };
 
 namespace masp {

@@ -133,6 +133,9 @@ def load_library():
     if hasattr(L, "masp_hip_sapling_compact_trial_decrypt"):
         L.masp_hip_sapling_compact_trial_decrypt.argtypes = [vp, sz, vp, sz, vp, vp, vp, C.c_int, vp, sz, vp, vp, vp, vp, C.POINTER(sz), C.POINTER(sz)]
         L.masp_hip_note_scan_compact_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
+    if hasattr(L, "masp_hip_sapling_output_recovery_scan"):
+        L.masp_hip_sapling_output_recovery_scan.argtypes = [vp, sz, vp, sz, vp, vp, vp, vp, sz, vp, vp, vp, C.POINTER(sz)]
+        L.masp_hip_out_recovery_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
     L.masp_hip_batch_upload.argtypes = [vp, sz, vp]
     L.masp_hip_batch_prove_resident.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.masp_hip_batch_prove_resident_steps.argtypes = [vp, C.c_int, sz, vp, vp, C.POINTER(C.c_float)]
@@ -442,6 +445,37 @@ class Context:
         ms = (C.c_double * 3)()
         self._check(self._L.masp_hip_note_scan_compact_last_timing(self._h, ms))
         return ms[0], ms[1], ms[2]
+
+    # ---- batch output recovery with outgoing viewing keys on the GPU ----
+    def sapling_output_recovery_scan(self, ovks, cvs, epks, cmus, c_outs, hit_capacity=None):
+        """The device half of try_sapling_output_recovery over outputs x ovks (masp_hip_sapling_output_recovery_scan): ovks n_ovk x 32, cvs,
+        epks and cmus n_out x 32, c_outs n_out x 80 (bytes or uint8 arrays) -> (hit_output uint32[h], hit_ovk uint32[h], hit_ocks uint8[h, 32]):
+        the pairs whose out_ciphertext tag verifies, sorted by (output, ovk), each with its ock.  hit_capacity: room for that many hits
+        (default: grown to what the call asks for)."""
+        ovks, cvs, epks, cmus, couts = _u8(ovks, 32), _u8(cvs, 32), _u8(epks, 32), _u8(cmus, 32), _u8(c_outs, 80)
+        n_ovk, n_out = ovks.shape[0], epks.shape[0]
+        assert cvs.shape[0] == n_out and cmus.shape[0] == n_out and couts.shape[0] == n_out
+        cap = max(16, n_out // 64) if hit_capacity is None else int(hit_capacity)
+        while True:
+            ho, hi, hk = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros((cap, 32), np.uint8)
+            nh = C.c_size_t(0)
+            rc = self._L.masp_hip_sapling_output_recovery_scan(self._h, n_ovk, _p(ovks), n_out, _p(cvs), _p(epks), _p(cmus), _p(couts), cap,
+                                                               _p(ho), _p(hi), _p(hk), C.byref(nh))
+            if rc == E_CAPACITY and hit_capacity is None:
+                cap = nh.value
+                continue
+            if rc == E_CAPACITY:
+                e = MaspHipError(rc, "%d hits" % nh.value)
+                e.needed = nh.value
+                raise e
+            self._check(rc)
+            return ho[:nh.value], hi[:nh.value], hk[:nh.value]
+
+    def out_recovery_last_timing(self):
+        """(upload ms, kernel ms) of the last output recovery scan, HIP events summed over its chunks"""
+        ms = (C.c_double * 2)()
+        self._check(self._L.masp_hip_out_recovery_last_timing(self._h, ms))
+        return ms[0], ms[1]
 
     # ---- building blocks ----
     def msm_g1(self, bases, scalars):

@@ -20,6 +20,7 @@ ERRORS = {1: "invalid encoding", 2: "invalid diversifier", 3: "synthesis error",
 E_NO_NOTE = 5
 NOTE_PLAINTEXT_SIZE, ENC_CIPHERTEXT_SIZE = 596, 612
 COMPACT_NOTE_SIZE = 84     # the note plaintext without its memo: what a compact (ZIP 307) output carries of enc_ciphertext
+OUT_PLAINTEXT_SIZE, OUT_CIPHERTEXT_SIZE = 64, 80     # op = pk_d | esk; out_ciphertext = op under the AEAD and the 16-byte tag
 
 
 class HostError(RuntimeError):
@@ -88,6 +89,13 @@ def load_library():
         L.masp_host_sapling_try_compact_note_decryption.argtypes = [cp, cp, cp, cp, C.c_int, cp, cp]
         L.masp_host_sapling_try_compact_note_decryption_batch.argtypes = [C.c_size_t, vp, C.c_size_t, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp,
                                                                          C.POINTER(C.c_uint64)]
+        L.masp_host_prf_ock.argtypes = [cp, cp, cp, cp, cp]
+        L.masp_host_prf_ock.restype = None
+        L.masp_host_sapling_encrypt_outgoing.argtypes = [cp, cp, cp, cp]
+        L.masp_host_sapling_encrypt_outgoing.restype = None
+        L.masp_host_sapling_try_output_recovery_with_ock.argtypes = [cp, cp, cp, cp, cp, C.c_int, cp, cp]
+        L.masp_host_sapling_try_output_recovery.argtypes = [cp, cp, cp, cp, cp, cp, C.c_int, cp, cp]
+        L.masp_host_sapling_try_output_recovery_batch.argtypes = [C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -613,3 +621,58 @@ def sapling_try_compact_note_decryption_batch(ivks, epks, cmus, enc_compacts, le
                                                                                threads or effective_cpus(), vp(hit), vp(pts), vp(pks),
                                                                                C.byref(cand)))
     return hit, pts, pks, cand.value
+
+
+# ---- the sender's side: out_ciphertext and recovery with an outgoing viewing key ----
+def prf_ock(ovk, cv, cmu, epk):
+    """PRF^ock: BLAKE2b-256 personalised "MASP__Derive_ock" over ovk | cv | cmu | epk -> the 32-byte outgoing cipher key"""
+    out = C.create_string_buffer(32)
+    load_library().masp_host_prf_ock(_b(ovk), _b(cv), _b(cmu), _b(epk), out)
+    return out.raw
+
+
+def sapling_encrypt_outgoing(ock, pk_d, esk):
+    """-> out_ciphertext[80] = AEAD(ock, pk_d | esk)"""
+    out = C.create_string_buffer(OUT_CIPHERTEXT_SIZE)
+    load_library().masp_host_sapling_encrypt_outgoing(_b(ock), _b(pk_d), _b(esk), out)
+    return out.raw
+
+
+def sapling_try_output_recovery_with_ock(ock, epk, cmu, enc_ciphertext, out_ciphertext, lead_byte=2):
+    """try_sapling_output_recovery_with_ock -> (plaintext[596], pk_d[32]) or None"""
+    pt, pk = C.create_string_buffer(NOTE_PLAINTEXT_SIZE), C.create_string_buffer(32)
+    rc = load_library().masp_host_sapling_try_output_recovery_with_ock(_b(ock), _b(epk), _b(cmu), _b(enc_ciphertext, ENC_CIPHERTEXT_SIZE),
+                                                                       _b(out_ciphertext, OUT_CIPHERTEXT_SIZE), lead_byte, pt, pk)
+    if rc == E_NO_NOTE:
+        return None
+    _check(rc)
+    return pt.raw, pk.raw
+
+
+def sapling_try_output_recovery(ovk, cv, epk, cmu, enc_ciphertext, out_ciphertext, lead_byte=2):
+    """try_sapling_output_recovery -> (plaintext[596], pk_d[32]) or None"""
+    pt, pk = C.create_string_buffer(NOTE_PLAINTEXT_SIZE), C.create_string_buffer(32)
+    rc = load_library().masp_host_sapling_try_output_recovery(_b(ovk), _b(cv), _b(epk), _b(cmu), _b(enc_ciphertext, ENC_CIPHERTEXT_SIZE),
+                                                              _b(out_ciphertext, OUT_CIPHERTEXT_SIZE), lead_byte, pt, pk)
+    if rc == E_NO_NOTE:
+        return None
+    _check(rc)
+    return pt.raw, pk.raw
+
+
+def sapling_try_output_recovery_batch(ovks, cvs, epks, cmus, enc_ciphertexts, out_ciphertexts, lead_byte=2, threads=None):
+    """try_sapling_output_recovery over outputs x ovks on host threads: (hit_ovk int32[n_out] (-1: none), plaintexts uint8[n_out, 596],
+    pk_ds uint8[n_out, 32])"""
+    def arr(x, w):
+        a = np.frombuffer(b"".join(bytes(i) for i in x), dtype=np.uint8) if isinstance(x, (list, tuple)) else np.ascontiguousarray(x, dtype=np.uint8)
+        return a.reshape(-1, w)
+    ovks, cvs, epks, cmus = arr(ovks, 32), arr(cvs, 32), arr(epks, 32), arr(cmus, 32)
+    encs, couts = arr(enc_ciphertexts, ENC_CIPHERTEXT_SIZE), arr(out_ciphertexts, OUT_CIPHERTEXT_SIZE)
+    n = epks.shape[0]
+    assert cvs.shape[0] == n and cmus.shape[0] == n and encs.shape[0] == n and couts.shape[0] == n
+    hit = np.full(n, -1, np.int32)
+    pts, pks = np.zeros((n, NOTE_PLAINTEXT_SIZE), np.uint8), np.zeros((n, 32), np.uint8)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(load_library().masp_host_sapling_try_output_recovery_batch(ovks.shape[0], vp(ovks), n, vp(cvs), vp(epks), vp(cmus), vp(encs), vp(couts),
+                                                                       lead_byte, threads or effective_cpus(), vp(hit), vp(pts), vp(pks)))
+    return hit, pts, pks

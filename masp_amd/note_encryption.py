@@ -9,7 +9,12 @@ The compact (ZIP 307) form, what a light wallet runs: a `CompactShieldedOutput` 
 without its memo) and no tag.  `try_sapling_compact_note_decryption` runs on the host; `batch.try_compact_note_decryption` runs the WHOLE
 check on the GPU (masp_hip_sapling_compact_trial_decrypt: the lead byte for every pair, then parsing, group hashes, pk_d, the Pedersen
 note commitment and the esk check for the pairs that pass it), so its hits are final and the host finishes nothing.
-Outgoing ciphertexts and recovery with an ovk are not mirrored."""
+
+The sender's side: `encrypt_outgoing_plaintext` makes an output's out_ciphertext (pk_d | esk under the ock = PRF^ock(ovk, cv, cmu, epk)),
+`try_sapling_output_recovery` and `try_sapling_output_recovery_with_ock` read an `OutputDescription` back on the host, and
+`batch.try_output_recovery` scans outputs x ovks on the GPU (masp_hip_sapling_output_recovery_scan: PRF^ock and out_ciphertext's tag for
+every pair) and finishes the pairs whose tag verifies on the host (masp_host_sapling_try_output_recovery_with_ock: everything else)."""
+import os
 from collections import namedtuple
 
 import numpy as np
@@ -26,6 +31,8 @@ Note = namedtuple("Note", "asset_identifier value pk_d rseed")                # 
 ShieldedOutput = namedtuple("ShieldedOutput", "epk cmu enc_ciphertext")       # ephemeral_key, cmstar_bytes, enc_ciphertext
 CompactShieldedOutput = namedtuple("CompactShieldedOutput", "epk cmu enc_ciphertext")   # CompactOutputDescription: enc_ciphertext[84]
 COMPACT_NOTE_SIZE = H.COMPACT_NOTE_SIZE
+OutputDescription = namedtuple("OutputDescription", "cv cmu epk enc_ciphertext out_ciphertext")   # (without the proof)
+OUT_PLAINTEXT_SIZE, OUT_CIPHERTEXT_SIZE = H.OUT_PLAINTEXT_SIZE, H.OUT_CIPHERTEXT_SIZE
 EMPTY_MEMO = b"\xf6" + bytes(MEMO_SIZE - 1)
 
 
@@ -89,6 +96,33 @@ def try_sapling_compact_note_decryption(ivk, output, lead_byte=2):
     return None if r is None else _parse_compact(*r)
 
 
+def prf_ock(ovk, cv, cmu, epk):
+    """PRF^ock -> the 32-byte outgoing cipher key"""
+    return H.prf_ock(ovk, cv, cmu, epk)
+
+
+def encrypt_outgoing_plaintext(ovk, cv, cmu, epk, pk_d, esk, rng_bytes=None):
+    """NoteEncryption::encrypt_outgoing_plaintext -> out_ciphertext[80].  ovk None is the ovk = ⊥ case: a random ock and a random op, which
+    nobody recovers; rng_bytes: the 96 bytes (ock | op) to use for it instead of os.urandom."""
+    if ovk is not None:
+        return H.sapling_encrypt_outgoing(H.prf_ock(ovk, cv, cmu, epk), pk_d, esk)
+    r = os.urandom(32 + OUT_PLAINTEXT_SIZE) if rng_bytes is None else bytes(rng_bytes)
+    assert len(r) == 32 + OUT_PLAINTEXT_SIZE
+    return H.sapling_encrypt_outgoing(r[:32], r[32:64], r[64:])
+
+
+def try_sapling_output_recovery(ovk, output, lead_byte=2):
+    """-> (Note, PaymentAddress, memo) or None, on the host.  ovk: 32 bytes; output: an OutputDescription."""
+    r = H.sapling_try_output_recovery(ovk, output.cv, output.epk, output.cmu, output.enc_ciphertext, output.out_ciphertext, lead_byte)
+    return None if r is None else _parse(*r)
+
+
+def try_sapling_output_recovery_with_ock(ock, output, lead_byte=2):
+    """-> (Note, PaymentAddress, memo) or None, on the host.  ock: the 32-byte outgoing cipher key."""
+    r = H.sapling_try_output_recovery_with_ock(ock, output.epk, output.cmu, output.enc_ciphertext, output.out_ciphertext, lead_byte)
+    return None if r is None else _parse(*r)
+
+
 class batch:
     """masp_note_encryption::batch"""
 
@@ -127,4 +161,25 @@ class batch:
         for o, k, pt, pk in zip(hit_output.tolist(), hit_ivk.tolist(), hit_pt, hit_pk):   # sorted by (output, ivk): the first success wins
             if result[o] is None:
                 result[o] = (_parse_compact(pt.tobytes(), pk.tobytes()), k)
+        return result
+
+    @staticmethod
+    def try_output_recovery(ovks, outputs, ctx, lead_byte=2):
+        """One entry per OutputDescription, in order: None or ((Note, PaymentAddress, memo), index of the first ovk of the list for which the
+        whole check succeeds).  ctx: a masp_amd.Context; the scan runs on its GPU."""
+        outputs = list(outputs)
+        ovks = [H._b(k) for k in ovks]
+        result = [None] * len(outputs)
+        if not ovks or not outputs:
+            return result
+        cvs, epks, cmus, couts = (np.frombuffer(b"".join(bytes(getattr(o, f)) for o in outputs), dtype=np.uint8)
+                                  for f in ("cv", "epk", "cmu", "out_ciphertext"))
+        hit_output, hit_ovk, hit_ocks = ctx.sapling_output_recovery_scan(b"".join(ovks), cvs, epks, cmus, couts)
+        for o, k, ock in zip(hit_output.tolist(), hit_ovk.tolist(), hit_ocks):   # sorted by (output, ovk): the first success wins
+            if result[o] is not None:
+                continue
+            out = outputs[o]
+            r = H.sapling_try_output_recovery_with_ock(ock.tobytes(), out.epk, out.cmu, out.enc_ciphertext, out.out_ciphertext, lead_byte)
+            if r is not None:
+                result[o] = (_parse(*r), k)
         return result
