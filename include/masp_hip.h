@@ -355,6 +355,31 @@ int masp_hip_sapling_output_recovery_scan(masp_hip_ctx* ctx, size_t n_ovk, const
                                           uint32_t* hit_output, uint32_t* hit_ovk, uint8_t* hit_ocks, size_t* n_hits);
 int masp_hip_out_recovery_last_timing(masp_hip_ctx* ctx, double ms[2]);
 
+/* ---- Frozen commitment trees on the GPU: batched Merkle hashing ----
+ * masp_hip_merkle_tree_complete <- FrozenCommitmentTree::complete, root and path (masp_primitives/src/merkle_tree.rs:177-251) over a row
+ * of n nodes at level height0 (0: the leaves, what FrozenCommitmentTree::new passes; above 0: what merge passes once the rows of its full
+ * subtrees are stitched).  row: n x 32, canonical encodings below the BLS12-381 scalar modulus (Node::read accepts nothing else);
+ * 0 <= height0 <= 32, n <= min(2^22, 2^(32 - height0)), n_paths <= 2^22.
+ * The node vector is exactly the one complete appends to, from the given row on: every row padded to an even width with
+ * empty_root(level), the width-1 rows near the top included, the next row directly behind it, the last row the single node of level 32;
+ * *n_nodes (may be NULL) is its length in nodes.  n = 0: the vector is empty, the root is empty_root(32), no GPU work.
+ * nodes_out (nodes_capacity x 32 bytes) may be NULL: a caller that wants its witnesses does not download 64 bytes per leaf.  If it is given
+ * and nodes_capacity < *n_nodes the call returns MASP_HIP_E_CAPACITY with *n_nodes set and writes nothing else.
+ * root32: the node of level 32.  positions: n_paths indices into the given row, each below n (MASP_HIP_E_INVALID_ARG otherwise);
+ * paths_out: n_paths x (32 - height0) x 32 bytes, position by position the siblings from level height0 up, gathered on the device.  Whether
+ * sibling i is a left node is bit i of the position and is not returned.
+ * A node of the row that is not canonical: MASP_HIP_E_INVALID_ARG with *bad_index (may be NULL) the smallest such index, else -1; no output
+ * buffer is written and the context stays usable.
+ * The result is deterministic.  Re-entrant next to proving and verification calls; on the context's first verifier stream, under the lock
+ * of the note scans (a context runs one scan or one tree at a time: they share the Pedersen table); on a multi-device context on the first
+ * device.  masp_host_merkle_tree_complete (include/masp_host.h) is the same on the host.
+ * masp_hip_merkle_last_timing - of the last tree of this context, from HIP events on its stream: ms[0] the host-to-device copies, ms[1] the
+ * kernels, ms[2] the device-to-host copies. */
+int masp_hip_merkle_tree_complete(masp_hip_ctx* ctx, unsigned height0, size_t n, const uint8_t* row, uint8_t* nodes_out, size_t nodes_capacity,
+                                  size_t* n_nodes, uint8_t root32[32], size_t n_paths, const uint64_t* positions, uint8_t* paths_out,
+                                  int64_t* bad_index);
+int masp_hip_merkle_last_timing(masp_hip_ctx* ctx, double ms[3]);
+
 /* ---- measurement hooks (bench.py): device-resident workloads, HIP-event timing on the ctx stream ---- */
 /* Keeps `n` jobs' assignments resident in HBM; returns a handle (>= 0) or a negative error code. */
 int masp_hip_batch_upload(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs);

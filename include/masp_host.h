@@ -28,6 +28,7 @@ extern "C" {
 #define MASP_HOST_E_SYNTHESIS 3     /* bellperson's SynthesisError */
 #define MASP_HOST_E_UNSATISFIED 4   /* check & 1: a constraint does not hold */
 #define MASP_HOST_E_NO_NOTE 5       /* trial decryption: the output is not a note of this key (the reference's None) */
+#define MASP_HOST_E_CAPACITY 6      /* an output buffer of the caller is too small: the call says how much it needs */
 
 /* `kind` everywhere: 0 Spend, 1 Output, 2 Convert (= MASP_HIP_SPEND / _OUTPUT / _CONVERT) */
 
@@ -110,6 +111,15 @@ int masp_host_value_commitment(const uint8_t id[32], uint64_t value, const uint8
 int masp_host_note_cmu(const uint8_t id[32], uint64_t value, const uint8_t diversifier[11], const uint8_t pk_d[32], const uint8_t rcm[32],
                        uint8_t cmu32[32]);
 int masp_host_merkle_hash(unsigned depth, const uint8_t lhs[32], const uint8_t rhs[32], uint8_t out32[32]);
+/* empty_root(0..32) of the commitment tree, 33 x 32 bytes: the uncommitted leaf 1 and the roots of the empty subtrees above it */
+void masp_host_merkle_empty_roots(uint8_t out[33 * 32]);
+/* FrozenCommitmentTree (masp_primitives/src/merkle_tree.rs:105-256) on the host, the arguments and results of masp_hip_merkle_tree_complete
+ * (include/masp_hip.h) without the context and with the number of host threads a row's parents are dealt to.  MASP_HOST_E_INVALID: an
+ * argument out of range, a position >= n, or a node that is not canonical (*bad_index = the first such, else -1);
+ * MASP_HOST_E_CAPACITY: nodes_out given with nodes_capacity < *n_nodes.  Either way no output but *n_nodes / *bad_index is written. */
+int masp_host_merkle_tree_complete(unsigned height0, size_t n, const uint8_t* row, uint8_t* nodes_out, size_t nodes_capacity, size_t* n_nodes,
+                                   uint8_t root32[32], size_t n_paths, const uint64_t* positions, uint8_t* paths_out, int64_t* bad_index,
+                                   int threads);
 int masp_host_jubjub_mul(const uint8_t p32[32], const uint8_t k32[32], uint8_t out32[32]);
 int masp_host_point_uv(const uint8_t p32[32], uint8_t out64[64]);
 int masp_host_jubjub_add(const uint8_t p32[32], const uint8_t q32[32], int subtract, uint8_t out32[32]);

@@ -650,6 +650,91 @@ int masp_host_merkle_hash(unsigned depth, const uint8_t lhs[32], const uint8_t r
     merkle_hash(depth, l, r).to_bytes(out32);
     return 0;
 }
+void masp_host_merkle_empty_roots(uint8_t out[33 * 32]) {
+    const auto& e = merkle_empty_roots();
+    for (int h = 0; h <= 32; ++h) memcpy(out + 32 * h, e[h].data(), 32);
+}
+// FrozenCommitmentTree::complete (masp_primitives/src/merkle_tree.rs:177-205) over a row of n nodes at height0, root() and path() (:207-251),
+// a row's parents dealt to `threads` host threads; what masp_hip_merkle_tree_complete computes, and its other side in the tests
+int masp_host_merkle_tree_complete(unsigned height0, size_t n, const uint8_t* row, uint8_t* nodes_out, size_t nodes_capacity, size_t* n_nodes,
+                                   uint8_t root32[32], size_t n_paths, const uint64_t* positions, uint8_t* paths_out, int64_t* bad_index,
+                                   int threads) {
+    if (bad_index) *bad_index = -1;
+    if (height0 > 32 || !root32 || (n && !row) || n > ((size_t)1 << 22) || n > ((uint64_t)1 << (32 - height0)) || (n_paths && !positions) ||
+        (n_paths && height0 < 32 && !paths_out))
+        return MASP_HOST_E_INVALID;
+    for (size_t p = 0; p < n_paths; ++p)
+        if (positions[p] >= n) return MASP_HOST_E_INVALID;
+    const unsigned depth = 32 - height0;
+    size_t total = 0;
+    if (n) {
+        size_t width = n;
+        for (unsigned i = 0; i < depth; ++i) {
+            width += width & 1;
+            total += width;
+            width /= 2;
+        }
+        total += width;   // the node of level 32
+    }
+    if (n_nodes) *n_nodes = total;
+    if (nodes_out && nodes_capacity < total) return MASP_HOST_E_CAPACITY;
+    for (size_t i = 0; i < n; ++i) {
+        Fr x;
+        if (!Fr::from_bytes(x, row + 32 * i)) {
+            if (bad_index) *bad_index = (int64_t)i;
+            return MASP_HOST_E_INVALID;
+        }
+    }
+    const auto& empty = merkle_empty_roots();
+    if (n == 0) {
+        memcpy(root32, empty[32].data(), 32);
+        return MASP_HOST_OK;
+    }
+    (void)pedersen_windows();   // the lazily built table, before the threads race for it
+    std::vector<uint8_t> own;
+    uint8_t* t = nodes_out;
+    if (!t) {
+        own.resize(32 * total);
+        t = own.data();
+    }
+    memcpy(t, row, 32 * n);
+    const int nt = std::max(1, std::min<int>(threads, 256));
+    size_t start = 0, width = n;
+    for (unsigned i = 0; i < depth; ++i) {
+        const unsigned level = height0 + i;
+        if (width & 1) memcpy(t + 32 * (start + width++), empty[level].data(), 32);
+        const size_t parents = width / 2;
+        const uint8_t* src = t + 32 * start;
+        uint8_t* dst = t + 32 * (start + width);
+        std::atomic<size_t> next{0};
+        auto work = [&] {
+            for (;;) {
+                const size_t j0 = next.fetch_add(16);
+                if (j0 >= parents) return;
+                for (size_t j = j0; j < std::min(parents, j0 + 16); ++j) merkle_hash_bytes(level, src + 64 * j, src + 64 * j + 32).to_bytes(dst + 32 * j);
+            }
+        };
+        std::vector<std::thread> pool;
+        if (parents >= 64)   // (a narrow row is not worth the threads' start)
+            for (int k = 1; k < nt; ++k) pool.emplace_back(work);
+        work();
+        for (auto& th : pool) th.join();
+        start += width;
+        width = parents;
+    }
+    memcpy(root32, t + 32 * (total - 1), 32);
+    for (size_t p = 0; p < n_paths; ++p) {
+        size_t pos = positions[p], s = 0, w = n;
+        for (unsigned i = 0; i < depth; ++i) {
+            w += w & 1;
+            memcpy(paths_out + 32 * (p * depth + i), t + 32 * (s + (pos ^ 1)), 32);   // (the sibling of a last, even node is the row's padding)
+            s += w;
+            w /= 2;
+            pos /= 2;
+        }
+    }
+    return MASP_HOST_OK;
+}
 // [k]P for P given as 32 bytes; (point decode / scalar multiplication / encode round trip)
 int masp_host_jubjub_mul(const uint8_t p32[32], const uint8_t k32[32], uint8_t out32[32]) {
     JPoint p;

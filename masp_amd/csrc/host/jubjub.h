@@ -393,5 +393,33 @@ inline Fr merkle_hash(unsigned depth, const Fr& lhs, const Fr& rhs) {
     for (int i = 0; i < 255; ++i) bits.push_back((r[i / 8] >> (i % 8)) & 1);
     return pedersen_hash({false, depth}, bits).to_affine().u;
 }
+// the same from the nodes' 32 bytes with the message in words instead of a bit vector, for the rows of a commitment tree: 6 + 255 + 255 bits
+// are 172 whole chunks over segments 0, 1 and 2
+inline Fr merkle_hash_bytes(unsigned depth, const uint8_t* lhs, const uint8_t* rhs) {
+    uint64_t m[9] = {depth & 63u, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (unsigned i = 0; i < 255; ++i) {
+        m[(6 + i) >> 6] |= (uint64_t)((lhs[i / 8] >> (i % 8)) & 1) << ((6 + i) & 63);
+        m[(261 + i) >> 6] |= (uint64_t)((rhs[i / 8] >> (i % 8)) & 1) << ((261 + i) & 63);
+    }
+    auto bit = [&](unsigned i) { return (unsigned)(m[i >> 6] >> (i & 63)) & 1u; };
+    const PedersenWindows& T = pedersen_windows();
+    JPoint p = JPoint::identity();
+    for (unsigned c = 0; c < 172; ++c) p = p.add_niels(T.e[c / 63][c % 63][bit(3 * c) + 2 * bit(3 * c + 1)], bit(3 * c + 2) != 0);
+    return p.to_affine().u;
+}
+// empty_root(0..32): the uncommitted leaf 1 (Node::blank) and above it the root of an empty subtree of each height
+inline const std::array<std::array<uint8_t, 32>, 33>& merkle_empty_roots() {
+    static const std::array<std::array<uint8_t, 32>, 33> t = [] {
+        std::array<std::array<uint8_t, 32>, 33> e;
+        Fr cur = Fr::one();
+        cur.to_bytes(e[0].data());
+        for (unsigned h = 0; h < 32; ++h) {
+            cur = merkle_hash(h, cur, cur);
+            cur.to_bytes(e[h + 1].data());
+        }
+        return e;
+    }();
+    return t;
+}
 
 }  // namespace masp_host

@@ -385,7 +385,7 @@ struct masp_hip_ctx {
     };
     NoteScanCompactSet nsc[2];
     DevBuf<uint8_t> nsc_ivks;         // the ivks as they come: stage 2's per-lane scalars
-    DevBuf<uint8_t> nsc_table;        // the Pedersen Niels table and G_ncr behind it, uploaded at the first compact scan
+    DevBuf<uint8_t> nsc_table;        // the Pedersen Niels table and G_ncr behind it, uploaded at the first compact scan or tree (pedersen_table.h)
     double nsc_last_ms[3] = {0, 0, 0};   // masp_hip_note_scan_compact_last_timing: upload, stage 1, stage 2 (under slot_mu)
     // the output recovery scan (k_out_recovery.hip: masp_hip_sapling_output_recovery_scan) runs under ns_mu too, on the same two streams;
     // per set the rows as they come (cv, cmu, epk 32 bytes each, out_ciphertext 80), their eleven 16-byte columns, and the hits
@@ -396,6 +396,11 @@ struct masp_hip_ctx {
     OutRecoverySet orc[2];
     DevBuf<uint32_t> orc_ovks;           // the ovks, eight words each: the kernel's wave-uniform message words
     double orc_last_ms[2] = {0, 0};      // masp_hip_out_recovery_last_timing: upload, kernels (under slot_mu)
+    // the commitment tree (k_merkle.hip: masp_hip_merkle_tree_complete) runs under ns_mu too, on the first verifier stream, and reads nsc_table:
+    // the node vector (eight words a node), the first bad input's index, the positions and their paths, empty_root(0..32)
+    DevBuf<uint32_t> mt_nodes, mt_bad, mt_paths, mt_empties;
+    DevBuf<uint64_t> mt_pos;
+    double mt_last_ms[3] = {0, 0, 0};    // masp_hip_merkle_last_timing: upload, kernels, download (under slot_mu)
 };
 
 namespace masp {

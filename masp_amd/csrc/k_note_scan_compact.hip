@@ -24,6 +24,7 @@
 #include "device/note_scan.hpp"
 #include "host/jubjub.h"
 #include "internal.h"
+#include "pedersen_table.h"
 
 using namespace masp;
 
@@ -125,38 +126,6 @@ __global__ __launch_bounds__(NSC_BLOCK2) void k_nsc_emit(const NscArgs a, int fr
     uint32_t* d = data + 29 * (size_t)i;
     for (int j = 0; j < 21; ++j) d[j] = st.pt[j];
     for (int j = 0; j < 8; ++j) d[21 + j] = st.msg[18 + j];
-}
-
-Fr fr_of_host(const masp_host::Fr& x) {
-    uint64_t c[4];
-    x.to_canonical(c);
-    Fr r;
-    for (int i = 0; i < 4; ++i) {
-        r.v[2 * i] = (uint32_t)c[i];
-        r.v[2 * i + 1] = (uint32_t)(c[i] >> 32);
-    }
-    return fe_to_mont(r);
-}
-
-// the Pedersen Niels table of the NoteCommitment hash, [segment][window][k], and G_ncr behind it, in the device's limbs
-const std::vector<uint8_t>& nsc_table_bytes() {
-    static const std::vector<uint8_t> t = [] {
-        std::vector<uint8_t> b(sizeof(JNiels) * PED_NC_TABLE + sizeof(JExt));
-        const masp_host::PedersenWindows& W = masp_host::pedersen_windows();
-        JNiels* n = (JNiels*)b.data();
-        for (uint32_t s = 0; s < PED_NC_SEGMENTS; ++s)
-            for (uint32_t w = 0; w < PED_WINDOWS; ++w)
-                for (uint32_t k = 0; k < 4; ++k) {
-                    const masp_host::JPoint::Niels& e = W.e[s][w][k];
-                    n[(s * PED_WINDOWS + w) * 4 + k] = {fr_of_host(e.vmu), fr_of_host(e.vpu), fr_of_host(e.t2d)};
-                }
-        const masp_host::JAffine g = masp_host::generators().note_commitment_randomness.to_affine();
-        const Fr u = fr_of_host(g.u), v = fr_of_host(g.v);
-        const JExt ge = {u, v, fe_one<FrCfg>(), fe_mul(u, v)};
-        memcpy(b.data() + sizeof(JNiels) * PED_NC_TABLE, &ge, sizeof(JExt));
-        return b;
-    }();
-    return t;
 }
 
 struct Hit {
@@ -278,7 +247,7 @@ int masp_hip_sapling_compact_trial_decrypt(masp_hip_ctx* ctx, size_t n_ivk, cons
         if (epk_status && n_out) memset(epk_status, 0, n_out);   // (not looked at: no key asked for them)
         return MASP_HIP_OK;
     }
-    const std::vector<uint8_t>& table = nsc_table_bytes();
+    (void)pedersen_table_bytes();   // built outside the locks
     const ApiLaunchScope api_scope;
     ctx = FIRST_DEVICE(ctx);
     std::shared_lock<std::shared_mutex> lock(ctx->mu);   // concurrent with provers and verifiers
@@ -288,7 +257,7 @@ int masp_hip_sapling_compact_trial_decrypt(masp_hip_ctx* ctx, size_t n_ivk, cons
     if ((rc = ctx->ns_digits.upload(digits.data(), digits.size(), ctx->streams.vk[0])) ||
         (rc = ctx->nsc_ivks.upload(ivks, 32 * n_ivk, ctx->streams.vk[0])))
         return fail(ctx, rc);
-    if (!ctx->nsc_table.p && (rc = ctx->nsc_table.upload(table.data(), table.size(), ctx->streams.vk[0]))) return fail(ctx, rc);
+    if ((rc = pedersen_table_ensure(ctx, ctx->streams.vk[0]))) return fail(ctx, rc);   // (shared with the commitment tree)
     if (hipStreamSynchronize(ctx->streams.vk[0]) != hipSuccess) {   // both streams read the digits, the ivks and the table
         last_hip_error() = std::string("compact note scan: upload failed: ") + hipGetErrorString(hipGetLastError());
         ctx->nsc_table.release();

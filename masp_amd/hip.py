@@ -136,6 +136,9 @@ def load_library():
     if hasattr(L, "masp_hip_sapling_output_recovery_scan"):
         L.masp_hip_sapling_output_recovery_scan.argtypes = [vp, sz, vp, sz, vp, vp, vp, vp, sz, vp, vp, vp, C.POINTER(sz)]
         L.masp_hip_out_recovery_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
+    if hasattr(L, "masp_hip_merkle_tree_complete"):
+        L.masp_hip_merkle_tree_complete.argtypes = [vp, C.c_uint, sz, vp, vp, sz, C.POINTER(sz), vp, sz, vp, vp, C.POINTER(C.c_int64)]
+        L.masp_hip_merkle_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
     L.masp_hip_batch_upload.argtypes = [vp, sz, vp]
     L.masp_hip_batch_prove_resident.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.masp_hip_batch_prove_resident_steps.argtypes = [vp, C.c_int, sz, vp, vp, C.POINTER(C.c_float)]
@@ -476,6 +479,40 @@ class Context:
         ms = (C.c_double * 2)()
         self._check(self._L.masp_hip_out_recovery_last_timing(self._h, ms))
         return ms[0], ms[1]
+
+    # ---- frozen commitment trees on the GPU ----
+    def merkle_tree_complete(self, row, height0=0, positions=(), want_nodes=True, nodes_capacity=None):
+        """FrozenCommitmentTree::complete, root and paths on the GPU (masp_hip_merkle_tree_complete): row n x 32 (bytes or a uint8 array), the
+        nodes of level height0; positions: indices into the row -> (nodes uint8[N, 32] or None with want_nodes=False: no download of the
+        vector, root bytes, paths uint8[len(positions), 32 - height0, 32] siblings lowest level first).  A node that is not canonical raises
+        MaspHipError with .bad_index; nodes_capacity: room for that many nodes (default: what the vector needs), too little raises with
+        .needed."""
+        row = _u8(row, 32)
+        pos = np.ascontiguousarray(positions, dtype=np.uint64).reshape(-1)
+        n, depth = row.shape[0], max(0, 32 - int(height0))
+        paths = np.zeros((pos.shape[0], depth, 32), np.uint8)
+        root = np.zeros(32, np.uint8)
+        nn, bad = C.c_size_t(0), C.c_int64(-1)
+        if want_nodes and nodes_capacity is None:
+            from .host import merkle_node_count
+            nodes_capacity = merkle_node_count(n, int(height0))
+        nodes = np.zeros((int(nodes_capacity), 32), np.uint8) if want_nodes else None
+        rc = self._L.masp_hip_merkle_tree_complete(self._h, int(height0), n, _p(row) if n else None, _p(nodes), int(nodes_capacity or 0),
+                                                   C.byref(nn), _p(root), pos.shape[0], _p(pos) if pos.shape[0] else None, _p(paths),
+                                                   C.byref(bad))
+        if rc:
+            detail = "node %d is not canonical" % bad.value if bad.value >= 0 else \
+                "%d nodes" % nn.value if rc == E_CAPACITY else self._L.masp_hip_last_error(self._h).decode(errors="replace")
+            e = MaspHipError(rc, detail)
+            e.bad_index, e.needed = bad.value, nn.value
+            raise e
+        return (nodes[:nn.value] if want_nodes else None), root.tobytes(), paths
+
+    def merkle_last_timing(self):
+        """(upload ms, kernel ms, download ms) of the last tree of this context, from HIP events on its stream"""
+        ms = (C.c_double * 3)()
+        self._check(self._L.masp_hip_merkle_last_timing(self._h, ms))
+        return ms[0], ms[1], ms[2]
 
     # ---- building blocks ----
     def msm_g1(self, bases, scalars):

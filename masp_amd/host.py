@@ -16,8 +16,9 @@ JUBJUB_ORDER = 65544843968907738099309675635232457297059212658723172813653591623
 FR_MODULUS = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
 TREE_DEPTH = 32
 ERRORS = {1: "invalid encoding", 2: "invalid diversifier", 3: "synthesis error", 4: "assignment does not satisfy the circuit",
-          5: "not a note of this key"}
+          5: "not a note of this key", 6: "an output buffer is too small"}
 E_NO_NOTE = 5
+E_CAPACITY = 6
 NOTE_PLAINTEXT_SIZE, ENC_CIPHERTEXT_SIZE = 596, 612
 COMPACT_NOTE_SIZE = 84     # the note plaintext without its memo: what a compact (ZIP 307) output carries of enc_ciphertext
 OUT_PLAINTEXT_SIZE, OUT_CIPHERTEXT_SIZE = 64, 80     # op = pk_d | esk; out_ciphertext = op under the AEAD and the 16-byte tag
@@ -58,6 +59,10 @@ def load_library():
         L.masp_host_value_commitment.argtypes = [cp, u64, cp, cp, cp]
         L.masp_host_note_cmu.argtypes = [cp, u64, cp, cp, cp, cp]
         L.masp_host_merkle_hash.argtypes = [C.c_uint, cp, cp, cp]
+        L.masp_host_merkle_empty_roots.argtypes = [vp]
+        L.masp_host_merkle_empty_roots.restype = None
+        L.masp_host_merkle_tree_complete.argtypes = [C.c_uint, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, vp, vp,
+                                                     C.POINTER(C.c_int64), C.c_int]
         L.masp_host_jubjub_mul.argtypes = [cp, cp, cp]
         L.masp_host_convert_cmu.argtypes = [cp, cp]
         L.masp_host_vk_prepare.restype = vp
@@ -393,6 +398,51 @@ def merkle_hash(depth, lhs, rhs):
     if load_library().masp_host_merkle_hash(depth, _b(lhs), _b(rhs), out):
         raise ValueError("non-canonical node")
     return out.raw
+
+
+def merkle_empty_roots():
+    """empty_root(0..32) as a (33, 32) uint8 array: the uncommitted leaf 1 and the roots of the empty subtrees above it"""
+    out = np.zeros((33, 32), np.uint8)
+    load_library().masp_host_merkle_empty_roots(out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def merkle_tree_complete(row, height0=0, positions=(), want_nodes=True, threads=None, nodes_capacity=None):
+    """masp_host_merkle_tree_complete: FrozenCommitmentTree::complete over `row` (n x 32 bytes, nodes of level height0) on host threads
+    -> (nodes uint8[N, 32] or None, root bytes, paths uint8[len(positions), 32 - height0, 32]).  A node that is not canonical or a
+    position >= n raises ValueError (with .bad_index); nodes_capacity: room for that many nodes (default: what the call asks for)."""
+    L = load_library()
+    row = np.ascontiguousarray(np.frombuffer(row, np.uint8) if isinstance(row, (bytes, bytearray, memoryview)) else row, dtype=np.uint8).reshape(-1, 32)
+    pos = np.ascontiguousarray(positions, dtype=np.uint64).reshape(-1)
+    n, depth = row.shape[0], max(0, TREE_DEPTH - int(height0))
+    paths = np.zeros((pos.shape[0], depth, 32), np.uint8)
+    root = np.zeros(32, np.uint8)
+    nn, bad = C.c_size_t(0), C.c_int64(-1)
+    threads = effective_cpus() if threads is None else int(threads)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    if want_nodes and nodes_capacity is None:
+        nodes_capacity = merkle_node_count(n, height0)
+    nodes =np.zeros((int(nodes_capacity), 32), np.uint8) if want_nodes else None
+    rc = L.masp_host_merkle_tree_complete(int(height0), n, vp(row), nodes.ctypes.data_as(C.c_void_p) if want_nodes else None,
+                                          int(nodes_capacity or 0), C.byref(nn), root.ctypes.data_as(C.c_void_p), pos.shape[0], vp(pos),
+                                          paths.ctypes.data_as(C.c_void_p), C.byref(bad), threads)
+    if rc:
+        e = ValueError("merkle_tree_complete: %s" % ("node %d is not canonical" % bad.value if bad.value >= 0 else ERRORS.get(rc, rc)))
+        e.code, e.bad_index, e.needed = rc, bad.value, nn.value
+        raise e
+    return (nodes[:nn.value] if want_nodes else None), root.tobytes(), paths
+
+
+def merkle_node_count(n, height0=0):
+    """the length of the node vector FrozenCommitmentTree::complete builds over n nodes of level height0"""
+    if n == 0:
+        return 0
+    total, width = 0, n
+    for _ in range(TREE_DEPTH - height0):
+        width += width & 1
+        total += width
+        width //= 2
+    return total + width
 
 
 def jubjub_mul(point, scalar):

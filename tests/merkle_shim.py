@@ -1,0 +1,49 @@
+"""Build of the test-only shim tests/native/merkle_dev.hip (the commitment tree's device header on the host), with the product's flags as
+device_shim.py reads them from the Makefile; rebuilt when it or a header it includes is newer than the library."""
+import ctypes as C
+import os
+import subprocess
+
+import device_shim
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SRC = os.path.join(HERE, "native", "merkle_dev.hip")
+SO = os.path.join(HERE, "native", "_merkle_dev.so")
+CSRC = os.path.join(os.path.dirname(HERE), "masp_amd", "csrc")
+DEPS = [SRC] + [os.path.join(CSRC, "device", f) for f in ("merkle.hpp", "pedersen.hpp", "blake2b.hpp", "jubjub.hpp", "field.hpp", "consts.hpp")] + \
+    [os.path.join(CSRC, "host", f) for f in ("jubjub.h", "fr.h", "mont.h")]
+_lib = None
+
+
+def load():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in DEPS):
+            flags = device_shim.makefile_flags()
+            tmp = SO + ".%d.tmp" % os.getpid()
+            subprocess.check_call([device_shim.HIPCC] + flags + ["-shared", SRC, "-o", tmp])
+            os.replace(tmp, SO)
+        _lib = C.CDLL(SO)
+        _lib.mkl_row_host.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        _lib.mkl_row_host.restype = None
+    return _lib
+
+
+def combine(items):
+    """items: (level, lhs 32 bytes, rhs 32 bytes) -> list of 32-byte parents from device/merkle.hpp's merkle_combine on the host"""
+    buf = b"".join(int(level).to_bytes(4, "little") + bytes(lhs) + bytes(rhs) for level, lhs, rhs in items)
+    out = C.create_string_buffer(32 * len(items))
+    assert load().mkl_combine_host(buf, len(items), out) == 0
+    return [out.raw[32 * i:32 * i + 32] for i in range(len(items))]
+
+
+def is_canonical(nodes):
+    out = C.create_string_buffer(len(nodes))
+    assert load().mkl_is_canonical_host(b"".join(bytes(x) for x in nodes), len(nodes), out) == 0
+    return [b != 0 for b in out.raw]
+
+
+def row(n, i):
+    s, w = C.c_uint64(0), C.c_uint64(0)
+    load().mkl_row_host(n, i, C.byref(s), C.byref(w))
+    return s.value, w.value
