@@ -9,6 +9,7 @@
 #include "host/groth16_vk.h"
 #include "host/pairing_prog.h"
 #include "internal.h"
+#include "verify_launch.h"
 
 using namespace masp;
 
@@ -113,9 +114,7 @@ int masp_hip_verify_batch(masp_hip_ctx* ctx, masp_hip_vk* vk, size_t n, const ui
     MASP_LAUNCH(k_verify_prepare, dim3((nn + 63) / 64, 5), dim3(64), 0, s, d_proofs.p, d_z.p, nn, d_za.p, d_b.p, d_zc.p, d_status.p);
     MASP_LAUNCH(k_g1_sum_export, dim3(1), dim3(256), 0, s, d_zc.p, nn, d_sum.p);
     MASP_LAUNCH(k_miller_pairs, dim3(nn), dim3(64), lds, s, vk->dbl, vk->add, vk->n_slots, d_za.p, d_b.p, d_f.p);
-    const uint32_t g = std::min<uint32_t>(nn, 64);
-    MASP_LAUNCH(k_fp12_product, dim3(g), dim3(64), lds, s, vk->mul12, vk->n_slots, d_f.p, nn, g);
-    if (g > 1) MASP_LAUNCH(k_fp12_product, dim3(1), dim3(64), lds, s, vk->mul12, vk->n_slots, d_f.p, g, 1u);
+    launch_fp12_product(s, vk->mul12, vk->n_slots, lds, d_f.p, nn);
     std::vector<int> status(n);
     masp_host::bls::Fp12 f;
     uint8_t sum96[96];

@@ -10,60 +10,8 @@ import pytest
 
 import oracle_lib as O
 import toy_r1cs
-from pyref import F1, F2, G1, G2, P, R, ec_add, ec_mul, g1_comp, g2_comp
-
-
-def _sqrt_fp(a):
-    r = pow(a, (P + 1) // 4, P)
-    return r if r * r % P == a else None
-
-
-def _sqrt_fp2(a):
-    if a == (0, 0):
-        return a
-    a0, a1 = a
-    n = _sqrt_fp((a0 * a0 + a1 * a1) % P)
-    if n is None:
-        return None
-    for sg in (n, (-n) % P):
-        d = (a0 + sg) * pow(2, -1, P) % P
-        x0 = _sqrt_fp(d)
-        if x0:
-            r = (x0, a1 * pow(2 * x0, -1, P) % P)
-            if F2.mul(r, r) == a:
-                return r
-    return None
-
-
-def _g1_decompress(b):
-    x = int.from_bytes(bytes([b[0] & 0x1f]) + b[1:48], "big")
-    y = _sqrt_fp((x ** 3 + 4) % P)
-    if (y > (P - 1) // 2) != bool(b[0] & 0x20):
-        y = P - y
-    return (x, y)
-
-
-def _g2_decompress(b):
-    x = (int.from_bytes(b[48:96], "big"), int.from_bytes(bytes([b[0] & 0x1f]) + b[1:48], "big"))
-    y = _sqrt_fp2(F2.add(F2.mul(F2.mul(x, x), x), (4, 4)))
-    big = (y[1] > (P - 1) // 2) if y[1] else (y[0] > (P - 1) // 2)
-    if big != bool(b[0] & 0x20):
-        y = F2.neg(y)
-    return (x, y)
-
-
-def small_order_points():
-    """T1 = (0, 2): order 3 on y^2 = x^3 + 4.  T2: a point of the twist outside G2, times r: its order divides the cofactor."""
-    t1 = (0, 2)
-    assert ec_mul(F1, t1, 3) is None
-    x = (2, 0)
-    while True:
-        y = _sqrt_fp2(F2.add(F2.mul(F2.mul(x, x), x), (4, 4)))
-        if y is not None and ec_mul(F2, (x, y), R) is not None:
-            break
-        x = (x[0] + 1, 0)
-    t2 = ec_mul(F2, (x, y), R)
-    return t1, t2
+from pyref import F1, F2, G1, G2, R, ec_add, ec_mul, g1_comp, g2_comp
+from verify_ref import _g1_decompress, _g2_decompress, _sqrt_fp, _sqrt_fp2, small_order_points  # noqa: F401  (they lived here first)
 
 
 def malleated(proof):

@@ -14,10 +14,14 @@ def _le(x):
     return np.frombuffer((x % R).to_bytes(32, "little"), dtype=np.uint8)
 
 
-def make(seed, n_inputs=3, n_free=6, n_constraints=20, bool_share=0.5, max_terms=3):
-    """returns (R1cs, inputs u8[n_inputs,32], aux u8[n_aux,32], values list[int])"""
+def make(seed, n_inputs=3, n_free=6, n_constraints=20, bool_share=0.5, max_terms=3, input_values=None):
+    """returns (R1cs, inputs u8[n_inputs,32], aux u8[n_aux,32], values list[int]).  input_values: the n_inputs - 1 public inputs to use
+    instead of the seeded ones: the same constraint system (its shape and coefficients come from the seed alone) with another statement"""
     rng = random.Random(seed)
     vals = [1] + [rng.randrange(R) for _ in range(n_inputs - 1)]          # inputs (ONE first)
+    if input_values is not None:
+        assert len(input_values) == n_inputs - 1
+        vals = [1] + [v % R for v in input_values]
     n_in = n_inputs
     aux = []
     rows = {"a": [], "b": [], "c": []}
