@@ -170,6 +170,16 @@ int masp_hip_ctx_get_options(const masp_hip_ctx* ctx, masp_hip_options* out);
  * replicates the CRS on every device (side by side).  A device may be listed more than once (two contexts on one
  * GPU).  The building-block and measurement entry points of such a context run on devices[0]. */
 int masp_hip_ctx_create_multi(const int* devices, int n_devices, masp_hip_ctx** out);
+/* Subset rows behind the window tables ("boolean blocks").  A third of a MASP witness is the scalar 1, and every such scalar is one entry
+ * of the MSM's bucket 0.  With block width k = 2^bits the loader also stores, for every aligned block of k consecutive points of the a,
+ * b_g1, b_g2 queries and of the l part of the merged h + l table, the 2^k - 1 sums of its non-empty subsets; a block whose k scalars are
+ * all 0 or 1 then costs one entry instead of up to k.  Same proof bytes (the same group elements summed in another order); a block in
+ * which some subset sums to the point at infinity is left to the plain path.  bits: 0 = the build's default, -1 = off, 2 or 3.
+ * Applies to circuits loaded AFTER the call.  Extra table memory for Spend, from the row counts: k = 4 ~0.1 GB,
+ * k = 8 ~1.5 GB.  (A call and not a field of masp_hip_options: that struct's size is part of the ABI older callers are checked against.) */
+int masp_hip_ctx_set_boolean_block_bits(masp_hip_ctx* ctx, int32_t bits);
+/* the resolved setting: 0 = no subset rows, 2 or 3 */
+int masp_hip_ctx_get_boolean_block_bits(const masp_hip_ctx* ctx, int32_t* out);
 /* number of device contexts behind `ctx` (1 for masp_hip_ctx_create) */
 int masp_hip_ctx_device_count(const masp_hip_ctx* ctx);
 /* counts[d] = proofs written so far by device context d (d < min(cap, masp_hip_ctx_device_count)): lets a caller (and the
@@ -243,6 +253,14 @@ int masp_hip_msm_g1_multi(masp_hip_ctx* ctx, const uint8_t* bases, size_t n, con
 /* the same over G2 (bases n x 192, out np x 192) */
 int masp_hip_msm_g2_multi(masp_hip_ctx* ctx, const uint8_t* bases, size_t n, const uint8_t* scalars, size_t np, int window_bits,
                           uint8_t* out);
+/* The two above with subset rows behind the window tables, chosen per call: block_bits = 0 (none), 2 or 3 — blocks of 4 / 8 consecutive bases
+ * by absolute index, those that lie wholly inside [sub_lo, sub_hi) (both cut to n) — see masp_hip_ctx_set_boolean_block_bits.  The plain
+ * entry points build no subset rows.  bucket0_entries (np words, may be NULL): the entries of every proof's bucket 0 after
+ * the sort — digits of magnitude 1, unit scalars outside an all-boolean block, and one per all-boolean block with a 1 in it. */
+int masp_hip_msm_g1_multi_ex(masp_hip_ctx* ctx, const uint8_t* bases, size_t n, const uint8_t* scalars, size_t np, int window_bits,
+                             int block_bits, size_t sub_lo, size_t sub_hi, uint8_t* out, uint32_t* bucket0_entries);
+int masp_hip_msm_g2_multi_ex(masp_hip_ctx* ctx, const uint8_t* bases, size_t n, const uint8_t* scalars, size_t np, int window_bits,
+                             int block_bits, size_t sub_lo, size_t sub_hi, uint8_t* out, uint32_t* bucket0_entries);
 /* h = ((A*B - C)/Z) coefficients from evaluation vectors a,b,c (nrows x 32 each, zero-padded to 2^logm);
  * h_out: (2^logm - 1) x 32 */
 int masp_hip_quotient_h(masp_hip_ctx* ctx, const uint8_t* a, const uint8_t* b, const uint8_t* c, size_t nrows,

@@ -73,6 +73,20 @@ __global__ void __launch_bounds__(64) k_msm_precompute(TabRow<O>* __restrict__ t
         tab[(size_t)j * n + i].p = p;
     }
 }
+// The subset rows behind the window tables (MsmSubset, msm_geom.h): one lane per row sums the bases of its bit pattern with the complete
+// mixed addition (two equal bases in a block are a doubling) and stores the sum in affine form.  A sum at infinity marks its block in `bad`:
+// the sort then treats the block as not covered, and no entry ever names such a row.
+template <class O>
+__global__ void __launch_bounds__(64) k_msm_subset_rows(TabRow<O>* __restrict__ tab, MsmSubset sub, uint32_t n_rows) {
+    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rows) return;
+    const uint32_t per = sub.patterns(), rb = r / per, pattern = r % per + 1u, i0 = (sub.b_first + rb) << sub.bits;
+    Xyzz<O> acc = xyzz_inf<O>();
+    for (uint32_t t = 0; t < (1u << sub.bits); ++t)
+        if ((pattern >> t) & 1u) xyzz_madd_nc(acc, tab[i0 + t].p, false);
+    if (xyzz_is_inf(acc)) atomicOr(&sub.bad[rb >> 5], 1u << (rb & 31u));
+    tab[(size_t)sub.row0 + r].p = xyzz_to_affine(acc);
+}
 
 // ---- (4) accumulate: device/msm_acc.hpp (its own translation unit) -------------------------------------
 

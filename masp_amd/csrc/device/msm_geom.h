@@ -27,6 +27,24 @@ __host__ __device__ static inline uint32_t msm_chunk_len(uint32_t total, uint32_
     return k < 4 ? 4 : k;  // at least 4 additions per lane: fewer partials to gather
 }
 
+// Subset rows behind the window tables of a base set (MsmBases, msm_host.h): for every aligned block of k = 2^bits consecutive bases that
+// lies wholly inside [lo, hi), the 2^k - 1 sums of its non-empty subsets.  Block b = scalars k b .. k b + k - 1 by absolute index; the row of
+// pattern p != 0 (bit t: base k b + t) is  row0 + (b - b_first)(2^k - 1) + p - 1.  A block of scalars that are all 0 or 1 is then ONE entry
+// of bucket 0 instead of up to k (device/msm_sort.hpp: msm_unit_lanes).  bad: one bit per covered block, set where a subset sums to the
+// point at infinity (P and -P in one block, a base at infinity): such a block is treated as not covered, so no entry names a row at infinity.
+struct MsmSubset {
+    uint32_t bits = 0;              // log2 of the block width: 0 = none, else 2 or 3 (blocks tile a 64-lane wave)
+    uint32_t b_first = 0, b_end = 0;  // covered blocks [b_first, b_end)
+    uint32_t row0 = 0;              // the first subset row = W n
+    uint32_t* bad = nullptr;        // [bad_words()] device words (written at load time only)
+    __host__ __device__ uint32_t bad_words() const { return (b_end - b_first + 31) / 32; }
+    __host__ __device__ uint32_t patterns() const { return (1u << (1u << bits)) - 1u; }
+    __host__ __device__ uint64_t rows() const { return bits ? (uint64_t)(b_end - b_first) * patterns() : 0; }
+};
+// scalars per range (= sorting workgroup) of a proof: a multiple of 64, so that lane l of every wave holds a scalar whose index is l mod 64
+// and an aligned block of scalars is an aligned group of lanes
+__host__ __device__ static inline uint32_t msm_range_len(uint32_t n, uint32_t ng) { return ((n + ng - 1) / ng + 63u) & ~63u; }
+
 // weighted-sum geometry (k_msm_wsum_level): 128 lanes per workgroup, 2^G_LOG buckets per lane
 static constexpr unsigned WSUM_L_LOG = 7, WSUM_L = 1u << WSUM_L_LOG;
 static constexpr unsigned WSUM_G_LOG_MIN = 2;

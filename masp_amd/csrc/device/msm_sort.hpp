@@ -19,7 +19,8 @@ namespace masp {
 //   k_msm_scatter  reloads  start[b] + rel[wg][b]  into LDS, recomputes the digits of the same range and places every
 //                  entry with one LDS atomic.
 // Scalars equal to 1 (a third of a MASP witness: booleans) all land in bucket 0 of window 0; a wave counts / places them
-// with one ballot instead of 64 colliding atomics.  Zero scalars (38 %) produce nothing.
+// with one ballot instead of 64 colliding atomics.  Zero scalars (38 %) produce nothing.  Where the base set has subset rows (MsmSubset,
+// msm_geom.h), an aligned block of k boolean scalars is ONE such entry, the row of the block's bit pattern (msm_unit_lanes).
 // scalars: n x 8 canonical little-endian limbs.  sorted entry = table row (j*n + i) | sign << 31, j = the window of the digit.
 // (Round 5 also had width-w NAF digits over a table per bit position here, as a template parameter of the iterator and its three kernels;
 // removed in round 6 — the tables it needs are beyond an XCD's TLB reach: EXPERIMENTS.md, profiles/r05_naf_digits_*.txt.)
@@ -60,23 +61,50 @@ __device__ __forceinline__ int msm_scalar_class(const uint32_t* sw) {
     if (rest == 0 && lo.x <= 1) return (int)lo.x;
     return 2;
 }
+// The entries of bucket 0 that the unit scalars of a wave become — the ONE classification k_msm_hist, k_msm_partition and k_msm_scatter
+// share, so that they agree on every entry.  Every lane of the wave calls it (two ballots) with the class of scalar i, and lane l holds a
+// scalar with i = l mod 64 (msm_range_len).  Returns the lanes that emit an entry; `entry` is this lane's, if it is one of them:
+//   without subset rows (MsmSubset, msm_geom.h), or outside a covered block: every unit scalar emits row i of window 0;
+//   a group of k adjacent lanes that holds a covered, good block of scalars that are all 0 or 1: its first lane emits the subset row of
+//   the block's bit pattern unless that is zero, the other lanes of the group nothing.
+// A lane's rank among the wave's entries is the popcount of the returned mask below it, as for the unit scalars alone before.
+__device__ __forceinline__ uint64_t msm_unit_lanes(int cls, uint32_t i, const MsmSubset& sub, uint32_t& entry) {
+    const uint64_t ones = __ballot(cls == 1);
+    entry = i;
+    if (sub.bits == 0) return ones;
+    const uint32_t lane = threadIdx.x & 63u, k = 1u << sub.bits, blk = i >> sub.bits;
+    bool covered = false;
+    if (cls <= 1 && blk >= sub.b_first && blk < sub.b_end) {
+        const uint32_t rb = blk - sub.b_first;
+        covered = ((sub.bad[rb >> 5] >> (rb & 31u)) & 1u) == 0;
+    }
+    const uint64_t boolean = __ballot(covered);
+    const uint32_t g0 = lane & ~(k - 1u);
+    const uint64_t gm = (uint64_t)((1u << k) - 1u) << g0;
+    const bool full = (boolean & gm) == gm;
+    const uint32_t pattern = (uint32_t)((ones & gm) >> g0);
+    const bool lead = full && lane == g0 && pattern != 0;
+    if (lead) entry = sub.row0 + (blk - sub.b_first) * sub.patterns() + pattern - 1u;
+    return __ballot(full ? lead : cls == 1);
+}
 __global__ void __launch_bounds__(1024)
-k_msm_hist(const uint32_t* __restrict__ scalars, size_t scalar_stride, uint32_t n, MsmGeom g, uint32_t ng, uint32_t* __restrict__ hist_wg) {
+k_msm_hist(const uint32_t* __restrict__ scalars, size_t scalar_stride, uint32_t n, MsmGeom g, uint32_t ng, MsmSubset sub, uint32_t* __restrict__ hist_wg) {
     extern __shared__ uint32_t msm_lds[];
     const uint32_t tid = threadIdx.x, wg = blockIdx.x, nb = (uint32_t)g.nb;
     scalars += MSM_P * scalar_stride;
     hist_wg += ((size_t)MSM_P * ng + wg) * nb;
     for (uint32_t b = tid; b < nb; b += MSM_SORT_THREADS) msm_lds[b] = 0;
     __syncthreads();
-    const uint32_t per = (n + ng - 1) / ng, lo = wg * per, hi = lo + per < n ? lo + per : n;
+    const uint32_t per = msm_range_len(n, ng), lo = wg * per, hi = lo < n && lo + per < n ? lo + per : n;
     for (uint32_t base = lo; base < hi; base += MSM_SORT_THREADS) {
         const uint32_t i = base + tid;
         const uint32_t* sw = scalars + (size_t)i * 8;
         const int cls = i < hi ? msm_scalar_class(sw) : 0;
-        const uint64_t ones = __ballot(cls == 1);
-        if (cls == 1) {
-            if ((uint32_t)__ffsll((unsigned long long)ones) - 1u == (tid & 63u)) atomicAdd(&msm_lds[0], (uint32_t)__popcll(ones));
-        } else if (cls == 2) {
+        uint32_t unit_entry;
+        const uint64_t units = msm_unit_lanes(cls, i, sub, unit_entry);
+        if (cls != 2) {
+            if (units && (uint32_t)__ffsll((unsigned long long)units) - 1u == (tid & 63u)) atomicAdd(&msm_lds[0], (uint32_t)__popcll(units));
+        } else {
             MsmDigitIter it(sw, g);
             for (int j = 0; j < g.W; ++j) {
                 uint32_t table, bucket, neg;
@@ -199,7 +227,7 @@ k_msm_offsets_scan_b(uint32_t nb, uint32_t* __restrict__ start, uint32_t* __rest
     }
 }
 __global__ void __launch_bounds__(1024)
-k_msm_scatter(const uint32_t* __restrict__ scalars, size_t scalar_stride, uint32_t n, MsmGeom g, uint32_t ng, const uint32_t* __restrict__ rel,
+k_msm_scatter(const uint32_t* __restrict__ scalars, size_t scalar_stride, uint32_t n, MsmGeom g, uint32_t ng, MsmSubset sub, const uint32_t* __restrict__ rel,
               const uint32_t* __restrict__ start, uint32_t* __restrict__ sorted, size_t sorted_stride) {
     extern __shared__ uint32_t msm_lds[];
     const uint32_t tid = threadIdx.x, wg = blockIdx.x, nb = (uint32_t)g.nb;
@@ -209,18 +237,20 @@ k_msm_scatter(const uint32_t* __restrict__ scalars, size_t scalar_stride, uint32
     sorted += (size_t)MSM_P * sorted_stride;
     for (uint32_t b = tid; b < nb; b += MSM_SORT_THREADS) msm_lds[b] = start[b] + rel[b];
     __syncthreads();
-    const uint32_t per = (n + ng - 1) / ng, lo = wg * per, hi = lo + per < n ? lo + per : n;
+    const uint32_t per = msm_range_len(n, ng), lo = wg * per, hi = lo < n && lo + per < n ? lo + per : n;
     for (uint32_t base = lo; base < hi; base += MSM_SORT_THREADS) {
         const uint32_t i = base + tid;
         const uint32_t* sw = scalars + (size_t)i * 8;
         const int cls = i < hi ? msm_scalar_class(sw) : 0;
-        const uint64_t ones = __ballot(cls == 1);
-        if (ones) {
-            const int leader = __ffsll((unsigned long long)ones) - 1;
+        uint32_t unit_entry;
+        const uint64_t units = msm_unit_lanes(cls, i, sub, unit_entry);
+        if (units) {
+            const int leader = __ffsll((unsigned long long)units) - 1;
             uint32_t first = 0;
-            if ((int)(tid & 63u) == leader) first = atomicAdd(&msm_lds[0], (uint32_t)__popcll(ones));
+            if ((int)(tid & 63u) == leader) first = atomicAdd(&msm_lds[0], (uint32_t)__popcll(units));
             first = __shfl(first, leader, 64);
-            if (cls == 1) sorted[first + (uint32_t)__popcll(ones & ((1ull << (tid & 63u)) - 1ull))] = i;  // window 0: row i, positive
+            // window 0: row i, or the subset row of an all-boolean block; positive
+            if ((units >> (tid & 63u)) & 1ull) sorted[first + (uint32_t)__popcll(units & ((1ull << (tid & 63u)) - 1ull))] = unit_entry;
         }
         if (cls == 2) {
             MsmDigitIter it(sw, g);
@@ -297,7 +327,7 @@ __device__ __forceinline__ void msm_small_scan(const uint32_t* cnt, uint32_t* of
     }
 }
 __global__ void __launch_bounds__(1024)
-k_msm_partition(const uint32_t* __restrict__ scalars, size_t scalar_stride, uint32_t n, MsmGeom g, uint32_t ng, const uint32_t* __restrict__ crel,
+k_msm_partition(const uint32_t* __restrict__ scalars, size_t scalar_stride, uint32_t n, MsmGeom g, uint32_t ng, MsmSubset sub, const uint32_t* __restrict__ crel,
                 const uint32_t* __restrict__ start /* packed offsets: MsmSortBuf::dense */, uint32_t* __restrict__ tmp, uint8_t* __restrict__ tmpf,
                 uint32_t wide) {
     extern __shared__ uint32_t msm_lds[];
@@ -317,14 +347,16 @@ k_msm_partition(const uint32_t* __restrict__ scalars, size_t scalar_stride, uint
     tmp += (size_t)MSM_P * n * g.W;
     tmpf += (size_t)MSM_P * n * g.W;
     if (tid < nbins) cursor[tid] = start[tid << MSM_FINE_LOG] + crel[tid];
-    const uint32_t per = (n + ng - 1) / ng, lo = wg * per, hi = lo + per < n ? lo + per : n;
+    const uint32_t per = msm_range_len(n, ng), lo = wg * per, hi = lo < n && lo + per < n ? lo + per : n;
     for (uint32_t base = lo; base < hi; base += MSM_PART_TILE) {
         if (tid < nbins) cnt[tid] = 0;
         __syncthreads();
         const uint32_t i = base + tid;
         const uint32_t* sw = scalars + (size_t)i * 8;
         const int cls = i < hi ? msm_scalar_class(sw) : 0;
-        const uint64_t ones = __ballot(cls == 1);
+        uint32_t unit_entry;
+        const uint64_t ones = msm_unit_lanes(cls, i, sub, unit_entry);  // the lanes with an entry of bucket 0 of their own: unit scalars, block leaders
+        const bool unit = (ones >> (tid & 63u)) & 1ull;
         const int leader = ones ? __ffsll((unsigned long long)ones) - 1 : -1;
         // ONE pass over the digits of a tile: the counting atomic already hands out the entry's rank inside its bin, the entry
         // and (rank, bin, low bucket bits) wait in registers for the scan of the counts (the digits were extracted and counted twice before)
@@ -353,8 +385,8 @@ k_msm_partition(const uint32_t* __restrict__ scalars, size_t scalar_stride, uint
         __syncthreads();
         msm_small_scan(cnt, off, fill, nbins, total, wsum);
         __syncthreads();
-        if (cls == 1) {
-            stage[off[0] + unit_rank] = i;
+        if (unit) {
+            stage[off[0] + unit_rank] = unit_entry;
             stageb[off[0] + unit_rank] = 0;
             if (wide) stagef[off[0] + unit_rank] = 0;
         }

@@ -23,6 +23,17 @@
 #include <atomic>
 #include "util.h"
 
+// block width (log2) of the subset rows behind the a, b and merged h + l window tables when a context is not told otherwise
+// (masp_hip_ctx_set_boolean_block_bits, include/masp_hip.h): 0 = none, 2 or 3.  A compile-time default, so that two builds can be compared with bench.py.
+// 2: blocks of four, + 1.6 % proofs/s for about 0.1 GB of tables per Spend circuit.  Blocks of eight measured + 2.2 % end to end, but take the
+// Spend tables past the 3.5 GiB an XCD's gathers reach, and the kernel profile that shows the level-0 pass of h + l no slower is not yet
+// taken (MEASUREMENTS.md "Boolean blocks"): 3 stays an option until it is.
+#ifndef MASP_SUBSET_BITS
+#define MASP_SUBSET_BITS 2
+#endif
+static_assert(MASP_SUBSET_BITS == 0 || MASP_SUBSET_BITS == 2 || MASP_SUBSET_BITS == 3, "subset blocks are 4 or 8 bases wide");
+
+
 namespace masp {
 
 template <class T>
@@ -311,6 +322,9 @@ struct masp_hip_ctx {
     // multi-device front (masp_hip_ctx_create_multi): one full context per device; this object only shards and forwards
     std::vector<masp_hip_ctx*> children;
     masp_hip_options opt{};   // resolved at creation (prover.hip: resolve_options); the library reads no environment
+    // block width (log2) of the subset rows behind the tables of circuits loaded from now on, resolved: 0 = none, 2 or 3
+    // (masp_hip_ctx_set_boolean_block_bits; the build's default is MASP_SUBSET_BITS)
+    int boolean_block_bits = MASP_SUBSET_BITS;
     int n_slots = 4;          // = opt.slots
     size_t batch_cap = 256;   // = opt.batch_cap
     std::shared_mutex mu;

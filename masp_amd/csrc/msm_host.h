@@ -25,13 +25,21 @@ struct MsmBases {
     MsmGeom g{};
     uint32_t n = 0;
     uint32_t n_eff = 0;        // scalars expected to be neither 0 nor 1 (<= n): the mean length of a bucket's run follows from it
-    TabRow<O>* tab = nullptr;  // g.W * n rows of 128 / 256 bytes
+    TabRow<O>* tab = nullptr;  // rows() rows of 128 / 256 bytes: g.W * n window rows, then the subset rows
     int import_status = 0;     // PT_* bits seen while decoding
+    // Subset rows behind the window tables (MsmSubset, device/msm_geom.h): for the aligned blocks of 2^sub_bits consecutive bases that lie
+    // wholly inside [sub_lo, sub_hi), every sum of a non-empty subset — a block of boolean scalars is one entry of bucket 0.
+    MsmSubset sub;                       // sub.bits == 0: none; sub.bad is owned by this object
+    uint32_t sub_lo = 0, sub_hi = 0;     // the covered index range the blocks of `sub` were cut from
+    const MsmSubset& subset() const { return sub; }
+    uint64_t rows() const { return (uint64_t)n * (uint32_t)g.W + sub.rows(); }
 
     ~MsmBases() { release(); }
     void release() {
         if (tab) dev_free(tab);
+        if (sub.bad) dev_free(sub.bad);
         tab = nullptr;
+        sub = MsmSubset();
     }
     // Window width by the number of scalars expected to be neither 0 nor 1 (`n_eff`; the caller knows the witness
     // statistics of its circuit, a generic caller passes n): per non-trivial scalar the accumulation costs W = 256/c
@@ -41,15 +49,17 @@ struct MsmBases {
         return msm_geom(c);
     }
     // raw: device pointer to n uncompressed points (bellman wire format)          [msm_impl.hpp]
-    // force_c: window width (0: pick_geom)
-    int load_device(const uint8_t* d_raw, uint32_t n_, hipStream_t s, uint32_t n_eff = 0xffffffffu, int force_c = 0);
-    int load_host(const uint8_t* raw, uint32_t n_, hipStream_t s, uint32_t n_eff = 0xffffffffu, int force_c = 0) {
+    // force_c: window width (0: pick_geom).  sub_bits_ / [sub_lo_, sub_hi_): subset rows (0: none; the range is cut to [0, n))
+    int load_device(const uint8_t* d_raw, uint32_t n_, hipStream_t s, uint32_t n_eff = 0xffffffffu, int force_c = 0, int sub_bits_ = 0,
+                    uint32_t sub_lo_ = 0, uint32_t sub_hi_ = 0xffffffffu);
+    int load_host(const uint8_t* raw, uint32_t n_, hipStream_t s, uint32_t n_eff = 0xffffffffu, int force_c = 0, int sub_bits_ = 0, uint32_t sub_lo_ = 0,
+                  uint32_t sub_hi_ = 0xffffffffu) {
         uint8_t* d_raw = nullptr;
         if (n_) {
             HIP_TRY(dev_malloc(&d_raw, (size_t)n_ * BYTES));
             HIP_TRY(hipMemcpyAsync(d_raw, raw, (size_t)n_ * BYTES, hipMemcpyHostToDevice, s));
         }
-        int rc = load_device(d_raw, n_, s, n_eff, force_c);
+        int rc = load_device(d_raw, n_, s, n_eff, force_c, sub_bits_, sub_lo_, sub_hi_);
         if (d_raw) dev_free(d_raw);
         return rc;
     }
@@ -63,7 +73,8 @@ struct MsmSortBuf {
     uint8_t* tmpf = nullptr;                   // ... and the low 7 bits of every such entry's bucket, where the entry word has no room
                                                // for them (msm_rows_wide: more than 2^24 table rows); not allocated otherwise
     bool has_tmpf = false;
-    static bool msm_rows_wide(uint32_t n_, const MsmGeom& g_) { return (uint64_t)n_ * (uint32_t)g_.W > (1u << 24); }
+    // rows: every row an entry can name — the window rows and the subset rows behind them (MsmBases::rows)
+    static bool msm_rows_wide(uint64_t rows) { return rows > (1u << 24); }
     uint32_t* dense = nullptr;                 // [np][nb + 1] offsets without padding (where a bin lies in `tmp`)
     uint2* btot = nullptr;                     // [np][ceil(nb / 1024)] the offsets scan's block totals (packed, aligned)
     // what the last msm_sort_enqueue produced (consumed by msm_reduce_enqueue)
@@ -99,13 +110,13 @@ struct MsmSortBuf {
         ng = std::min(ng, 64u);
         return std::max(1u, std::min(ng, (n + 1023) / 1024));
     }
-    int reserve(uint32_t n_, const MsmGeom& g_, uint32_t np_, uint32_t pad_log_ = 0) {
+    int reserve(uint32_t n_, const MsmGeom& g_, uint32_t np_, uint32_t pad_log_ = 0, uint64_t rows_ = 0) {
         // the per-workgroup histograms are addressed with the launch's own strides: np x ng x nb words, and np x ng <= 512
         // for every batch size (ranges_for) — a batch of 64 proofs (8 ranges each) fits what a batch of 256 (2 each) allocated
         const size_t need_ent = std::max(padded_entries(n_, g_, pad_log_), cap_ent), ng = ranges_for(n_, np_);
         const size_t bins = std::max<size_t>(g_.nb >> 7, 1);
         const size_t hist_need = (size_t)np_ * ng * g_.nb, crel_need = (size_t)np_ * ng * bins;
-        const bool want_tmpf = has_tmpf || msm_rows_wide(n_, g_);
+        const bool want_tmpf = has_tmpf || msm_rows_wide(std::max<uint64_t>(rows_, (uint64_t)n_ * (uint32_t)g_.W));
         if (need_ent <= cap_ent && (size_t)g_.nb <= cap_nb && np_ <= cap_np && hist_need <= cap_hist && crel_need <= cap_crel && want_tmpf == has_tmpf)
             return MASP_HIP_OK;
         const size_t need_nb = std::max<size_t>(g_.nb, cap_nb), need_np = std::max<size_t>(np_, cap_np);
@@ -373,9 +384,10 @@ struct MsmProfile {
 
 // Counting sort of the signed window digits of `np` scalar vectors (n scalars each) by bucket, on stream `s`.
 // scalars_p = d_scalars + p * scalar_stride (u32 units), n x 8 canonical LE limbs each.  No host synchronisation.   [k_msm_sort.hip]
-// pad_log: see MsmSortBuf (0: packed runs).
+// pad_log: see MsmSortBuf (0: packed runs).  sub: the subset rows of the base set the entries will be gathered from (MsmBases::subset) —
+// where two base sets are reduced from one sort, they have the same row layout and `sub.bad` is the union of their bitmaps.
 int msm_sort_enqueue(hipStream_t s, uint32_t n, const MsmGeom& g, MsmSortBuf& sb, const uint32_t* d_scalars, size_t scalar_stride, uint32_t np,
-                     uint32_t pad_log = 0);
+                     uint32_t pad_log = 0, const MsmSubset& sub = MsmSubset());
 
 // runs of the digit list padded to multiples of 2^MASP_TREE_PAD_LOG entries when a tree follows: that many levels need no records
 #ifndef MASP_TREE_PAD_LOG
@@ -427,9 +439,16 @@ int msm_enqueue(hipStream_t s, const MsmBases<O, BYTES>& B, MsmWorkspace<O>& ws,
     }
     // the tree wants runs of even length
     const bool tree = msm_tree_levels(B.n_eff, B.g, np, ws.tree_levels) || msm_tree_levels(B.n_eff, B.g, np, ws.tree_levels_shared);
-    int rc = msm_sort_enqueue(s, B.n, B.g, ws.sort, d_scalars, scalar_stride, np, tree ? (uint32_t)MASP_TREE_PAD_LOG : 0u);
+    int rc = msm_sort_enqueue(s, B.n, B.g, ws.sort, d_scalars, scalar_stride, np, tree ? (uint32_t)MASP_TREE_PAD_LOG : 0u, B.subset());
     if (rc) return rc;
     return msm_reduce_enqueue(s, B, ws.sort, ws, d_out, out_stride, prof);
+}
+
+// may base set b be reduced from the digit list sorted for base set a?  Same scalars (the caller's business), same length, same windows —
+// and then the same row layout of their subset rows, whose bad-block bitmaps the loader unites (masp_hip_circuit_load)
+template <class A, class B>
+inline bool msm_same_sort(const A& a, const B& b) {
+    return a.n == b.n && a.g.c == b.g.c;
 }
 
 typedef MsmBases<FpOps, 96> BasesG1;

@@ -26,23 +26,46 @@ static inline uint32_t log2_ceil_u64(uint64_t n) {
 }
 
 template <class O, int BYTES>
-int MsmBases<O, BYTES>::load_device(const uint8_t* d_raw, uint32_t n_, hipStream_t s, uint32_t n_eff, int force_c) {
+int MsmBases<O, BYTES>::load_device(const uint8_t* d_raw, uint32_t n_, hipStream_t s, uint32_t n_eff, int force_c, int sub_bits_, uint32_t sub_lo_,
+                                    uint32_t sub_hi_) {
         release();
         n = n_;
         this->n_eff = std::min(n_eff, n_);
         g = force_c ? msm_geom(force_c) : pick_geom(std::min(n_eff, n_));
         if (n == 0) return MASP_HIP_OK;
-        if ((uint64_t)n * (uint32_t)g.W > 0x7ffffffeull) {
+        if (sub_bits_ != 0 && sub_bits_ != 2 && sub_bits_ != 3) {
+            last_hip_error() = "MsmBases: subset blocks are 4 or 8 bases wide";
+            return MASP_HIP_E_INVALID_ARG;
+        }
+        // the blocks that lie wholly inside the covered range, by absolute index
+        sub_lo = std::min(sub_lo_, n);
+        sub_hi = std::min(sub_hi_, n);
+        if (sub_bits_) {
+            MsmSubset u;
+            u.bits = (uint32_t)sub_bits_;
+            u.b_first = (uint32_t)(((uint64_t)sub_lo + (1u << sub_bits_) - 1) >> sub_bits_);
+            u.b_end = sub_hi >> sub_bits_;
+            u.row0 = n * (uint32_t)g.W;
+            if (u.b_end > u.b_first) sub = u;
+        }
+        if (rows() > 0x7ffffffeull) {
+            sub = MsmSubset();
             last_hip_error() = "MsmBases: more table rows than an entry's 31 bits can name";
             return MASP_HIP_E_INVALID_ARG;
         }
-        HIP_TRY(dev_malloc(&tab, sizeof(TabRow<O>) * (size_t)g.W * n));
+        HIP_TRY(dev_malloc(&tab, sizeof(TabRow<O>) * (size_t)rows()));
         int* d_status;
         HIP_TRY(dev_malloc(&d_status, sizeof(int)));
         HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(int), s));
         dim3 grid((n + 63) / 64), block(64);
         MASP_LAUNCH((k_msm_import<O, BYTES>), grid, block, 0, s, d_raw, tab, n, d_status);
         MASP_LAUNCH((k_msm_precompute<O>), grid, block, 0, s, tab, n, g.c, g.W);
+        if (sub.bits) {
+            HIP_TRY(dev_malloc(&sub.bad, sizeof(uint32_t) * sub.bad_words()));
+            HIP_TRY(hipMemsetAsync(sub.bad, 0, sizeof(uint32_t) * sub.bad_words(), s));
+            const uint32_t n_rows = (uint32_t)sub.rows();
+            MASP_LAUNCH((k_msm_subset_rows<O>), dim3((n_rows + 63) / 64), block, 0, s, tab, sub, n_rows);
+        }
         HIP_TRY(hipMemcpyAsync(&import_status, d_status, sizeof(int), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         dev_free(d_status);

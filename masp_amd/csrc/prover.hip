@@ -234,7 +234,7 @@ static int enqueue_proofs(Slot& sl, Circuit& C, uint32_t np, const Fr* d_w, size
     if ((rc = sl.sa.reserve((size_t)C.na * np)) || (rc = sl.sb.reserve((size_t)C.nbq * np))) return rc;
     MsmProfile* prof = sl.profiling ? &sl.prof : nullptr;
     const size_t m8 = C.m * 8;
-    const bool share_b = C.nbq && C.b2.n == C.b1.n && C.b2.g.c == C.b1.g.c;  // B2 runs over the same scalars as B1
+    const bool share_b = C.nbq && msm_same_sort(C.b1, C.b2);  // B2 runs over the same scalars as B1
     if (lone) {
         // the four witness MSMs run on their own streams (forked above) while the main stream runs SpMV -> quotient -> H.
         // The pieces of the assembly start as soon as what they read exists: the fixed-base multiplications (r and s only)
@@ -263,7 +263,7 @@ static int enqueue_proofs(Slot& sl, Circuit& C, uint32_t np, const Fr* d_w, size
             if (C.nbq) launch_gather_scalars(sl.aux[2], d_w, w_stride, C.b_var.p, C.nbq, sl.sb.p, np);
             HIP_TRY(hipEventRecord(sl.ev_sort_b, sl.aux[2]));  // B2 on aux[3] reads sb (and, without tables of its own, B1's sort) behind this
             if (share_b) {
-                if ((r = msm_sort_enqueue(sl.aux[2], C.b1.n, C.b1.g, sl.ws_b.sort, (const uint32_t*)sl.sb.p, (size_t)C.nbq * 8, np))) return r;
+                if ((r = msm_sort_enqueue(sl.aux[2], C.b1.n, C.b1.g, sl.ws_b.sort, (const uint32_t*)sl.sb.p, (size_t)C.nbq * 8, np, 0, C.b1.subset()))) return r;
                 if (!own_b2) HIP_TRY(hipEventRecord(sl.ev_sort_b, sl.aux[2]));
                 if ((r = msm_reduce_enqueue(sl.aux[2], C.b1, sl.ws_b.sort, sl.ws_b, sl.res1.p + 3, 4))) return r;
             } else if ((r = msm_enqueue(sl.aux[2], C.b1, sl.ws_b, (const uint32_t*)sl.sb.p, (size_t)C.nbq * 8, sl.res1.p + 3, 4, np))) {
@@ -758,6 +758,23 @@ int masp_hip_ctx_get_options(const masp_hip_ctx* ctx, masp_hip_options* out) {
     return MASP_HIP_OK;
 }
 
+int masp_hip_ctx_set_boolean_block_bits(masp_hip_ctx* ctx, int32_t bits) {
+    if (!ctx || (bits != 0 && bits != -1 && bits != 2 && bits != 3)) return MASP_HIP_E_INVALID_ARG;
+    const int resolved = bits == 0 ? (int)(MASP_SUBSET_BITS) : bits < 0 ? 0 : bits;
+    auto set = [&](masp_hip_ctx* c) {
+        std::unique_lock<std::shared_mutex> lock(c->mu);
+        c->boolean_block_bits = resolved;
+    };
+    set(ctx);
+    for (masp_hip_ctx* c : ctx->children) set(c);
+    return MASP_HIP_OK;
+}
+int masp_hip_ctx_get_boolean_block_bits(const masp_hip_ctx* ctx, int32_t* out) {
+    if (!ctx || !out) return MASP_HIP_E_INVALID_ARG;
+    *out = (ctx->children.empty() ? ctx : ctx->children[0])->boolean_block_bits;
+    return MASP_HIP_OK;
+}
+
 int masp_hip_ctx_create(int device, masp_hip_ctx** out) {
     if (!out) return MASP_HIP_E_INVALID_ARG;
     return masp_hip_ctx_create_ex(&device, 1, nullptr, out);
@@ -971,10 +988,27 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
     const int c_h = ctx->opt.window_bits_h ? ctx->opt.window_bits_h : n_h >= 49152 ? 16 : n_h >= 16384 ? 15 : 0;
     // (h's own table serves lone proofs only: its window width is theirs to choose — masp_hip_options::window_bits_h_lone)
     const int c_h_lone = ctx->opt.window_bits_h_lone ? ctx->opt.window_bits_h_lone : c_h;
+    // subset rows (MsmSubset, device/msm_geom.h) behind the tables whose scalars are witness values — a, b_g1, b_g2 and the l part of the merged
+    // h + l —: a third of a witness is the scalar 1, and an aligned block of boolean scalars becomes one entry.  The tables that only lone
+    // proofs use (h, l, b2_lone) have none.
+    const int sub_bits = ctx->boolean_block_bits;
     if ((rc = C->h.load_host(L.h, (uint32_t)(C->m - 1), s, 0xffffffffu, c_h_lone)) || (rc = C->l.load_host(L.l, L.n_l, s, eff(L.n_l), c_la)) ||
-        (rc = C->a.load_host(L.a, L.n_a, s, eff(L.n_a), c_la)) || (rc = C->b1.load_host(L.b_g1, L.n_b1, s, eff(L.n_b1), c_b)) ||
-        (rc = C->b2.load_host(L.b_g2, L.n_b2, s, eff(L.n_b2), c_b2)))
+        (rc = C->a.load_host(L.a, L.n_a, s, eff(L.n_a), c_la, sub_bits)) || (rc = C->b1.load_host(L.b_g1, L.n_b1, s, eff(L.n_b1), c_b, sub_bits)) ||
+        (rc = C->b2.load_host(L.b_g2, L.n_b2, s, eff(L.n_b2), c_b2, sub_bits)))
         return fail(ctx, rc);
+    if (C->b1.sub.bits && C->b2.sub.bits && msm_same_sort(C->b1, C->b2)) {
+        // b_g2 is reduced from b_g1's sorted digit list (enqueue_proofs: share_b): the two tables have the same row layout, and the sort
+        // must leave alone every block that is bad in either — both bitmaps become their union
+        const uint32_t words = C->b1.sub.bad_words();
+        std::vector<uint32_t> w1(words), w2(words);
+        if (hipMemcpyAsync(w1.data(), C->b1.sub.bad, 4 * (size_t)words, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipMemcpyAsync(w2.data(), C->b2.sub.bad, 4 * (size_t)words, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+            return fail(ctx, MASP_HIP_E_HIP);
+        for (uint32_t i = 0; i < words; ++i) w1[i] |= w2[i];
+        if (hipMemcpyAsync(C->b1.sub.bad, w1.data(), 4 * (size_t)words, hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(C->b2.sub.bad, w1.data(), 4 * (size_t)words, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+            return fail(ctx, MASP_HIP_E_HIP);
+    }
     {
         const int c_lone = ctx->opt.window_bits_b2_lone;  // 0 = lone proofs share the batch tables (and B1's sort)
         if (c_lone > 0 && L.n_b2 && (rc = C->b2_lone.load_host(L.b_g2, L.n_b2, s, eff(L.n_b2), c_lone))) return fail(ctx, rc);
@@ -985,7 +1019,8 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
         memcpy(cat.data(), L.h, 96 * nh);
         memcpy(cat.data() + 96 * nh, L.l, 96 * (size_t)L.n_l);
         const int c_hl = c_h ? c_h : ctx->opt.window_bits_h_lone ? 0 : C->h.g.c;
-        if ((rc = C->hl.load_host(cat.data(), (uint32_t)(nh + L.n_l), s, 0xffffffffu, c_hl))) return fail(ctx, rc);
+        // (subset rows over the l part only: the quotient's coefficients are uniform in Fr)
+        if ((rc = C->hl.load_host(cat.data(), (uint32_t)(nh + L.n_l), s, 0xffffffffu, c_hl, sub_bits, (uint32_t)nh))) return fail(ctx, rc);
     }
     int st = C->h.import_status | C->l.import_status | C->a.import_status | C->b1.import_status | C->b2.import_status;
     if (st) return MASP_HIP_E_PARAMS_FORMAT;  // includes infinity inside a query vector, which bellman rejects
@@ -1367,10 +1402,14 @@ int masp_hip_prove(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* inputs, cons
 // np MSMs over ONE base set (how a batch of proofs uses the engine: gridDim.y = np, one launch per stage):
 // scalars np x n x 32 B, out np x BYTES uncompressed.  window_bits 0 = the engine's own choice for n.
 template <class O, int BYTES>
-static int msm_multi(masp_hip_ctx* ctx, const uint8_t* bases, size_t n, const uint8_t* scalars, size_t np, int window_bits, uint8_t* out) {
+static int msm_multi(masp_hip_ctx* ctx, const uint8_t* bases, size_t n, const uint8_t* scalars, size_t np, int window_bits, uint8_t* out,
+                     int block_bits = 0, size_t sub_lo = 0, size_t sub_hi = (size_t)-1, uint32_t* bucket0_entries = nullptr) {
     if (!ctx || !out || !np || np > 256 || !n || !bases || !scalars || n > (1u << 22) || window_bits < 0 || window_bits == 1 || window_bits > 16)
         return MASP_HIP_E_INVALID_ARG;
+    if (block_bits != 0 && block_bits != 2 && block_bits != 3) return MASP_HIP_E_INVALID_ARG;
     if (!ctx->children.empty()) ctx = ctx->children[0];
+    sub_lo = std::min(sub_lo, n);
+    sub_hi = std::min(sub_hi, n);
     std::unique_lock<std::shared_mutex> lock(ctx->mu);
     hipSetDevice(ctx->device);
     hipStream_t s = ctx->streams.main;
@@ -1393,10 +1432,16 @@ static int msm_multi(masp_hip_ctx* ctx, const uint8_t* bases, size_t n, const ui
     DevBuf<Xyzz<O>> res;
     DevBuf<uint8_t> d_out;
     int rc;
-    if ((rc = B.load_host(bases, (uint32_t)n, s, 0xffffffffu, window_bits))) return fail(ctx, rc);
+    if ((rc = B.load_host(bases, (uint32_t)n, s, 0xffffffffu, window_bits, block_bits, (uint32_t)sub_lo, (uint32_t)sub_hi))) return fail(ctx, rc);
     if (B.import_status & (PT_BAD_FLAGS | PT_NOT_CANONICAL)) return MASP_HIP_E_PARAMS_FORMAT;
     if ((rc = ctx->tmp_scalars.upload((const Fr*)scalars, n * np, s)) || (rc = res.reserve(np)) || (rc = d_out.reserve(BYTES * np))) return fail(ctx, rc);
     if ((rc = msm_enqueue(s, B, ws, (const uint32_t*)ctx->tmp_scalars.p, n * 8, res.p, 1, (uint32_t)np))) return fail(ctx, rc);
+    if (bucket0_entries) {
+        // the sort's packed offsets: dense[p][1] = entries of proof p's bucket 0 (digits of magnitude 1, unit scalars, boolean blocks)
+        if (hipMemcpy2DAsync(bucket0_entries, sizeof(uint32_t), ws.sort.dense + 1, sizeof(uint32_t) * ((size_t)B.g.nb + 1), sizeof(uint32_t), np,
+                             hipMemcpyDeviceToHost, s) != hipSuccess)
+            return fail(ctx, MASP_HIP_E_HIP);
+    }
     for (size_t p = 0; p < np; ++p) {
         if constexpr (BYTES == 96)
             launch_g1_export(s, res.p + p, d_out.p + BYTES * p);
@@ -1462,6 +1507,17 @@ int masp_hip_msm_g1_multi(masp_hip_ctx* ctx, const uint8_t* bases, size_t n, con
 int masp_hip_msm_g2_multi(masp_hip_ctx* ctx, const uint8_t* bases, size_t n, const uint8_t* scalars, size_t np, int window_bits, uint8_t* out) {
     const ApiLaunchScope api_scope;
     return msm_multi<Fp2Ops, 192>(ctx, bases, n, scalars, np, window_bits, out);
+}
+
+int masp_hip_msm_g1_multi_ex(masp_hip_ctx* ctx, const uint8_t* bases, size_t n, const uint8_t* scalars, size_t np, int window_bits, int block_bits,
+                             size_t sub_lo, size_t sub_hi, uint8_t* out, uint32_t* bucket0_entries) {
+    const ApiLaunchScope api_scope;
+    return msm_multi<FpOps, 96>(ctx, bases, n, scalars, np, window_bits, out, block_bits, sub_lo, sub_hi, bucket0_entries);
+}
+int masp_hip_msm_g2_multi_ex(masp_hip_ctx* ctx, const uint8_t* bases, size_t n, const uint8_t* scalars, size_t np, int window_bits, int block_bits,
+                             size_t sub_lo, size_t sub_hi, uint8_t* out, uint32_t* bucket0_entries) {
+    const ApiLaunchScope api_scope;
+    return msm_multi<Fp2Ops, 192>(ctx, bases, n, scalars, np, window_bits, out, block_bits, sub_lo, sub_hi, bucket0_entries);
 }
 
 int masp_hip_quotient_h(masp_hip_ctx* ctx, const uint8_t* a, const uint8_t* b, const uint8_t* c, size_t nrows, uint32_t logm, uint8_t* h_out) {

@@ -117,6 +117,11 @@ def load_library():
     L.masp_hip_msm_g2.argtypes = [vp, vp, vp, sz, vp]
     L.masp_hip_msm_g1_multi.argtypes = [vp, vp, sz, vp, sz, C.c_int, vp]
     L.masp_hip_msm_g2_multi.argtypes = [vp, vp, sz, vp, sz, C.c_int, vp]
+    if hasattr(L, "masp_hip_msm_g1_multi_ex"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
+        L.masp_hip_msm_g1_multi_ex.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_int, sz, sz, vp, vp]
+        L.masp_hip_msm_g2_multi_ex.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_int, sz, sz, vp, vp]
+        L.masp_hip_ctx_set_boolean_block_bits.argtypes = [vp, C.c_int32]
+        L.masp_hip_ctx_get_boolean_block_bits.argtypes = [vp, C.POINTER(C.c_int32)]
     L.masp_hip_quotient_h.argtypes = [vp, vp, vp, vp, sz, u32, vp]
     L.masp_hip_ntt.argtypes = [vp, vp, u32, C.c_int]
     L.masp_hip_vk_prepare.argtypes = [vp, vp, sz, C.POINTER(vp)]
@@ -546,6 +551,37 @@ class Context:
         out = np.zeros((npf, 192), dtype=np.uint8)
         self._check(self._L.masp_hip_msm_g2_multi(self._h, _p(bases), n, _p(scalars), npf, int(window_bits), _p(out)))
         return [out[i].tobytes() for i in range(npf)]
+
+    def _msm_multi_ex(self, fn, size, bases, scalars, window_bits, block_bits, sub_lo, sub_hi):
+        bases = _u8(bases, size)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint8)
+        npf, n = scalars.shape[0], scalars.shape[1]
+        assert scalars.shape == (npf, n, 32) and bases.shape[0] == n
+        out = np.zeros((npf, size), dtype=np.uint8)
+        cnt = np.zeros(npf, dtype=np.uint32)
+        self._check(fn(self._h, _p(bases), n, _p(scalars), npf, int(window_bits), int(block_bits), int(sub_lo), int(n if sub_hi is None else sub_hi),
+                       _p(out), _p(cnt)))
+        return [out[i].tobytes() for i in range(npf)], [int(c) for c in cnt]
+
+    def msm_g1_multi_ex(self, bases, scalars, window_bits=0, block_bits=0, sub_lo=0, sub_hi=None):
+        """msm_g1_multi with subset rows over the aligned blocks of 2^block_bits bases (0: none, 2, 3) inside [sub_lo, sub_hi) ->
+        (results, entries of every proof's bucket 0 after the sort)."""
+        return self._msm_multi_ex(self._L.masp_hip_msm_g1_multi_ex, 96, bases, scalars, window_bits, block_bits, sub_lo, sub_hi)
+
+    def msm_g2_multi_ex(self, bases, scalars, window_bits=0, block_bits=0, sub_lo=0, sub_hi=None):
+        """the same over G2"""
+        return self._msm_multi_ex(self._L.masp_hip_msm_g2_multi_ex, 192, bases, scalars, window_bits, block_bits, sub_lo, sub_hi)
+
+    def set_boolean_block_bits(self, bits):
+        """Block width (log2) of the subset rows behind the tables of circuits loaded FROM NOW ON: 0 = the build's default, -1 = off, 2 or 3."""
+        self._check(self._L.masp_hip_ctx_set_boolean_block_bits(self._h, int(bits)))
+
+    @property
+    def boolean_block_bits(self):
+        """the resolved value: 0 = no subset rows, 2 or 3"""
+        v = C.c_int32(0)
+        self._check(self._L.masp_hip_ctx_get_boolean_block_bits(self._h, C.byref(v)))
+        return int(v.value)
 
     def current_options(self):
         """masp_hip_ctx_get_options now: the options with what lack of tree scratch has changed since creation — the
