@@ -16,6 +16,7 @@
 #include <thread>
 #include <vector>
 
+#include "chunk_pipeline.h"
 #include "device/io.hpp"
 #include "device/ntt_geom.h"
 #include "launch.h"
@@ -442,11 +443,9 @@ static inline int get_domain(masp_hip_ctx* ctx, uint32_t logm, NttDomain** out) 
     return MASP_HIP_OK;
 }
 
-// the note scan's geometry and the pieces its two units share (defined in k_note_scan.hip)
-constexpr uint32_t NS_BLOCK = 256;
+// the note scan's limits (its geometry: chunk_pipeline.h) and the pieces its two units share (defined in k_note_scan.hip)
 constexpr size_t NS_MAX_IVKS = 4096;
 constexpr size_t NS_MAX_OUTPUTS = (size_t)1 << 26;
-constexpr size_t NS_CHUNK_PAIRS = (size_t)1 << 18;   // pairs per launch: one lane each, four waves on every SIMD of the chip
 // the digit masks of the trial kernels for n_ivk ivks (16 words each); MASP_HIP_E_INVALID_ARG if one is not below r_J
 int ns_recode_ivks(std::vector<uint32_t>& digits, size_t n_ivk, const uint8_t* ivks, bool signed_digits);
 // k_ns_decode over n epks of 32 bytes: a status byte and the Niels form (96 bytes) per output

@@ -20,7 +20,7 @@
 #include "device/jubjub.hpp"
 #include "device/note_scan.hpp"
 #include "device/poly1305.hpp"
-#include "internal.h"
+#include "scan_host.h"
 
 using namespace masp;
 
@@ -129,19 +129,9 @@ void recode(uint32_t out[16], const uint32_t k_in[8], bool signed_digits) {
     }
 }
 
-struct Hit {
-    uint32_t output, ivk;
-    uint8_t key[32];
-};
-
-struct ChunkInFlight {
-    size_t o0 = 0, n = 0;
-    int set = 0;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // before the upload, behind it, behind the kernels
-};
-
 // enqueues one chunk of outputs on its stream: upload, decode, repitch, trials, and the count's way back
-int enqueue_chunk(masp_hip_ctx* ctx, ChunkInFlight& c, size_t n_ivk, const uint8_t* epks, const uint8_t* encs, uint32_t* h_count) {
+int enqueue_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, ScanSetHost<3>& h, size_t n_ivk, const uint8_t* epks, const uint8_t* encs,
+                  uint32_t* h_count) {
     masp_hip_ctx::NoteScanSet& b = ctx->ns[c.set];
     hipStream_t s = ctx->streams.vk[c.set];
     const uint32_t n = (uint32_t)c.n, nb = (n + NS_BLOCK - 1) / NS_BLOCK, n_pad = nb * NS_BLOCK;
@@ -151,55 +141,19 @@ int enqueue_chunk(masp_hip_ctx* ctx, ChunkInFlight& c, size_t n_ivk, const uint8
         (rc = b.pts.reserve(sizeof(JNiels) * (size_t)n_pad)) || (rc = b.status.reserve(n_pad)) || (rc = b.count.reserve(1)) ||
         (rc = b.hit_idx.reserve(2 * cap)) || (rc = b.hit_keys.reserve(32 * cap)))
         return rc;
-    for (hipEvent_t& e : c.ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(c.ev[0], s));
+    if ((rc = h.create_events())) return rc;
+    HIP_TRY(hipEventRecord(h.ev[0], s));
     HIP_TRY(hipMemcpyAsync(b.epk.p, epks + 32 * c.o0, 32 * c.n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(b.raw.p, encs + NS_ENC * c.o0, NS_ENC * c.n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(b.count.p, 0, sizeof(uint32_t), s));
-    HIP_TRY(hipEventRecord(c.ev[1], s));
+    HIP_TRY(hipEventRecord(h.ev[1], s));
     launch_ns_decode(s, b.epk.p, n, b.status.p, b.pts.p);
     MASP_LAUNCH(k_ns_repitch, dim3(nb, NS_COLS), dim3(NS_BLOCK), 0, s, (const uint32_t*)b.raw.p, n, n_pad, (uint4*)b.ct.p);
     MASP_LAUNCH(k_ns_trial, dim3(nb, (uint32_t)n_ivk), dim3(NS_BLOCK), 0, s, (const uint32_t*)ctx->ns_digits.p, (const JNiels*)b.pts.p,
                 (const uint8_t*)b.status.p, (const uint4*)b.epk.p, (const uint4*)b.ct.p, n, n_pad, (uint32_t)c.o0, ctx->ns_inversion.load(),
                 b.count.p, (uint32_t)cap, (uint2*)b.hit_idx.p, (uint4*)b.hit_keys.p);
-    HIP_TRY(hipEventRecord(c.ev[2], s));
+    HIP_TRY(hipEventRecord(h.ev[2], s));
     HIP_TRY(hipMemcpyAsync(h_count, b.count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    return MASP_HIP_OK;
-}
-
-// waits for a chunk and takes its statuses and hits
-int collect_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, size_t n_ivk, const uint32_t* h_count, uint8_t* epk_status, std::vector<Hit>& hits,
-                  double ms[3]) {
-    masp_hip_ctx::NoteScanSet& b = ctx->ns[c.set];
-    hipStream_t s = ctx->streams.vk[c.set];
-    HIP_TRY(hipStreamSynchronize(s));
-    if (launch_status() != MASP_HIP_OK) return MASP_HIP_E_HIP;   // a refused launch: the buffers mean nothing
-    const size_t nh = *h_count;
-    if (nh > c.n * n_ivk) {
-        last_hip_error() = "note scan: hit count beyond the chunk's pairs";
-        return MASP_HIP_E_HIP;
-    }
-    if (epk_status) HIP_TRY(hipMemcpyAsync(epk_status + c.o0, b.status.p, c.n, hipMemcpyDeviceToHost, s));
-    std::vector<uint32_t> idx(2 * nh);
-    std::vector<uint8_t> keys(32 * nh);
-    if (nh) {
-        HIP_TRY(hipMemcpyAsync(idx.data(), b.hit_idx.p, 8 * nh, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(keys.data(), b.hit_keys.p, 32 * nh, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    for (size_t i = 0; i < nh; ++i) {
-        Hit h;
-        h.output = idx[2 * i];
-        h.ivk = idx[2 * i + 1];
-        memcpy(h.key, &keys[32 * i], 32);
-        hits.push_back(h);
-    }
-    float up = 0, kern = 0;
-    HIP_TRY(hipEventElapsedTime(&up, c.ev[0], c.ev[1]));
-    HIP_TRY(hipEventElapsedTime(&kern, c.ev[1], c.ev[2]));
-    ms[0] += up;
-    ms[1] += kern;
     return MASP_HIP_OK;
 }
 
@@ -250,54 +204,28 @@ int masp_hip_sapling_trial_decrypt(masp_hip_ctx* ctx, size_t n_ivk, const uint8_
         last_hip_error() = std::string("note scan: upload failed: ") + hipGetErrorString(hipGetLastError());
         return fail(ctx, MASP_HIP_E_HIP);
     }
-    // Chunks of outputs, alternately on the two verifier streams with a buffer set each: a chunk's upload runs beside the chunk before's kernels.
-    size_t per = std::max<size_t>(NS_BLOCK, NS_CHUNK_PAIRS / n_ivk / NS_BLOCK * NS_BLOCK);
-    std::vector<Hit> hits;
-    double ms[3] = {0, 0, 0};
-    ChunkInFlight fly[2];
+    // chunks of outputs, alternately on the two verifier streams with a buffer set each (chunk_pipeline.h)
+    ScanSetHost<3> host[2];   // events: before the upload, behind it, behind the kernels
     uint32_t h_count[2] = {0, 0};
-    bool pending[2] = {false, false};
-    rc = MASP_HIP_OK;
-    int set = 0;
-    for (size_t o0 = 0; o0 < n_out && !rc; o0 += per, set ^= 1) {
-        if (pending[set]) {   // the set's previous chunk, two chunks back
-            rc = collect_chunk(ctx, fly[set], n_ivk, &h_count[set], epk_status, hits, ms);
-            pending[set] = false;
-            if (rc) break;
-        }
-        fly[set].o0 = o0;
-        fly[set].n = std::min(per, n_out - o0);
-        fly[set].set = set;
-        rc = enqueue_chunk(ctx, fly[set], n_ivk, epks, enc_ciphertexts, &h_count[set]);
-        pending[set] = rc == MASP_HIP_OK;
-    }
-    for (int i = 0; i < 2; ++i) {   // (set: the older of the two first)
-        const int s2 = set ^ i;
-        if (!pending[s2]) continue;
-        if (!rc)
-            rc = collect_chunk(ctx, fly[s2], n_ivk, &h_count[s2], epk_status, hits, ms);
-        else
-            (void)hipStreamSynchronize(ctx->streams.vk[s2]);   // nothing of this call stays in flight
-    }
-    for (ChunkInFlight& c : fly)
-        for (hipEvent_t e : c.ev)
-            if (e) (void)hipEventDestroy(e);
+    std::vector<ScanHit<32>> hits;
+    double ms[2] = {0, 0};
+    rc = run_chunks(
+        n_out, chunk_outputs(n_ivk),
+        [&](const ChunkInFlight& c) { return enqueue_chunk(ctx, c, host[c.set], n_ivk, epks, enc_ciphertexts, &h_count[c.set]); },
+        [&](const ChunkInFlight& c) {
+            const masp_hip_ctx::NoteScanSet& b = ctx->ns[c.set];
+            return scan_collect(
+                ctx->streams.vk[c.set], c, host[c.set], [&](size_t& nh) { return (nh = h_count[c.set]) <= c.n * n_ivk; },
+                "note scan: hit count beyond the chunk's pairs", epk_status, b.status.p, b.hit_idx.p, b.hit_keys.p, hits, ms);
+        },
+        [&](int set) { (void)hipStreamSynchronize(ctx->streams.vk[set]); });
     if (rc) return fail(ctx, rc);
-    // the order lanes reached the counter in is not an order: by (output, ivk)
-    std::sort(hits.begin(), hits.end(), [](const Hit& a, const Hit& b) { return a.output != b.output ? a.output < b.output : a.ivk < b.ivk; });
     {
         std::lock_guard<std::mutex> g(ctx->slot_mu);
         ctx->ns_last_ms[0] = ms[0];
         ctx->ns_last_ms[1] = ms[1];
     }
-    *n_hits = hits.size();
-    if (hits.size() > hit_capacity) return MASP_HIP_E_CAPACITY;   // nothing written: the caller comes back with room for *n_hits
-    for (size_t i = 0; i < hits.size(); ++i) {
-        hit_output[i] = hits[i].output;
-        hit_ivk[i] = hits[i].ivk;
-        memcpy(hit_keys + 32 * i, hits[i].key, 32);
-    }
-    return MASP_HIP_OK;
+    return scan_finish(hits, hit_capacity, hit_output, hit_ivk, hit_keys, 32, nullptr, n_hits);
 }
 
 int masp_hip_note_scan_configure(masp_hip_ctx* ctx, int signed_digits, int inversion) {

@@ -23,7 +23,7 @@
 #include "device/compact_note.hpp"
 #include "device/note_scan.hpp"
 #include "host/jubjub.h"
-#include "internal.h"
+#include "scan_host.h"
 #include "pedersen_table.h"
 
 using namespace masp;
@@ -128,20 +128,9 @@ __global__ __launch_bounds__(NSC_BLOCK2) void k_nsc_emit(const NscArgs a, int fr
     for (int j = 0; j < 8; ++j) d[21 + j] = st.msg[18 + j];
 }
 
-struct Hit {
-    uint32_t output, ivk;
-    uint8_t data[116];   // plaintext 84 | pk_d 32
-};
-
-struct ChunkInFlight {
-    size_t o0 = 0, n = 0;
-    int set = 0;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // before the upload, behind it, behind stage 1, behind stage 2
-};
-
 // enqueues one chunk of outputs on its stream: upload, decode, stage 1, stage 2, and the counts' way back
-int enqueue_chunk(masp_hip_ctx* ctx, ChunkInFlight& c, size_t n_ivk, const uint8_t* epks, const uint8_t* cmus, const uint8_t* encs, int lead,
-                  uint32_t* h_counts) {
+int enqueue_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, ScanSetHost<4>& h, size_t n_ivk, const uint8_t* epks, const uint8_t* cmus,
+                  const uint8_t* encs, int lead, uint32_t* h_counts) {
     masp_hip_ctx::NoteScanSet& b = ctx->ns[c.set];
     masp_hip_ctx::NoteScanCompactSet& x = ctx->nsc[c.set];
     hipStream_t s = ctx->streams.vk[c.set];
@@ -153,19 +142,18 @@ int enqueue_chunk(masp_hip_ctx* ctx, ChunkInFlight& c, size_t n_ivk, const uint8
         (rc = x.cand.reserve(sizeof(NscCand) * cap)) || (rc = x.state.reserve(sizeof(NscState) * cap)) || (rc = x.list.reserve(4 * cap)) ||
         (rc = x.hit_idx.reserve(8 * cap)) || (rc = x.hit_data.reserve(116 * cap)))
         return rc;
-    for (hipEvent_t& e : c.ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(c.ev[0], s));
+    if ((rc = h.create_events())) return rc;
+    HIP_TRY(hipEventRecord(h.ev[0], s));
     HIP_TRY(hipMemcpyAsync(b.epk.p, epks + 32 * c.o0, 32 * c.n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(x.cmu.p, cmus + 32 * c.o0, 32 * c.n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(x.enc.p, encs + NSC_ENC * c.o0, NSC_ENC * c.n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(x.count.p, 0, 5 * sizeof(uint32_t), s));
-    HIP_TRY(hipEventRecord(c.ev[1], s));
+    HIP_TRY(hipEventRecord(h.ev[1], s));
     launch_ns_decode(s, b.epk.p, n, b.status.p, b.pts.p);
     MASP_LAUNCH(k_nsc_trial, dim3(nb, (uint32_t)n_ivk), dim3(NS_BLOCK), 0, s, (const uint32_t*)ctx->ns_digits.p, (const JNiels*)b.pts.p,
                 (const uint8_t*)b.status.p, (const uint4*)b.epk.p, (const uint32_t*)x.enc.p, n, ctx->ns_inversion.load(), (uint32_t)lead,
                 x.count.p, (uint32_t)cap, (NscCand*)x.cand.p);
-    HIP_TRY(hipEventRecord(c.ev[2], s));
+    HIP_TRY(hipEventRecord(h.ev[2], s));
     NscArgs a;
     a.counts = x.count.p;
     a.cand = (const NscCand*)x.cand.p;
@@ -184,47 +172,8 @@ int enqueue_chunk(masp_hip_ctx* ctx, ChunkInFlight& c, size_t n_ivk, const uint8
     MASP_LAUNCH(k_nsc_commit, grid2, block2, 0, s, a);
     if (lead == 2) MASP_LAUNCH(k_nsc_esk, grid2, block2, 0, s, a);
     MASP_LAUNCH(k_nsc_emit, grid2, block2, 0, s, a, lead == 2 ? 3 : 2, (uint32_t)c.o0, (uint2*)x.hit_idx.p, (uint32_t*)x.hit_data.p);
-    HIP_TRY(hipEventRecord(c.ev[3], s));
+    HIP_TRY(hipEventRecord(h.ev[3], s));
     HIP_TRY(hipMemcpyAsync(h_counts, x.count.p, 5 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    return MASP_HIP_OK;
-}
-
-// waits for a chunk and takes its statuses and hits
-int collect_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, size_t n_ivk, int lead, const uint32_t* h_counts, uint8_t* epk_status,
-                  std::vector<Hit>& hits, size_t& candidates, double ms[3]) {
-    masp_hip_ctx::NoteScanSet& b = ctx->ns[c.set];
-    masp_hip_ctx::NoteScanCompactSet& x = ctx->nsc[c.set];
-    hipStream_t s = ctx->streams.vk[c.set];
-    HIP_TRY(hipStreamSynchronize(s));
-    if (launch_status() != MASP_HIP_OK) return MASP_HIP_E_HIP;   // a refused launch: the buffers mean nothing
-    const size_t nc = h_counts[0], nh = h_counts[lead == 2 ? 4 : 3];
-    if (nc > c.n * n_ivk || nh > nc) {
-        last_hip_error() = "compact note scan: a count beyond the chunk's pairs";
-        return MASP_HIP_E_HIP;
-    }
-    candidates += nc;
-    if (epk_status) HIP_TRY(hipMemcpyAsync(epk_status + c.o0, b.status.p, c.n, hipMemcpyDeviceToHost, s));
-    std::vector<uint32_t> idx(2 * nh);
-    std::vector<uint8_t> data(116 * nh);
-    if (nh) {
-        HIP_TRY(hipMemcpyAsync(idx.data(), x.hit_idx.p, 8 * nh, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(data.data(), x.hit_data.p, 116 * nh, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    for (size_t i = 0; i < nh; ++i) {
-        Hit h;
-        h.output = idx[2 * i];
-        h.ivk = idx[2 * i + 1];
-        memcpy(h.data, &data[116 * i], 116);
-        hits.push_back(h);
-    }
-    float up = 0, k1 = 0, k2 = 0;
-    HIP_TRY(hipEventElapsedTime(&up, c.ev[0], c.ev[1]));
-    HIP_TRY(hipEventElapsedTime(&k1, c.ev[1], c.ev[2]));
-    HIP_TRY(hipEventElapsedTime(&k2, c.ev[2], c.ev[3]));
-    ms[0] += up;
-    ms[1] += k1;
-    ms[2] += k2;
     return MASP_HIP_OK;
 }
 
@@ -263,57 +212,36 @@ int masp_hip_sapling_compact_trial_decrypt(masp_hip_ctx* ctx, size_t n_ivk, cons
         ctx->nsc_table.release();
         return fail(ctx, MASP_HIP_E_HIP);
     }
-    // Chunks of outputs, alternately on the two verifier streams with a buffer set each: a chunk's upload and stage 1 run beside the thin
-    // stage 2 of the chunk before.
-    size_t per = std::max<size_t>(NS_BLOCK, NS_CHUNK_PAIRS / n_ivk / NS_BLOCK * NS_BLOCK);
-    std::vector<Hit> hits;
+    // chunks of outputs, alternately on the two verifier streams with a buffer set each (chunk_pipeline.h): a chunk's upload and stage 1
+    // run beside the thin stage 2 of the chunk before
+    ScanSetHost<4> host[2];   // events: before the upload, behind it, behind stage 1, behind stage 2
+    uint32_t h_counts[2][5] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};
+    std::vector<ScanHit<116>> hits;   // plaintext 84 | pk_d 32
     size_t candidates = 0;
     double ms[3] = {0, 0, 0};
-    ChunkInFlight fly[2];
-    uint32_t h_counts[2][5] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};
-    bool pending[2] = {false, false};
-    rc = MASP_HIP_OK;
-    int set = 0;
-    for (size_t o0 = 0; o0 < n_out && !rc; o0 += per, set ^= 1) {
-        if (pending[set]) {   // the set's previous chunk, two chunks back
-            rc = collect_chunk(ctx, fly[set], n_ivk, lead_byte, h_counts[set], epk_status, hits, candidates, ms);
-            pending[set] = false;
-            if (rc) break;
-        }
-        fly[set].o0 = o0;
-        fly[set].n = std::min(per, n_out - o0);
-        fly[set].set = set;
-        rc = enqueue_chunk(ctx, fly[set], n_ivk, epks, cmus, enc_compact, lead_byte, h_counts[set]);
-        pending[set] = rc == MASP_HIP_OK;
-    }
-    for (int i = 0; i < 2; ++i) {   // (set: the older of the two first)
-        const int s2 = set ^ i;
-        if (!pending[s2]) continue;
-        if (!rc)
-            rc = collect_chunk(ctx, fly[s2], n_ivk, lead_byte, h_counts[s2], epk_status, hits, candidates, ms);
-        else
-            (void)hipStreamSynchronize(ctx->streams.vk[s2]);   // nothing of this call stays in flight
-    }
-    for (ChunkInFlight& c : fly)
-        for (hipEvent_t e : c.ev)
-            if (e) (void)hipEventDestroy(e);
+    rc = run_chunks(
+        n_out, chunk_outputs(n_ivk),
+        [&](const ChunkInFlight& c) { return enqueue_chunk(ctx, c, host[c.set], n_ivk, epks, cmus, enc_compact, lead_byte, h_counts[c.set]); },
+        [&](const ChunkInFlight& c) {
+            const masp_hip_ctx::NoteScanCompactSet& x = ctx->nsc[c.set];
+            auto count = [&](size_t& nh) {   // the candidates of stage 1, of them the survivors of stage 2
+                const size_t nc = h_counts[c.set][0];
+                nh = h_counts[c.set][lead_byte == 2 ? 4 : 3];
+                if (nc > c.n * n_ivk || nh > nc) return false;
+                candidates += nc;
+                return true;
+            };
+            return scan_collect(ctx->streams.vk[c.set], c, host[c.set], count, "compact note scan: a count beyond the chunk's pairs", epk_status,
+                                ctx->ns[c.set].status.p, x.hit_idx.p, x.hit_data.p, hits, ms);
+        },
+        [&](int set) { (void)hipStreamSynchronize(ctx->streams.vk[set]); });
     if (rc) return fail(ctx, rc);
-    // the order lanes reached the counters in is not an order: by (output, ivk)
-    std::sort(hits.begin(), hits.end(), [](const Hit& a, const Hit& b) { return a.output != b.output ? a.output < b.output : a.ivk < b.ivk; });
     {
         std::lock_guard<std::mutex> g(ctx->slot_mu);
         for (int i = 0; i < 3; ++i) ctx->nsc_last_ms[i] = ms[i];
     }
-    *n_hits = hits.size();
     if (n_candidates) *n_candidates = candidates;
-    if (hits.size() > hit_capacity) return MASP_HIP_E_CAPACITY;   // nothing written: the caller comes back with room for *n_hits
-    for (size_t i = 0; i < hits.size(); ++i) {
-        hit_output[i] = hits[i].output;
-        hit_ivk[i] = hits[i].ivk;
-        memcpy(hit_plaintexts + 84 * i, hits[i].data, 84);
-        memcpy(hit_pk_d + 32 * i, hits[i].data + 84, 32);
-    }
-    return MASP_HIP_OK;
+    return scan_finish(hits, hit_capacity, hit_output, hit_ivk, hit_plaintexts, 84, hit_pk_d, n_hits);
 }
 
 int masp_hip_note_scan_compact_last_timing(masp_hip_ctx* ctx, double ms[3]) {

@@ -14,7 +14,7 @@
 #include <mutex>
 
 #include "device/out_recovery.hpp"
-#include "internal.h"
+#include "scan_host.h"
 
 using namespace masp;
 
@@ -56,23 +56,12 @@ __global__ __launch_bounds__(NS_BLOCK) void k_or_trial(const uint32_t* __restric
     hit_ocks[2 * slot + 1] = make_uint4(ock[4], ock[5], ock[6], ock[7]);
 }
 
-struct Hit {
-    uint32_t output, ovk;
-    uint8_t ock[32];
-};
-
-struct ChunkInFlight {
-    size_t o0 = 0, n = 0;
-    int set = 0;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // before the upload, behind it, behind the kernels
-};
-
 struct Rows {
     const uint8_t *cvs, *epks, *cmus, *couts;
 };
 
 // enqueues one chunk of outputs on its stream: upload, repitch, trials, and the count's way back
-int enqueue_chunk(masp_hip_ctx* ctx, ChunkInFlight& c, size_t n_ovk, const Rows& r, uint32_t* h_count) {
+int enqueue_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, ScanSetHost<3>& h, size_t n_ovk, const Rows& r, uint32_t* h_count) {
     masp_hip_ctx::OutRecoverySet& b = ctx->orc[c.set];
     hipStream_t s = ctx->streams.vk[c.set];
     const uint32_t n = (uint32_t)c.n, nb = (n + NS_BLOCK - 1) / NS_BLOCK, n_pad = nb * NS_BLOCK;
@@ -82,54 +71,20 @@ int enqueue_chunk(masp_hip_ctx* ctx, ChunkInFlight& c, size_t n_ovk, const Rows&
         (rc = b.cout.reserve(OR_OUT * (size_t)n_pad)) || (rc = b.cols.reserve(16 * (size_t)OR_COLS * n_pad)) || (rc = b.count.reserve(1)) ||
         (rc = b.hit_idx.reserve(2 * cap)) || (rc = b.hit_ocks.reserve(32 * cap)))
         return rc;
-    for (hipEvent_t& e : c.ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(c.ev[0], s));
+    if ((rc = h.create_events())) return rc;
+    HIP_TRY(hipEventRecord(h.ev[0], s));
     HIP_TRY(hipMemcpyAsync(b.cv.p, r.cvs + 32 * c.o0, 32 * c.n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(b.cmu.p, r.cmus + 32 * c.o0, 32 * c.n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(b.epk.p, r.epks + 32 * c.o0, 32 * c.n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(b.cout.p, r.couts + OR_OUT * c.o0, OR_OUT * c.n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(b.count.p, 0, sizeof(uint32_t), s));
-    HIP_TRY(hipEventRecord(c.ev[1], s));
+    HIP_TRY(hipEventRecord(h.ev[1], s));
     MASP_LAUNCH(k_or_repitch, dim3(nb, OR_COLS), dim3(NS_BLOCK), 0, s, (const uint4*)b.cv.p, (const uint4*)b.cmu.p, (const uint4*)b.epk.p,
                 (const uint4*)b.cout.p, n, n_pad, (uint4*)b.cols.p);
     MASP_LAUNCH(k_or_trial, dim3(nb, (uint32_t)n_ovk), dim3(NS_BLOCK), 0, s, (const uint32_t*)ctx->orc_ovks.p, (const uint4*)b.cols.p, n, n_pad,
                 (uint32_t)c.o0, b.count.p, (uint32_t)cap, (uint2*)b.hit_idx.p, (uint4*)b.hit_ocks.p);
-    HIP_TRY(hipEventRecord(c.ev[2], s));
+    HIP_TRY(hipEventRecord(h.ev[2], s));
     HIP_TRY(hipMemcpyAsync(h_count, b.count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    return MASP_HIP_OK;
-}
-
-// waits for a chunk and takes its hits
-int collect_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, size_t n_ovk, const uint32_t* h_count, std::vector<Hit>& hits, double ms[2]) {
-    masp_hip_ctx::OutRecoverySet& b = ctx->orc[c.set];
-    hipStream_t s = ctx->streams.vk[c.set];
-    HIP_TRY(hipStreamSynchronize(s));
-    if (launch_status() != MASP_HIP_OK) return MASP_HIP_E_HIP;   // a refused launch: the buffers mean nothing
-    const size_t nh = *h_count;
-    if (nh > c.n * n_ovk) {
-        last_hip_error() = "output recovery scan: hit count beyond the chunk's pairs";
-        return MASP_HIP_E_HIP;
-    }
-    std::vector<uint32_t> idx(2 * nh);
-    std::vector<uint8_t> ocks(32 * nh);
-    if (nh) {
-        HIP_TRY(hipMemcpyAsync(idx.data(), b.hit_idx.p, 8 * nh, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(ocks.data(), b.hit_ocks.p, 32 * nh, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    for (size_t i = 0; i < nh; ++i) {
-        Hit h;
-        h.output = idx[2 * i];
-        h.ovk = idx[2 * i + 1];
-        memcpy(h.ock, &ocks[32 * i], 32);
-        hits.push_back(h);
-    }
-    float up = 0, kern = 0;
-    HIP_TRY(hipEventElapsedTime(&up, c.ev[0], c.ev[1]));
-    HIP_TRY(hipEventElapsedTime(&kern, c.ev[1], c.ev[2]));
-    ms[0] += up;
-    ms[1] += kern;
     return MASP_HIP_OK;
 }
 
@@ -158,55 +113,29 @@ int masp_hip_sapling_output_recovery_scan(masp_hip_ctx* ctx, size_t n_ovk, const
         last_hip_error() = std::string("output recovery scan: upload failed: ") + hipGetErrorString(hipGetLastError());
         return fail(ctx, MASP_HIP_E_HIP);
     }
-    // Chunks of outputs, alternately on the two verifier streams with a buffer set each: a chunk's upload runs beside the chunk before's kernels.
-    const size_t per = std::max<size_t>(NS_BLOCK, NS_CHUNK_PAIRS / n_ovk / NS_BLOCK * NS_BLOCK);
+    // chunks of outputs, alternately on the two verifier streams with a buffer set each (chunk_pipeline.h)
     const Rows rows = {cvs, epks, cmus, out_ciphertexts};
-    std::vector<Hit> hits;
-    double ms[2] = {0, 0};
-    ChunkInFlight fly[2];
+    ScanSetHost<3> host[2];   // events: before the upload, behind it, behind the kernels
     uint32_t h_count[2] = {0, 0};
-    bool pending[2] = {false, false};
-    rc = MASP_HIP_OK;
-    int set = 0;
-    for (size_t o0 = 0; o0 < n_out && !rc; o0 += per, set ^= 1) {
-        if (pending[set]) {   // the set's previous chunk, two chunks back
-            rc = collect_chunk(ctx, fly[set], n_ovk, &h_count[set], hits, ms);
-            pending[set] = false;
-            if (rc) break;
-        }
-        fly[set].o0 = o0;
-        fly[set].n = std::min(per, n_out - o0);
-        fly[set].set = set;
-        rc = enqueue_chunk(ctx, fly[set], n_ovk, rows, &h_count[set]);
-        pending[set] = rc == MASP_HIP_OK;
-    }
-    for (int i = 0; i < 2; ++i) {   // (set: the older of the two first)
-        const int s2 = set ^ i;
-        if (!pending[s2]) continue;
-        if (!rc)
-            rc = collect_chunk(ctx, fly[s2], n_ovk, &h_count[s2], hits, ms);
-        else
-            (void)hipStreamSynchronize(ctx->streams.vk[s2]);   // nothing of this call stays in flight
-    }
-    for (ChunkInFlight& c : fly)
-        for (hipEvent_t e : c.ev)
-            if (e) (void)hipEventDestroy(e);
+    std::vector<ScanHit<32>> hits;
+    double ms[2] = {0, 0};
+    rc = run_chunks(
+        n_out, chunk_outputs(n_ovk),
+        [&](const ChunkInFlight& c) { return enqueue_chunk(ctx, c, host[c.set], n_ovk, rows, &h_count[c.set]); },
+        [&](const ChunkInFlight& c) {
+            const masp_hip_ctx::OutRecoverySet& b = ctx->orc[c.set];
+            return scan_collect(
+                ctx->streams.vk[c.set], c, host[c.set], [&](size_t& nh) { return (nh = h_count[c.set]) <= c.n * n_ovk; },
+                "output recovery scan: hit count beyond the chunk's pairs", nullptr, nullptr, b.hit_idx.p, b.hit_ocks.p, hits, ms);
+        },
+        [&](int set) { (void)hipStreamSynchronize(ctx->streams.vk[set]); });
     if (rc) return fail(ctx, rc);
-    // the order lanes reached the counter in is not an order: by (output, ovk)
-    std::sort(hits.begin(), hits.end(), [](const Hit& a, const Hit& b) { return a.output != b.output ? a.output < b.output : a.ovk < b.ovk; });
     {
         std::lock_guard<std::mutex> g(ctx->slot_mu);
         ctx->orc_last_ms[0] = ms[0];
         ctx->orc_last_ms[1] = ms[1];
     }
-    *n_hits = hits.size();
-    if (hits.size() > hit_capacity) return MASP_HIP_E_CAPACITY;   // nothing written: the caller comes back with room for *n_hits
-    for (size_t i = 0; i < hits.size(); ++i) {
-        hit_output[i] = hits[i].output;
-        hit_ovk[i] = hits[i].ovk;
-        memcpy(hit_ocks + 32 * i, hits[i].ock, 32);
-    }
-    return MASP_HIP_OK;
+    return scan_finish(hits, hit_capacity, hit_output, hit_ovk, hit_ocks, 32, nullptr, n_hits);
 }
 
 int masp_hip_out_recovery_last_timing(masp_hip_ctx* ctx, double ms[2]) {

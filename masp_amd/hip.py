@@ -386,6 +386,25 @@ class Context:
         return out.tobytes()
 
     # ---- batch trial decryption of Sapling notes on the GPU ----
+    def _scan_with_room(self, fn, args, widths, n_out, hit_capacity, tail=()):
+        """One output scan fn(ctx, *args, capacity, hit_output, hit_key, <an array of uint8[w] rows per w of widths>, &n_hits, *tail) with
+        room for its hits: too little of it (E_CAPACITY) raises MaspHipError with `.needed` if hit_capacity was given, else the call is
+        repeated with the room it asked for.  -> the hit arrays, cut to the hits."""
+        cap = max(16, n_out // 64) if hit_capacity is None else int(hit_capacity)
+        while True:
+            hits = [np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)] + [np.zeros((cap, w), np.uint8) for w in widths]
+            nh = C.c_size_t(0)
+            rc = fn(self._h, *args, cap, *[_p(h) for h in hits], C.byref(nh), *tail)
+            if rc == E_CAPACITY and hit_capacity is None:
+                cap = nh.value
+                continue
+            if rc == E_CAPACITY:
+                e = MaspHipError(rc, "%d hits" % nh.value)
+                e.needed = nh.value
+                raise e
+            self._check(rc)
+            return [h[:nh.value] for h in hits]
+
     def sapling_trial_decrypt(self, ivks, epks, enc_ciphertexts, hit_capacity=None):
         """The device half of batch::try_note_decryption (masp_hip_sapling_trial_decrypt): ivks n_ivk x 32, epks n_out x 32, enc_ciphertexts
         n_out x 612 (bytes or uint8 arrays) -> (epk_status uint8[n_out], hit_output uint32[h], hit_ivk uint32[h], hit_keys uint8[h, 32]): the
@@ -395,21 +414,9 @@ class Context:
         n_ivk, n_out = ivks.shape[0], epks.shape[0]
         assert encs.shape[0] == n_out
         status = np.zeros(n_out, dtype=np.uint8)
-        cap = max(16, n_out // 64) if hit_capacity is None else int(hit_capacity)
-        while True:
-            ho, hi, hk = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros((cap, 32), np.uint8)
-            nh = C.c_size_t(0)
-            rc = self._L.masp_hip_sapling_trial_decrypt(self._h, n_ivk, _p(ivks), n_out, _p(epks), _p(encs), _p(status), cap, _p(ho), _p(hi),
-                                                        _p(hk), C.byref(nh))
-            if rc == E_CAPACITY and hit_capacity is None:
-                cap = nh.value
-                continue
-            if rc == E_CAPACITY:
-                e = MaspHipError(rc, "%d hits" % nh.value)
-                e.needed = nh.value
-                raise e
-            self._check(rc)
-            return status, ho[:nh.value], hi[:nh.value], hk[:nh.value]
+        ho, hi, hk = self._scan_with_room(self._L.masp_hip_sapling_trial_decrypt, (n_ivk, _p(ivks), n_out, _p(epks), _p(encs), _p(status)), (32,),
+                                          n_out, hit_capacity)
+        return status, ho, hi, hk
 
     def note_scan_configure(self, signed_digits=1, inversion=0):
         """measurement knobs of the note scan (masp_hip_note_scan_configure); results do not depend on them"""
@@ -430,23 +437,11 @@ class Context:
         n_ivk, n_out = ivks.shape[0], epks.shape[0]
         assert encs.shape[0] == n_out and cmus.shape[0] == n_out
         status = np.zeros(n_out, dtype=np.uint8)
-        cap = max(16, n_out // 64) if hit_capacity is None else int(hit_capacity)
-        while True:
-            ho, hi = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
-            hp, hk = np.zeros((cap, 84), np.uint8), np.zeros((cap, 32), np.uint8)
-            nh, nc = C.c_size_t(0), C.c_size_t(0)
-            rc = self._L.masp_hip_sapling_compact_trial_decrypt(self._h, n_ivk, _p(ivks), n_out, _p(epks), _p(cmus), _p(encs), int(lead_byte),
-                                                                _p(status), cap, _p(ho), _p(hi), _p(hp), _p(hk), C.byref(nh),
-                                                                C.byref(nc) if count_candidates else None)
-            if rc == E_CAPACITY and hit_capacity is None:
-                cap = nh.value
-                continue
-            if rc == E_CAPACITY:
-                e = MaspHipError(rc, "%d hits" % nh.value)
-                e.needed = nh.value
-                raise e
-            self._check(rc)
-            return status, ho[:nh.value], hi[:nh.value], hp[:nh.value], hk[:nh.value], (nc.value if count_candidates else None)
+        nc = C.c_size_t(0)
+        ho, hi, hp, hk = self._scan_with_room(self._L.masp_hip_sapling_compact_trial_decrypt,
+                                              (n_ivk, _p(ivks), n_out, _p(epks), _p(cmus), _p(encs), int(lead_byte), _p(status)), (84, 32), n_out,
+                                              hit_capacity, tail=(C.byref(nc) if count_candidates else None,))
+        return status, ho, hi, hp, hk, (nc.value if count_candidates else None)
 
     def note_scan_compact_last_timing(self):
         """(upload ms, stage 1 ms, stage 2 ms) of the last compact scan, HIP events summed over its chunks"""
@@ -463,21 +458,8 @@ class Context:
         ovks, cvs, epks, cmus, couts = _u8(ovks, 32), _u8(cvs, 32), _u8(epks, 32), _u8(cmus, 32), _u8(c_outs, 80)
         n_ovk, n_out = ovks.shape[0], epks.shape[0]
         assert cvs.shape[0] == n_out and cmus.shape[0] == n_out and couts.shape[0] == n_out
-        cap = max(16, n_out // 64) if hit_capacity is None else int(hit_capacity)
-        while True:
-            ho, hi, hk = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros((cap, 32), np.uint8)
-            nh = C.c_size_t(0)
-            rc = self._L.masp_hip_sapling_output_recovery_scan(self._h, n_ovk, _p(ovks), n_out, _p(cvs), _p(epks), _p(cmus), _p(couts), cap,
-                                                               _p(ho), _p(hi), _p(hk), C.byref(nh))
-            if rc == E_CAPACITY and hit_capacity is None:
-                cap = nh.value
-                continue
-            if rc == E_CAPACITY:
-                e = MaspHipError(rc, "%d hits" % nh.value)
-                e.needed = nh.value
-                raise e
-            self._check(rc)
-            return ho[:nh.value], hi[:nh.value], hk[:nh.value]
+        return tuple(self._scan_with_room(self._L.masp_hip_sapling_output_recovery_scan,
+                                          (n_ovk, _p(ovks), n_out, _p(cvs), _p(epks), _p(cmus), _p(couts)), (32,), n_out, hit_capacity))
 
     def out_recovery_last_timing(self):
         """(upload ms, kernel ms) of the last output recovery scan, HIP events summed over its chunks"""

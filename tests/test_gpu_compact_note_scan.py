@@ -111,6 +111,16 @@ def test_scan_over_several_chunks(ctx):
     assert cand > len(places)
 
 
+@pytest.mark.parametrize("n", [2 * 8192, 3 * 8192 + 1])
+def test_scan_ends_on_a_chunk_boundary_or_one_output_behind_it(ctx, n):
+    """32 ivks, 8 192 outputs per chunk.  16 384 outputs: the call ends exactly where the second chunk does, no empty third one.  24 577: four
+    chunks, both buffer sets used twice, the last chunk a single output.  Notes at every chunk's first and last output; the statuses of every
+    output and the hits (the planted pairs with their plaintexts and pk_d, and no other pair)"""
+    places = sorted({0, 8191, 8192, n - 1} | ({16383, 16384, 24575, 24576} if n > 3 * 8192 else set()))
+    cand = _scan(ctx, n, 32, places, 46, against_host=False)
+    assert cand > len(places)
+
+
 def test_every_pair_a_candidate_and_a_hit(ctx):
     rng = random.Random(43)
     ivk, other = rng.randrange(1, RJ), rng.randrange(1, RJ)

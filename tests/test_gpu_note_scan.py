@@ -101,7 +101,7 @@ def test_the_vectors_as_one_call(ctx):
         ctx.note_scan_configure(1, 0)      # the defaults
 
 
-def _scan(ctx, n, n_ivk, places, seed):
+def _scan(ctx, n, n_ivk, places, seed, against_host=True):
     rng = random.Random(seed)
     ivks_int = [rng.randrange(1, RJ) for _ in range(n_ivk)]
     ivks = [k.to_bytes(32, "little") for k in ivks_int]
@@ -118,6 +118,8 @@ def _scan(ctx, n, n_ivk, places, seed):
     assert 0 < sum(1 for s in status.tolist() if s) < n            # both kinds are in the batch
     # the raw hits: the planted pairs, no other pair, sorted, each with the host's key
     assert list(zip(ho.tolist(), hi.tolist(), (k.tobytes() for k in hk))) == want_pairs
+    if not against_host:
+        return ivks, epks, cmus, encs
     # the whole result list against the host path over every pair
     want = host_result(ivks, epks, cmus, encs, 2)
     assert [i for i, w in enumerate(want) if w is not None] == sorted(places)
@@ -138,6 +140,16 @@ def test_scan_over_several_chunks(ctx):
     places = [0, 8191, 8192, 8193, 16383, 16384, n - 1] + random.Random(32).sample(range(100, 16000), 33)
     assert len(set(places)) == len(places)
     _scan(ctx, n, 32, places, 42)
+
+
+@pytest.mark.parametrize("n", [2 * 8192, 3 * 8192 + 1])
+def test_scan_ends_on_a_chunk_boundary_or_one_output_behind_it(ctx, n):
+    """32 ivks, 8 192 outputs per chunk.  16 384 outputs: the call ends exactly where the second chunk does, no empty third one.  24 577: four
+    chunks, both buffer sets used twice, the last chunk a single output.  Notes at every chunk's first and last output; the statuses of every
+    output and the raw hits (the planted pairs with the host's keys, and no other pair; the host path over all 786 464 pairs is left to the
+    smaller tests)"""
+    places = sorted({0, 8191, 8192, n - 1} | ({16383, 16384, 24575, 24576} if n > 3 * 8192 else set()))
+    _scan(ctx, n, 32, places, 46, against_host=False)
 
 
 def test_every_pair_a_hit(ctx):

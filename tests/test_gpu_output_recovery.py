@@ -73,7 +73,7 @@ def test_the_vectors_as_one_call(ctx):
     assert NE.batch.try_output_recovery(ovks, outs, ctx, lead_byte=2) == [None] * 10
 
 
-def _scan(ctx, n, n_ovk, places, seed):
+def _scan(ctx, n, n_ovk, places, seed, against_host=True):
     rng = random.Random(seed)
     ovks = [rng.randbytes(32) for _ in range(n_ovk)]
     rows = noise(n, seed)
@@ -86,6 +86,8 @@ def _scan(ctx, n, n_ovk, places, seed):
     want_pairs.sort()
     # the raw hits: the planted pairs, no other pair, sorted, each with the host's ock
     assert scan(ctx, ovks, rows) == want_pairs
+    if not against_host:
+        return
     # the whole result list against the host path over every pair
     want = host_result(ovks, rows, 2)
     assert [i for i, w in enumerate(want) if w is not None] == sorted(places)
@@ -107,6 +109,15 @@ def test_scan_over_several_chunks(ctx):
     places = [0, 8191, 8192, 8193, 16383, 16384, n - 1] + random.Random(52).sample(range(100, 16000), 9)
     assert len(set(places)) == len(places)
     _scan(ctx, n, 32, places, 62)
+
+
+@pytest.mark.parametrize("n", [2 * 8192, 3 * 8192 + 1])
+def test_scan_ends_on_a_chunk_boundary_or_one_output_behind_it(ctx, n):
+    """32 ovks, 8 192 outputs per chunk.  16 384 outputs: the call ends exactly where the second chunk does, no empty third one.  24 577: four
+    chunks, both buffer sets used twice, the last chunk a single output.  Notes at every chunk's first and last output; the raw hits (the
+    planted pairs with the host's ocks, and no other pair; the host path over all 786 464 pairs is left to the smaller tests)"""
+    places = sorted({0, 8191, 8192, n - 1} | ({16383, 16384, 24575, 24576} if n > 3 * 8192 else set()))
+    _scan(ctx, n, 32, places, 66, against_host=False)
 
 
 def test_every_pair_a_hit(ctx):
