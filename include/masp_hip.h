@@ -397,6 +397,21 @@ int masp_hip_merkle_tree_complete(masp_hip_ctx* ctx, unsigned height0, size_t n,
                                   size_t* n_nodes, uint8_t root32[32], size_t n_paths, const uint64_t* positions, uint8_t* paths_out,
                                   int64_t* bad_index);
 int masp_hip_merkle_last_timing(masp_hip_ctx* ctx, double ms[3]);
+/* masp_hip_merkle_tree_append - a block of leaves at an arbitrary offset of the depth-32 tree: what advances a CommitmentTree and its
+ * IncrementalWitnesses (masp_primitives/src/merkle_tree.rs:271-723) by that block with one call instead of one hash chain per leaf and
+ * witness.  row: n x 32, the leaves at positions start .. start + n - 1, canonical encodings; start even or odd, start + n <= 2^32,
+ * n <= 2^22.  frontier: 32 x 32 bytes, entry h the node (level h, index (start >> h) - 1), the root of the complete 2^h-leaf subtree that
+ * ends just before start; entry h is read, and has to be canonical, only where bit h of start is set, the others are ignored (frontier may
+ * be NULL with start = 0).
+ * nodes_out: level by level for h = 1 .. 32 the nodes (h, i) with start >> h <= i < (start + n) >> h, 32 bytes each: exactly the complete
+ * nodes whose last leaf lies in the block, nothing padded.  *n_nodes (may be NULL) is their number, fewer than n + 32.  nodes_out NULL:
+ * *n_nodes alone, no GPU work.  nodes_capacity < *n_nodes: MASP_HIP_E_CAPACITY, nothing written.
+ * A node that is not canonical: MASP_HIP_E_INVALID_ARG with *bad_index (may be NULL) = -2 - h for the lowest used frontier entry h, else
+ * the smallest such index of the row; nothing is written and the context stays usable.  *bad_index is -1 otherwise.
+ * Deterministic; same stream, lock, table and scratch as the frozen tree's call, and masp_hip_merkle_last_timing reports the last call of
+ * either kind.  masp_host_merkle_tree_append (include/masp_host.h) is the same on the host. */
+int masp_hip_merkle_tree_append(masp_hip_ctx* ctx, uint64_t start, const uint8_t frontier[32 * 32], size_t n, const uint8_t* row,
+                                uint8_t* nodes_out, size_t nodes_capacity, size_t* n_nodes, int64_t* bad_index);
 
 /* ---- measurement hooks (bench.py): device-resident workloads, HIP-event timing on the ctx stream ---- */
 /* Keeps `n` jobs' assignments resident in HBM; returns a handle (>= 0) or a negative error code. */

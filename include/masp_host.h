@@ -120,6 +120,10 @@ void masp_host_merkle_empty_roots(uint8_t out[33 * 32]);
 int masp_host_merkle_tree_complete(unsigned height0, size_t n, const uint8_t* row, uint8_t* nodes_out, size_t nodes_capacity, size_t* n_nodes,
                                    uint8_t root32[32], size_t n_paths, const uint64_t* positions, uint8_t* paths_out, int64_t* bad_index,
                                    int threads);
+/* A block of n leaves at position `start` of the depth-32 tree against the old frontier: the arguments and results of
+ * masp_hip_merkle_tree_append (include/masp_hip.h) without the context and with the number of host threads a level's parents are dealt to. */
+int masp_host_merkle_tree_append(uint64_t start, const uint8_t frontier[32 * 32], size_t n, const uint8_t* row, uint8_t* nodes_out,
+                                 size_t nodes_capacity, size_t* n_nodes, int64_t* bad_index, int threads);
 int masp_host_jubjub_mul(const uint8_t p32[32], const uint8_t k32[32], uint8_t out32[32]);
 int masp_host_point_uv(const uint8_t p32[32], uint8_t out64[64]);
 int masp_host_jubjub_add(const uint8_t p32[32], const uint8_t q32[32], int subtract, uint8_t out32[32]);

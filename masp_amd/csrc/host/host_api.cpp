@@ -735,6 +735,60 @@ int masp_host_merkle_tree_complete(unsigned height0, size_t n, const uint8_t* ro
     }
     return MASP_HOST_OK;
 }
+// A block of n leaves at `start` of the depth-32 tree: level by level the complete nodes whose last leaf lies in the block, the first
+// parent's left child out of the old frontier where the level starts at an odd index; what masp_hip_merkle_tree_append computes
+int masp_host_merkle_tree_append(uint64_t start, const uint8_t frontier[32 * 32], size_t n, const uint8_t* row, uint8_t* nodes_out,
+                                 size_t nodes_capacity, size_t* n_nodes, int64_t* bad_index, int threads) {
+    if (bad_index) *bad_index = -1;
+    const uint64_t full = (uint64_t)1 << 32, end = start + n;
+    if (start > full || n > ((size_t)1 << 22) || end > full || (n && !row) || (n && start && !frontier)) return MASP_HOST_E_INVALID;
+    size_t total = 0;
+    for (unsigned h = 1; h <= 32; ++h) total += (size_t)((end >> h) - (start >> h));
+    if (n_nodes) *n_nodes = total;
+    if (!nodes_out) return MASP_HOST_OK;   // the count alone
+    if (nodes_capacity < total) return MASP_HOST_E_CAPACITY;
+    if (n == 0) return MASP_HOST_OK;
+    Fr x;
+    for (unsigned h = 0; h < 32; ++h)
+        if (((start >> h) & 1) && !Fr::from_bytes(x, frontier + 32 * h)) {
+            if (bad_index) *bad_index = -2 - (int64_t)h;
+            return MASP_HOST_E_INVALID;
+        }
+    for (size_t i = 0; i < n; ++i)
+        if (!Fr::from_bytes(x, row + 32 * i)) {
+            if (bad_index) *bad_index = (int64_t)i;
+            return MASP_HOST_E_INVALID;
+        }
+    (void)pedersen_windows();   // the lazily built table, before the threads race for it
+    const int nt = std::max(1, std::min<int>(threads, 256));
+    const uint8_t* src = row;
+    uint8_t* dst = nodes_out;   // (every refusal is behind us)
+    for (unsigned level = 0; level < 32; ++level) {
+        const uint64_t c0 = start >> level, c1 = end >> level;
+        const size_t parents = (size_t)((c1 >> 1) - (c0 >> 1)), odd = (size_t)(c0 & 1);
+        if (!parents) break;   // (and none above)
+        std::atomic<size_t> next{0};
+        auto work = [&] {
+            for (;;) {
+                const size_t t0 = next.fetch_add(16);
+                if (t0 >= parents) return;
+                for (size_t t = t0; t < std::min(parents, t0 + 16); ++t) {
+                    const uint8_t* r = src + 32 * (2 * t + 1 - odd);
+                    const uint8_t* l = (odd && t == 0) ? frontier + 32 * level : r - 32;
+                    merkle_hash_bytes(level, l, r).to_bytes(dst + 32 * t);
+                }
+            }
+        };
+        std::vector<std::thread> pool;
+        if (parents >= 64)   // (a narrow level is not worth the threads' start)
+            for (int k = 1; k < nt; ++k) pool.emplace_back(work);
+        work();
+        for (auto& th : pool) th.join();
+        src = dst;
+        dst += 32 * parents;
+    }
+    return MASP_HOST_OK;
+}
 // [k]P for P given as 32 bytes; (point decode / scalar multiplication / encode round trip)
 int masp_host_jubjub_mul(const uint8_t p32[32], const uint8_t k32[32], uint8_t out32[32]) {
     JPoint p;

@@ -9,6 +9,11 @@
 //                           compact scan uses, the parent's 32 canonical bytes into the next row's place.  One launch per row, on one stream.
 //           k_mt_top        rows of at most MT_TOP_PARENTS parents: one wave loops over the remaining levels up to 32 in one launch.
 //           k_mt_paths      one lane per (position, level): the sibling out of the node vector.
+// masp_hip_merkle_tree_append hashes a block of leaves at an arbitrary offset of the depth-32 tree instead: the complete nodes whose last
+// leaf lies in the block, which is all that a CommitmentTree and its IncrementalWitnesses need to advance by that block.
+//           k_mt_append_level  one lane per parent of a level of the block; the first parent's left child is the old frontier's node of
+//                              that level where the block starts at an odd index there.  No padding: an unpaired last node has no parent.
+//           k_mt_append_top    at most MT_TOP_PARENTS parents: one wave loops up to level 32, the carry chain against the frontier included.
 // Why the table is read from global memory, the inversion is one per lane and the hand-over is at one wave: KERNELS.md.
 #include <mutex>
 
@@ -93,6 +98,58 @@ __global__ __launch_bounds__(MT_BLOCK) void k_mt_paths(const uint32_t* __restric
     dst[1] = src[1];
 }
 
+// ---- a block appended at an arbitrary offset (masp_hip_merkle_tree_append) ----
+// The buffer: frontier[0..32) | the row, leaves start .. end - 1 | level 1 | ... | level 32, level h being the nodes (h, i) for
+// start >> h <= i < end >> h, the complete nodes whose last leaf is in the block.  Nothing is padded: an unpaired last node has no parent.
+constexpr uint64_t MT_APPEND_ROW = MT_DEPTH;   // the row's first node in the buffer, behind the frontier
+
+// parent t of one level: its children are nodes of `level` from nodes[src] on, the first of them node (level, c0).  c0 odd: that node is a
+// RIGHT child, and its parent's left child is frontier[level], the complete subtree that ends just before the block.
+__device__ __forceinline__ void mt_append_parent(uint32_t* nodes, const JNiels* __restrict__ table, uint64_t src, uint64_t dst, uint32_t odd,
+                                                 uint32_t level, uint32_t t) {
+    const uint4* row = (const uint4*)nodes + 2 * src;
+    const size_t ri = 2 * (size_t)t + 1 - odd;   // the right child's place in the row; the left one is in front of it, or is the frontier's
+    const uint4* lp = (odd && t == 0) ? (const uint4*)nodes + 2 * level : row + 2 * (ri - 1);
+    const uint4 a = lp[0], b = lp[1], c = row[2 * ri], d = row[2 * ri + 1];
+    const uint32_t l[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}, r[8] = {c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w};
+    uint32_t out[8];
+    merkle_combine(out, table, level, l, r);
+    uint4* o = (uint4*)nodes + 2 * (dst + t);
+    o[0] = make_uint4(out[0], out[1], out[2], out[3]);
+    o[1] = make_uint4(out[4], out[5], out[6], out[7]);
+}
+
+__global__ __launch_bounds__(MT_BLOCK) void k_mt_append_level(uint32_t* nodes, const JNiels* __restrict__ table, const uint32_t* __restrict__ bad,
+                                                              uint64_t src, uint64_t dst, uint32_t parents, uint32_t odd, uint32_t level) {
+    const uint32_t t = blockIdx.x * MT_BLOCK + threadIdx.x;
+    if (t >= parents || *bad != MT_NO_BAD) return;
+    mt_append_parent(nodes, table, src, dst, odd, level, t);
+}
+
+// one workgroup of one wave, from a level of at most MT_TOP_PARENTS parents up to level 32: above log2(n) a level has at most one parent,
+// the carry chain against the frontier.  Every lane sees the same start, end and level: the loop and its barrier are uniform.
+__global__ __launch_bounds__(MT_TOP_PARENTS) void k_mt_append_top(uint32_t* nodes, const JNiels* __restrict__ table,
+                                                                  const uint32_t* __restrict__ bad, uint64_t start, uint64_t end, uint64_t src,
+                                                                  uint32_t level) {
+    if (*bad != MT_NO_BAD) return;   // (the whole workgroup)
+#pragma unroll 1
+    for (; level < MT_DEPTH; ++level) {
+        const uint64_t c0 = start >> level, c1 = end >> level;
+        const uint32_t width = (uint32_t)(c1 - c0), parents = (uint32_t)((c1 >> 1) - (c0 >> 1));
+        if (parents == 0) break;   // (and none above)
+        if (threadIdx.x < parents) mt_append_parent(nodes, table, src, src + width, (uint32_t)(c0 & 1u), level, threadIdx.x);
+        __syncthreads();
+        src += width;
+    }
+}
+
+// the nodes of levels 1..32 that a block of n leaves at `start` completes
+size_t mt_append_count(uint64_t start, uint64_t n) {
+    size_t total = 0;
+    for (uint32_t h = 1; h <= MT_DEPTH; ++h) total += (size_t)(((start + n) >> h) - (start >> h));
+    return total;
+}
+
 struct Events {
     hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
     ~Events() {
@@ -169,6 +226,66 @@ int run_tree(masp_hip_ctx* ctx, unsigned height0, size_t n, size_t total, const 
     return MASP_HIP_OK;
 }
 
+// a block of n >= 1 leaves at `start`, on the same stream and in the same scratch as run_tree; the caller holds ns_mu
+int run_append(masp_hip_ctx* ctx, uint64_t start, const uint8_t* frontier, size_t n, size_t total, const uint8_t* row, uint8_t* nodes_out,
+               int64_t* bad_index, bool& first_upload) {
+    hipStream_t s = ctx->streams.vk[0];
+    const uint64_t end = start + n;
+    int rc;
+    if ((rc = ctx->mt_nodes.reserve(8 * (MT_APPEND_ROW + n + total))) || (rc = ctx->mt_bad.reserve(1))) return rc;
+    Events ev;
+    for (hipEvent_t& e : ev.e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipEventRecord(ev.e[0], s));
+    first_upload = !ctx->nsc_table.p;
+    if ((rc = pedersen_table_ensure(ctx, s))) return rc;
+    uint32_t* nodes = ctx->mt_nodes.p;
+    HIP_TRY(hipMemcpyAsync(nodes, frontier, 32 * MT_DEPTH, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(nodes + 8 * MT_APPEND_ROW, row, 32 * n, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(ctx->mt_bad.p, 0xff, sizeof(uint32_t), s));
+    HIP_TRY(hipEventRecord(ev.e[1], s));
+    const uint32_t* bad = ctx->mt_bad.p;
+    const JNiels* table = (const JNiels*)ctx->nsc_table.p;
+    MASP_LAUNCH(k_mt_check, dim3((uint32_t)((n + MT_BLOCK - 1) / MT_BLOCK)), dim3(MT_BLOCK), 0, s, (const uint32_t*)(nodes + 8 * MT_APPEND_ROW),
+                (uint32_t)n, ctx->mt_bad.p);
+    uint64_t src = MT_APPEND_ROW;
+    uint32_t level = 0;
+    for (; level < MT_DEPTH; ++level) {
+        const uint64_t c0 = start >> level, c1 = end >> level;
+        const uint32_t parents = (uint32_t)((c1 >> 1) - (c0 >> 1));
+        if (parents <= MT_TOP_PARENTS) break;
+        MASP_LAUNCH(k_mt_append_level, dim3((parents + MT_BLOCK - 1) / MT_BLOCK), dim3(MT_BLOCK), 0, s, nodes, table, bad, src, src + (c1 - c0),
+                    parents, (uint32_t)(c0 & 1u), level);
+        src += c1 - c0;
+    }
+    if (level < MT_DEPTH && (end >> (level + 1)) > (start >> (level + 1)))
+        MASP_LAUNCH(k_mt_append_top, dim3(1), dim3(MT_TOP_PARENTS), 0, s, nodes, table, bad, start, end, src, level);
+    HIP_TRY(hipEventRecord(ev.e[2], s));
+    uint32_t h_bad = MT_NO_BAD;
+    HIP_TRY(hipMemcpyAsync(&h_bad, ctx->mt_bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (launch_status() != MASP_HIP_OK) return MASP_HIP_E_HIP;   // a refused launch: the buffers mean nothing
+    if (h_bad != MT_NO_BAD) {
+        if (h_bad >= n) {
+            last_hip_error() = "commitment tree: an index beyond the row";
+            return MASP_HIP_E_HIP;
+        }
+        if (bad_index) *bad_index = (int64_t)h_bad;
+        return MASP_HIP_E_INVALID_ARG;   // nothing written
+    }
+    if (total) HIP_TRY(hipMemcpyAsync(nodes_out, nodes + 8 * (MT_APPEND_ROW + n), 32 * total, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipEventRecord(ev.e[3], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float up = 0, k = 0, down = 0;
+    HIP_TRY(hipEventElapsedTime(&up, ev.e[0], ev.e[1]));
+    HIP_TRY(hipEventElapsedTime(&k, ev.e[1], ev.e[2]));
+    HIP_TRY(hipEventElapsedTime(&down, ev.e[2], ev.e[3]));
+    std::lock_guard<std::mutex> g(ctx->slot_mu);
+    ctx->mt_last_ms[0] = up;
+    ctx->mt_last_ms[1] = k;
+    ctx->mt_last_ms[2] = down;
+    return MASP_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -208,6 +325,41 @@ int masp_hip_merkle_tree_complete(masp_hip_ctx* ctx, unsigned height0, size_t n,
             ctx->nsc_table.release();
             ctx->mt_empties.release();
         }
+    }
+    return rc ? fail(ctx, rc) : MASP_HIP_OK;
+}
+
+int masp_hip_merkle_tree_append(masp_hip_ctx* ctx, uint64_t start, const uint8_t frontier[32 * 32], size_t n, const uint8_t* row,
+                                uint8_t* nodes_out, size_t nodes_capacity, size_t* n_nodes, int64_t* bad_index) {
+    if (bad_index) *bad_index = -1;
+    constexpr uint64_t full = (uint64_t)1 << MT_DEPTH;
+    if (!ctx || start > full || n > MT_MAX_ROW || start + n > full || (n && !row) || (n && start && !frontier)) return MASP_HIP_E_INVALID_ARG;
+    const size_t total = mt_append_count(start, n);
+    if (n_nodes) *n_nodes = total;
+    if (!nodes_out) return MASP_HIP_OK;                                   // the count alone
+    if (nodes_capacity < total) return MASP_HIP_E_CAPACITY;               // nothing written: the caller comes back with room for *n_nodes
+    if (n == 0) return MASP_HIP_OK;
+    uint8_t no_frontier[32 * MT_DEPTH] = {0};   // start = 0 reads none of it
+    if (!frontier) frontier = no_frontier;
+    for (uint32_t h = 0; h < MT_DEPTH; ++h) {   // the 32 nodes of the frontier are the host's to check: bit h of start set, entry h is used
+        uint32_t w[8];
+        memcpy(w, frontier + 32 * h, 32);
+        if (((start >> h) & 1u) && !fr_is_canonical(w)) {
+            if (bad_index) *bad_index = -2 - (int64_t)h;
+            return MASP_HIP_E_INVALID_ARG;
+        }
+    }
+    (void)pedersen_table_bytes();   // built outside the locks
+    const ApiLaunchScope api_scope;
+    ctx = FIRST_DEVICE(ctx);
+    std::shared_lock<std::shared_mutex> lock(ctx->mu);   // concurrent with provers and verifiers
+    std::lock_guard<std::mutex> nlock(ctx->ns_mu);       // one scan or one tree at a time: they share the stream and the table
+    hipSetDevice(ctx->device);
+    bool first_upload = false;
+    const int rc = run_append(ctx, start, frontier, n, total, row, nodes_out, bad_index, first_upload);
+    if (rc == MASP_HIP_E_HIP) {
+        (void)hipStreamSynchronize(ctx->streams.vk[0]);   // nothing of this call stays in flight
+        if (first_upload) ctx->nsc_table.release();       // the table may not have arrived
     }
     return rc ? fail(ctx, rc) : MASP_HIP_OK;
 }

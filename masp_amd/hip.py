@@ -144,6 +144,8 @@ def load_library():
     if hasattr(L, "masp_hip_merkle_tree_complete"):
         L.masp_hip_merkle_tree_complete.argtypes = [vp, C.c_uint, sz, vp, vp, sz, C.POINTER(sz), vp, sz, vp, vp, C.POINTER(C.c_int64)]
         L.masp_hip_merkle_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
+    if hasattr(L, "masp_hip_merkle_tree_append"):
+        L.masp_hip_merkle_tree_append.argtypes = [vp, C.c_uint64, vp, sz, vp, vp, sz, C.POINTER(sz), C.POINTER(C.c_int64)]
     L.masp_hip_batch_upload.argtypes = [vp, sz, vp]
     L.masp_hip_batch_prove_resident.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.masp_hip_batch_prove_resident_steps.argtypes = [vp, C.c_int, sz, vp, vp, C.POINTER(C.c_float)]
@@ -494,6 +496,29 @@ class Context:
             e.bad_index, e.needed = bad.value, nn.value
             raise e
         return (nodes[:nn.value] if want_nodes else None), root.tobytes(), paths
+
+    def merkle_tree_append(self, start, frontier, row, nodes_capacity=None):
+        """A block of leaves at an arbitrary offset on the GPU (masp_hip_merkle_tree_append): row n x 32 (bytes or a uint8 array), the leaves
+        at positions start .. start + n - 1 of the depth-32 tree; frontier 32 x 32 (or None with start = 0), entry h the node
+        (h, (start >> h) - 1), read where bit h of start is set -> uint8[N, 32]: for h = 1..32 in turn the nodes (h, i) with
+        start >> h <= i < (start + n) >> h.  A node that is not canonical raises MaspHipError with .bad_index (the row's index, or -2 - h
+        for frontier entry h); nodes_capacity: room for that many nodes (default: what the call needs), too little raises with .needed."""
+        from .host import merkle_append_args, merkle_append_error, merkle_append_node_count
+        row, frontier = merkle_append_args(start, frontier, row)
+        n = row.shape[0]
+        if nodes_capacity is None:
+            nodes_capacity = merkle_append_node_count(int(start), n)
+        nodes = np.zeros((max(1, int(nodes_capacity)), 32), np.uint8)
+        nn, bad = C.c_size_t(0), C.c_int64(-1)
+        rc = self._L.masp_hip_merkle_tree_append(self._h, int(start), _p(frontier), n, _p(row) if n else None, _p(nodes), int(nodes_capacity),
+                                                 C.byref(nn), C.byref(bad))
+        if rc:
+            detail = merkle_append_error("merkle_tree_append", bad.value) if bad.value != -1 else \
+                "%d nodes" % nn.value if rc == E_CAPACITY else self._L.masp_hip_last_error(self._h).decode(errors="replace")
+            e = MaspHipError(rc, detail)
+            e.bad_index, e.needed = bad.value, nn.value
+            raise e
+        return nodes[:nn.value]
 
     def merkle_last_timing(self):
         """(upload ms, kernel ms, download ms) of the last tree of this context, from HIP events on its stream"""

@@ -63,6 +63,8 @@ def load_library():
         L.masp_host_merkle_empty_roots.restype = None
         L.masp_host_merkle_tree_complete.argtypes = [C.c_uint, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, vp, vp,
                                                      C.POINTER(C.c_int64), C.c_int]
+        if hasattr(L, "masp_host_merkle_tree_append"):
+            L.masp_host_merkle_tree_append.argtypes = [u64, vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int64), C.c_int]
         L.masp_host_jubjub_mul.argtypes = [cp, cp, cp]
         L.masp_host_convert_cmu.argtypes = [cp, cp]
         L.masp_host_vk_prepare.restype = vp
@@ -443,6 +445,51 @@ def merkle_node_count(n, height0=0):
         total += width
         width //= 2
     return total + width
+
+
+def merkle_append_node_count(start, n):
+    """the number of nodes merkle_tree_append returns: the complete nodes of levels 1..32 whose last leaf is in [start, start + n)"""
+    return sum(((start + n) >> h) - (start >> h) for h in range(1, TREE_DEPTH + 1))
+
+
+def merkle_append_args(start, frontier, row):
+    """the arguments of either merkle_tree_append as arrays: (row uint8[n, 32], frontier uint8[32, 32])"""
+    if not 0 <= int(start) <= 1 << TREE_DEPTH:
+        raise ValueError("merkle_tree_append: start %d is not a position of the depth-%d tree" % (start, TREE_DEPTH))
+    row = np.ascontiguousarray(np.frombuffer(row, np.uint8) if isinstance(row, (bytes, bytearray, memoryview)) else row, dtype=np.uint8).reshape(-1, 32)
+    if frontier is None:
+        frontier = np.zeros((TREE_DEPTH, 32), np.uint8)
+    elif isinstance(frontier, (bytes, bytearray, memoryview)):
+        frontier = np.frombuffer(frontier, np.uint8)
+    frontier = np.ascontiguousarray(frontier, dtype=np.uint8).reshape(TREE_DEPTH, 32)
+    return row, frontier
+
+
+def merkle_append_error(name, bad):
+    return "%s: %s" % (name, "node %d is not canonical" % bad if bad >= 0 else "frontier entry %d is not canonical" % (-2 - bad))
+
+
+def merkle_tree_append(start, frontier, row, threads=None, nodes_capacity=None):
+    """masp_host_merkle_tree_append: the leaves `row` (n x 32 bytes) at positions start .. start + n - 1 of the depth-32 tree; frontier
+    (32 x 32 bytes or None with start = 0): entry h the node (h, (start >> h) - 1), read where bit h of start is set -> uint8[N, 32], for
+    h = 1..32 in turn the nodes (h, i) with start >> h <= i < (start + n) >> h.  A node that is not canonical raises ValueError with
+    .bad_index (the row's index, or -2 - h for frontier entry h); start + n > 2^32 raises ValueError too."""
+    L = load_library()
+    row, frontier = merkle_append_args(start, frontier, row)
+    n = row.shape[0]
+    if nodes_capacity is None:
+        nodes_capacity = merkle_append_node_count(int(start), n)
+    nodes = np.zeros((max(1, int(nodes_capacity)), 32), np.uint8)
+    nn, bad = C.c_size_t(0), C.c_int64(-1)
+    threads = effective_cpus() if threads is None else int(threads)
+    rc = L.masp_host_merkle_tree_append(int(start), frontier.ctypes.data_as(C.c_void_p), n, row.ctypes.data_as(C.c_void_p) if n else None,
+                                        nodes.ctypes.data_as(C.c_void_p), int(nodes_capacity), C.byref(nn), C.byref(bad), threads)
+    if rc:
+        e = ValueError(merkle_append_error("merkle_tree_append", bad.value) if bad.value != -1 else
+                       "merkle_tree_append: %s" % ERRORS.get(rc, rc))
+        e.code, e.bad_index, e.needed = rc, bad.value, nn.value
+        raise e
+    return nodes[:nn.value]
 
 
 def jubjub_mul(point, scalar):
