@@ -180,6 +180,19 @@ int masp_hip_ctx_create_multi(const int* devices, int n_devices, masp_hip_ctx** 
 int masp_hip_ctx_set_boolean_block_bits(masp_hip_ctx* ctx, int32_t bits);
 /* the resolved setting: 0 = no subset rows, 2 or 3 */
 int masp_hip_ctx_get_boolean_block_bits(const masp_hip_ctx* ctx, int32_t* out);
+/* The form in which a BATCH (eight proofs or more of a circuit's own a, b, c) computes its quotient.  Only the group element
+ * sum_k h_k H_k enters a proof, and it is linear in h: in EVALUATION form the loader derives, once per circuit, a second merged base set —
+ * the h query carried through a group-valued inverse DFT, and C's share of the quotient folded into the l query — and a proof then needs
+ * four transforms of size m instead of six, no evaluation of C w and no coefficient vector at all; its MSM runs over the coset
+ * evaluations a b / (g^m - 1), the aux assignment and the few inputs C uses.  Same proof bytes for every witness, satisfying or not (exact
+ * linear algebra, the same group element).  Costs, per circuit: a second merged window table (Spend: 0.47 GB by its row count) and two group transforms
+ * at load time.  form: MASP_HIP_QUOTIENT_EVALUATION (0, the default) or MASP_HIP_QUOTIENT_COEFFICIENT (1, six transforms
+ * over the h and l queries as they come).  Applies to circuits loaded AFTER the call.  Lone proofs and jobs with caller-supplied a, b, c
+ * use the coefficient form whatever is set.  (A call and not a field of masp_hip_options, as masp_hip_ctx_set_boolean_block_bits.) */
+#define MASP_HIP_QUOTIENT_EVALUATION 0
+#define MASP_HIP_QUOTIENT_COEFFICIENT 1
+int masp_hip_ctx_set_quotient_form(masp_hip_ctx* ctx, int32_t form);
+int masp_hip_ctx_get_quotient_form(const masp_hip_ctx* ctx, int32_t* out);
 /* number of device contexts behind `ctx` (1 for masp_hip_ctx_create) */
 int masp_hip_ctx_device_count(const masp_hip_ctx* ctx);
 /* counts[d] = proofs written so far by device context d (d < min(cap, masp_hip_ctx_device_count)): lets a caller (and the
@@ -225,6 +238,17 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
  *          the plain double-and-add, with the bytes the reference computes. */
 #define MASP_HIP_CIRCUIT_G1_ENDOMORPHISM 1u
 int masp_hip_circuit_flags(const masp_hip_ctx* ctx, uint32_t slot, uint32_t* flags);
+
+/* *form = the form the batches of the circuit in `slot` really use.  MASP_HIP_QUOTIENT_COEFFICIENT also where the evaluation form was asked
+ * for and a derived base came out as the point at infinity (negligible for a real CRS, possible for a toy one): such a circuit loads
+ * without error and keeps the coefficient form. */
+int masp_hip_circuit_quotient_form(const masp_hip_ctx* ctx, uint32_t slot, int32_t* form);
+/* The derived bases of the circuit in `slot`, uncompressed (96 bytes each), in table order: m = 2^logm points T'_i, then n_aux points L'_j,
+ * then one point per input column that C uses — input_cols lists those columns, ascending.  *n_points / *n_input_cols always receive the
+ * counts (both 0 for a circuit in coefficient form); bases == NULL and input_cols == NULL asks for the counts only; a capacity that is
+ * too small gives MASP_HIP_E_CAPACITY and writes nothing.  Exists so that the derivation can be checked on its own. */
+int masp_hip_circuit_eval_bases(const masp_hip_ctx* ctx, uint32_t slot, uint8_t* bases, size_t cap_points, size_t* n_points, uint32_t* input_cols,
+                                size_t cap_inputs, size_t* n_input_cols);
 
 /* One proof, blocking.  proof_out: 192 bytes = A (48, G1 compressed) | B (96, G2 compressed) | C (48). */
 int masp_hip_prove(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* inputs, const uint8_t* aux, const uint8_t* a,

@@ -78,6 +78,16 @@ __global__ void k_ntt_ab_bitrev(const Fr* __restrict__ a, const Fr* __restrict__
     y += (size_t)NTT_P << logm;
     fr_store(y + bitrev(k, logm), fe_mul(fr_load(a + k), fr_load(b + k)));
 }
+// y[k] = a[k] * b[k] * scale   (no permutation; a plain-form scale: the result leaves Montgomery form).  The quotient's evaluation form:
+// a, b are the coset evaluations, scale = 1 / (g^m - 1), y a proof's share of the merged scalar buffer.
+__global__ void k_ntt_ab_eval(const Fr* __restrict__ a, const Fr* __restrict__ b, Fr scale, Fr* __restrict__ y, uint32_t n, size_t y_stride) {
+    uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    a += (size_t)NTT_P * n;
+    b += (size_t)NTT_P * n;
+    y += (size_t)NTT_P * y_stride;
+    fr_store(y + k, fe_mul(fe_mul(fr_load(a + k), fr_load(b + k)), scale));
+}
 // y[k] = x[k] * scale[k] - c[k] * cscale   (plain-form scale factors: the result leaves Montgomery form)
 __global__ void k_fr_scale_sub(const Fr* __restrict__ x, const Fr* __restrict__ scale, const Fr* __restrict__ c, Fr cscale, Fr* __restrict__ y,
                                uint32_t n, size_t y_stride) {

@@ -82,13 +82,13 @@ __global__ void k_r1cs_eval(R1csMatrices M, const Fr* __restrict__ w, uint32_t n
     fr_store(out + row, acc);
 }
 
-// dst[k] = src[idx[k]]  (32-byte scalars)
+// dst[k] = src[idx[k]]  (32-byte scalars; proof p writes dst + p * dst_stride)
 __global__ void k_gather_scalars(const Fr* __restrict__ src, size_t src_stride, const uint32_t* __restrict__ idx, uint32_t n,
-                                 Fr* __restrict__ dst) {
+                                 Fr* __restrict__ dst, size_t dst_stride) {
     uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     src += blockIdx.y * src_stride;
-    dst += (size_t)blockIdx.y * n;
+    dst += (size_t)blockIdx.y * dst_stride;
     fr_store(dst + k, fr_load(src + idx[k]));
 }
 

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "chunk_pipeline.h"
+#include "host/eval_form.h"
 #include "device/io.hpp"
 #include "device/ntt_geom.h"
 #include "launch.h"
@@ -80,6 +81,7 @@ struct NttDomain {
     size_t m = 0;
     DevBuf<Fr> tw_fwd, tw_inv, coset_scale, h_scale;
     Fr c_scale;  // 1 / (m (g^m - 1)), plain form
+    Fr e_scale;  // 1 / (g^m - 1), plain form (the evaluation form's only factor: k_ntt_ab_eval)
     int init(uint32_t logm_, hipStream_t s) {
         logm = logm_;
         m = (size_t)1 << logm;
@@ -92,6 +94,7 @@ struct NttDomain {
         const Fr zinv = fe_inv(fe_sub(fe_pow(g, e, 2), fe_one<FrCfg>()));  // 1 / Z on the coset g H
         const Fr mzinv = fe_mul(minv, zinv);
         c_scale = fe_from_mont(mzinv);
+        e_scale = fe_from_mont(zinv);
         Fr one = fe_one<FrCfg>();
         size_t half = std::max<size_t>(m / 2, 1);
         int rc;
@@ -129,6 +132,16 @@ struct Circuit {
     // h and l as ONE base set (h's points, then l's) on h's windows: C only needs H + L, so a batch runs them as one MSM over
     // one bucket set — l's scalars then cost 16 window digits instead of 22 and its sort / bucket tails disappear
     BasesG1 hl;
+    // The quotient in EVALUATION form: sum_k h_k H_k is linear in h, so the last inverse transform and all of c move into
+    // the bases, once, when the circuit is loaded (k_setup.hip: build_eval_bases).  Points: [0, m) T'_i, the inverse DFT of g^-k H_k / m, in
+    // the order the forward passes leave the coset evaluations; [m, m + n_aux) L'_j = L_j - Q_j / (g^m - 1) with Q = C^T (DFT of H);
+    // then -Q_j / (g^m - 1) for the input columns C uses (eval_in_var).  A batch's scalars are E_i = a b / (g^m - 1) on the coset, its aux
+    // assignment and those inputs.  n = 0: not built (masp_hip_ctx_set_quotient_form, or a derived point came out at infinity) — the
+    // batch then runs the coefficient form on `hl`, as do jobs with caller-supplied a / b / c.
+    BasesG1 hl_eval;
+    DevBuf<uint32_t> eval_in_var;
+    uint32_t n_eval_in = 0;
+    std::vector<uint32_t> eval_inputs;   // eval_in_var on the host (masp_hip_circuit_eval_bases; the points are read back from hl_eval.tab)
     BasesG2 b2;
     // the same G2 points on narrow windows (128 buckets), for lone proofs only: B2's bucket tails are the longest chain of
     // a lone proof (every G2 addition is 40 dependent 384-bit products on one lane), and with 128 instead of 2 048 buckets
@@ -326,6 +339,8 @@ struct masp_hip_ctx {
     // block width (log2) of the subset rows behind the tables of circuits loaded from now on, resolved: 0 = none, 2 or 3
     // (masp_hip_ctx_set_boolean_block_bits; the build's default is MASP_SUBSET_BITS)
     int boolean_block_bits = MASP_SUBSET_BITS;
+    // the quotient's form for circuits loaded from now on: 0 = evaluation form, 1 = coefficient form (masp_hip_ctx_set_quotient_form)
+    int quotient_form = 0;
     int n_slots = 4;          // = opt.slots
     size_t batch_cap = 256;   // = opt.batch_cap
     std::shared_mutex mu;
@@ -442,6 +457,16 @@ static inline int get_domain(masp_hip_ctx* ctx, uint32_t logm, NttDomain** out) 
     *out = it->second.get();
     return MASP_HIP_OK;
 }
+
+// The bases of the quotient's evaluation form for one circuit (Circuit::hl_eval), derived on the device from the h and l queries
+// (uncompressed, m - 1 and n_aux points on the host) and the R1CS matrix C: two group-valued transforms over G1, the sparse combine, one
+// normalisation.  d_raw: lay.n() uncompressed points on the device.  usable: none of them is the point at infinity.   [k_setup.hip]
+struct EvalBases {
+    DevBuf<uint8_t> d_raw;
+    EvalLayout lay;
+    bool usable = false;
+};
+int build_eval_bases(masp_hip_ctx* ctx, const NttDomain& D, const uint8_t* h_raw, const uint8_t* l_raw, const masp_hip_r1cs* cs, EvalBases& out);
 
 // the note scan's limits (its geometry: chunk_pipeline.h) and the pieces its two units share (defined in k_note_scan.hip)
 constexpr size_t NS_MAX_IVKS = 4096;

@@ -26,6 +26,9 @@ void launch_ntt_scale_bitrev(hipStream_t s, const Fr* x, const Fr* scale, Fr* y,
 void launch_ntt_ab_bitrev(hipStream_t s, const Fr* a, const Fr* b, Fr* y, uint32_t logm, uint32_t np) {
     MASP_LAUNCH(k_ntt_ab_bitrev, dim3(((1u << logm) + 255) / 256, np), dim3(256), 0, s, a, b, y, logm);
 }
+void launch_ntt_ab_eval(hipStream_t s, const Fr* a, const Fr* b, const Fr& scale, Fr* y, uint32_t n, uint32_t np, size_t y_stride) {
+    MASP_LAUNCH(k_ntt_ab_eval, dim3((n + 255) / 256, np), dim3(256), 0, s, a, b, scale, y, n, y_stride);
+}
 void launch_fr_scale_sub(hipStream_t s, const Fr* x, const Fr* scale, const Fr* c, const Fr& cscale, Fr* y, uint32_t n, uint32_t np, size_t y_stride) {
     MASP_LAUNCH(k_fr_scale_sub, dim3((n + 255) / 256, np), dim3(256), 0, s, x, scale, c, cscale, y, n, y_stride ? y_stride : (size_t)n);
 }
@@ -41,13 +44,14 @@ void launch_fr_to_mont(hipStream_t s, const Fr* x, size_t x_stride, Fr* y, uint3
 void launch_fr_split_forms(hipStream_t s, Fr* x, size_t x_stride, Fr* y, uint32_t n, uint32_t mont_from, uint32_t np, int* range_err) {
     MASP_LAUNCH(k_fr_split_forms, dim3((n + 255) / 256, np), dim3(256), 0, s, x, x_stride, y, n, mont_from, range_err);
 }
-void launch_r1cs_eval(hipStream_t s, const R1csMatrices& M, const Fr* w, uint32_t n_vars, uint32_t n_constraints, uint32_t n_inputs, uint32_t np) {
+void launch_r1cs_eval(hipStream_t s, const R1csMatrices& M, const Fr* w, uint32_t n_vars, uint32_t n_constraints, uint32_t n_inputs, uint32_t np,
+                      uint32_t n_mat) {
     // lanes: 64 per long row, one per remaining row (the matrix with the most long rows sizes the grid)
-    const uint32_t nl = std::max(M.n_long[0], std::max(M.n_long[1], M.n_long[2])), lanes = n_constraints + n_inputs + nl * 63u;
-    MASP_LAUNCH(k_r1cs_eval, dim3((lanes + 127) / 128, np, 3), dim3(128), 0, s, M, w, n_vars, n_constraints, n_inputs);
+    const uint32_t nl = std::max(M.n_long[0], std::max(M.n_long[1], n_mat > 2 ? M.n_long[2] : 0u)), lanes = n_constraints + n_inputs + nl * 63u;
+    MASP_LAUNCH(k_r1cs_eval, dim3((lanes + 127) / 128, np, n_mat), dim3(128), 0, s, M, w, n_vars, n_constraints, n_inputs);
 }
-void launch_gather_scalars(hipStream_t s, const Fr* src, size_t src_stride, const uint32_t* idx, uint32_t n, Fr* dst, uint32_t np) {
-    MASP_LAUNCH(k_gather_scalars, dim3((n + 255) / 256, np), dim3(256), 0, s, src, src_stride, idx, n, dst);
+void launch_gather_scalars(hipStream_t s, const Fr* src, size_t src_stride, const uint32_t* idx, uint32_t n, Fr* dst, uint32_t np, size_t dst_stride) {
+    MASP_LAUNCH(k_gather_scalars, dim3((n + 255) / 256, np), dim3(256), 0, s, src, src_stride, idx, n, dst, dst_stride ? dst_stride : (size_t)n);
 }
 
 }  // namespace masp

@@ -5,6 +5,68 @@
 
 using namespace masp;
 
+// ---- the quotient's evaluation form: derived bases (Circuit::hl_eval) ------------------------------------------------------------------
+// With h_k = (P_k - c_k) / (g^m - 1), P the coset interpolation of a o b and c = iNTT(C w):
+//   sum_k h_k H_k = sum_i E_i T'_i + sum_j w_j Qs_j,     E_i = a(g w^i) b(g w^i) / (g^m - 1),
+//   T'_i = sum_k w^-ik (g^-k / m) H_k,   Qs_j = sum_i C_ij Ts_i,   Ts_i = sum_k w^-ik (-1 / (m (g^m - 1))) H_k,   H_{m-1} = infinity
+// (the DFT matrix is symmetric: the transposed transform is the transform).  Exact linear algebra in h, whatever the witness.
+// Both transforms run side by side: one launch per stage, m butterflies of a full scalar multiplication each — set-up code, about
+// 2 x m log m / 2 multiplications per circuit.  Every point is normalised by its own lane's inversion, not by one shared inversion: by
+// operation counts (not measured) m + n_aux inversions of about one scalar multiplication's cost each are a few per cent of the
+// m log m multiplications above.
+// h_raw and l_raw have passed the loader's import check before this is called (no bad encoding, no infinity): the statuses of
+// g1_read_uncompressed in the kernels are not looked at again.
+int masp::build_eval_bases(masp_hip_ctx* ctx, const NttDomain& D, const uint8_t* h_raw, const uint8_t* l_raw, const masp_hip_r1cs* cs, EvalBases& out) {
+    hipStream_t s = ctx->streams.main;
+    const uint32_t logm = D.logm, n_in = cs->n_inputs, n_aux = cs->n_aux, nv = n_in + n_aux;
+    const size_t m = D.m;
+    out.usable = false;
+    if (logm < 1 || m > ((size_t)1 << 30)) return MASP_HIP_OK;   // (a domain of one point has no h query at all)
+    const uint32_t n_h = (uint32_t)(m - 1);
+    CscMatrix csc;
+    if (!csc_from_csr(cs->n_constraints, nv, cs->c_rowptr, cs->c_col, cs->c_coef, csc)) return MASP_HIP_E_INVALID_ARG;
+    out.lay = eval_layout(csc, n_in, n_aux, m);
+    const EvalLayout& lay = out.lay;
+    std::vector<uint32_t> slot_cols(lay.n_slots());
+    for (uint32_t o = 0; o < lay.n_slots(); ++o) slot_cols[o] = lay.slot_col(o);
+    const Fr minv = fe_inv(fr_from_u64_mont(m)), ginv = fr_const(FrCfg::GEN_INV);
+    const Fr neg_mzinv = fe_from_mont(fe_neg(fe_to_mont(D.c_scale))), minus_one = fe_from_mont(fe_neg(fe_one<FrCfg>()));
+    DevBuf<uint8_t> d_h, d_l;
+    DevBuf<Fr> scale, d_coef;
+    DevBuf<G1Xyzz> X;
+    DevBuf<uint32_t> d_colptr, d_rowidx, d_slot_cols, d_long;
+    DevBuf<int> d_inf;
+    int rc;
+    if ((rc = d_h.upload(h_raw, (size_t)96 * n_h, s)) || (rc = d_l.upload(l_raw, (size_t)96 * n_aux, s)) || (rc = scale.reserve(m)) ||
+        (rc = X.reserve(2 * m)) || (rc = out.d_raw.reserve((size_t)96 * lay.n())) || (rc = d_inf.reserve(1)) ||
+        (rc = d_colptr.upload(csc.colptr.data(), csc.colptr.size(), s)) || (rc = d_rowidx.upload(csc.rowidx.data(), csc.rowidx.size(), s)) ||
+        (rc = d_coef.upload((const Fr*)csc.coef.data(), csc.rowidx.size(), s)) || (rc = d_slot_cols.upload(slot_cols.data(), slot_cols.size(), s)) ||
+        (rc = d_long.upload(lay.long_slots.data(), lay.long_slots.size(), s)))
+        return rc;
+    HIP_TRY(hipMemsetAsync(d_inf.p, 0, sizeof(int), s));
+    launch_fr_powers(s, scale.p, (uint32_t)m, ginv, minv, 1);   // g^-k / m, plain form
+    const dim3 block(64);
+    MASP_LAUNCH(k_g1ntt_load, dim3((uint32_t)((m + 63) / 64), 2), block, 0, s, d_h.p, n_h, scale.p, neg_mzinv, logm, X.p);
+    for (uint32_t st = 0; st < logm; ++st)
+        MASP_LAUNCH(k_g1ntt_stage, dim3((uint32_t)((m / 2 + 63) / 64), 2), block, 0, s, X.p, D.tw_inv.p, logm, st);
+    MASP_LAUNCH(k_g1_xyzz_to_bytes, dim3((uint32_t)((m + 63) / 64)), block, 0, s, X.p, (uint32_t)m, out.d_raw.p, d_inf.p);
+    uint8_t* d_slots = out.d_raw.p + (size_t)96 * m;
+    if (lay.n_slots())
+        MASP_LAUNCH(k_eval_combine, dim3((lay.n_slots() + 63) / 64), block, 0, s, d_colptr.p, d_rowidx.p, d_coef.p, X.p + m, d_slot_cols.p, lay.n_slots(),
+                    n_aux, EvalLayout::LONG_COL, minus_one, d_l.p, d_slots, d_inf.p);
+    if (!lay.long_slots.empty())
+        MASP_LAUNCH(k_eval_combine_long, dim3((uint32_t)lay.long_slots.size()), block, 0, s, d_colptr.p, d_rowidx.p, d_coef.p, X.p + m, d_slot_cols.p,
+                    d_long.p, n_aux, minus_one, d_l.p, d_slots, d_inf.p);
+    int any_inf = 1;
+    if (hipMemcpyAsync(&any_inf, d_inf.p, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess ||
+        launch_status() != MASP_HIP_OK) {
+        last_hip_error() = std::string("evaluation-form bases failed: ") + hipGetErrorString(hipGetLastError());
+        return MASP_HIP_E_HIP;
+    }
+    out.usable = any_inf == 0;
+    return MASP_HIP_OK;
+}
+
 extern "C" {
 
 // ---- parameter generation -------------------------------------------------------------------------

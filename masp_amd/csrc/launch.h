@@ -16,6 +16,8 @@ void launch_ntt_load_bitrev(hipStream_t s, const Fr* x, size_t x_stride, uint32_
 void launch_ntt_copy_bitrev(hipStream_t s, const Fr* x, size_t x_stride, uint32_t nrows, Fr* y, uint32_t logm, uint32_t np);
 void launch_ntt_scale_bitrev(hipStream_t s, const Fr* x, const Fr* scale, Fr* y, uint32_t logm, uint32_t np);
 void launch_ntt_ab_bitrev(hipStream_t s, const Fr* a, const Fr* b, Fr* y, uint32_t logm, uint32_t np);
+// y_p[k] = a_p[k] * b_p[k] * scale for k < n (a, b: np vectors of n back to back; plain-form scale: canonical results), y_p = y + p * y_stride
+void launch_ntt_ab_eval(hipStream_t s, const Fr* a, const Fr* b, const Fr& scale, Fr* y, uint32_t n, uint32_t np, size_t y_stride);
 void launch_fr_scale_sub(hipStream_t s, const Fr* x, const Fr* scale, const Fr* c, const Fr& cscale, Fr* y, uint32_t n, uint32_t np, size_t y_stride = 0);
 // y_p = y + p * y_stride (0: n)
 void launch_fr_scale(hipStream_t s, const Fr* x, const Fr* scale, Fr* y, uint32_t n, uint32_t np, size_t y_stride = 0);
@@ -31,8 +33,10 @@ struct R1csMatrices {  // the static R1CS of a circuit (CSR, rows by decreasing 
     uint32_t n_long[3];  // the first n_long rows of `order` (>= R1CS_LONG_ROW terms) are summed by a wave each
 };
 static constexpr uint32_t R1CS_LONG_ROW = 64;
-void launch_r1cs_eval(hipStream_t s, const R1csMatrices& M, const Fr* w, uint32_t n_vars, uint32_t n_constraints, uint32_t n_inputs, uint32_t np);
-void launch_gather_scalars(hipStream_t s, const Fr* src, size_t src_stride, const uint32_t* idx, uint32_t n, Fr* dst, uint32_t np);
+void launch_r1cs_eval(hipStream_t s, const R1csMatrices& M, const Fr* w, uint32_t n_vars, uint32_t n_constraints, uint32_t n_inputs, uint32_t np,
+                      uint32_t n_mat = 3);   // n_mat = 2: a and b only (the quotient's evaluation form never evaluates c)
+// dst_p = dst + p * dst_stride (0: n)
+void launch_gather_scalars(hipStream_t s, const Fr* src, size_t src_stride, const uint32_t* idx, uint32_t n, Fr* dst, uint32_t np, size_t dst_stride = 0);
 
 // ---- k_groth16.hip: proof assembly, point import / export, fixed-base tables (device/groth16.hpp) ----
 void launch_groth16_fixed_g1(hipStream_t s, const G1Xyzz* fb1, const uint32_t* rs, size_t rs_stride, G1Xyzz* part, uint32_t np);

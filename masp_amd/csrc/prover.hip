@@ -184,6 +184,30 @@ static int enqueue_quotient(Slot& sl, const NttDomain& D, const Fr* const in[3],
     return MASP_HIP_OK;
 }
 
+// The quotient of a batch in EVALUATION form (Circuit::hl_eval): a and b only — to coefficients, onto the coset g H — and then their
+// pointwise product E = a b / (g^m - 1), canonical, straight into the merged scalar buffer (e_out + p * e_stride); four transforms per
+// proof, no permutation behind the last.  in[0], in[1] + p * in_stride: Montgomery evaluation vectors of `nrows` entries.
+static int enqueue_quotient_eval(Slot& sl, const NttDomain& D, const Fr* const in[2], size_t in_stride, uint32_t nrows, uint32_t np, Fr* e_out,
+                                 size_t e_stride) {
+    hipStream_t s = sl.stream;
+    const uint32_t m = (uint32_t)D.m, logm = D.logm;
+    const uint32_t sub_max = sl.ntt_sub;  // as in enqueue_quotient: the work buffers (here sub x 4 x 32 m bytes) stay in the Infinity Cache
+    const uint32_t sub = sub_max ? std::min(sub_max, np) : np;
+    int rc;
+    if ((rc = sl.x0.reserve((size_t)2 * m * sub)) || (rc = sl.x1.reserve((size_t)2 * m * sub))) return rc;
+    Fr *x0 = sl.x0.p, *x1 = sl.x1.p;
+    for (uint32_t p0 = 0; p0 < np; p0 += sub) {
+        const uint32_t q = std::min(sub, np - p0);
+        const size_t part = (size_t)q * m;  // one of a / b for the whole sub-batch
+        for (int i = 0; i < 2; ++i) launch_ntt_copy_bitrev(s, in[i] + (size_t)p0 * in_stride, in_stride, nrows, x0 + i * part, logm, q);
+        D.passes(s, x0, D.tw_inv.p, 2 * q);                                     // m A, m B (coefficients)
+        launch_ntt_scale_bitrev(s, x0, D.coset_scale.p, x1, logm, 2 * q);       // * g^k / m
+        D.passes(s, x1, D.tw_fwd.p, 2 * q);                                     // A, B on the coset g H, natural order
+        launch_ntt_ab_eval(s, x1, x1 + part, D.e_scale, e_out + (size_t)p0 * e_stride, m, q, e_stride);
+    }
+    return MASP_HIP_OK;
+}
+
 // Enqueue np proofs of circuit C as one batch.  d_w + p * w_stride: n_vars canonical scalars on the device (inputs then
 // aux).  d_abc[i] + p * nrows: canonical evaluation vectors on the device, or all NULL.  d_rs + p * 16: r | s limbs.
 // d_proof + p * 192: output.
@@ -209,8 +233,10 @@ static int enqueue_proofs(Slot& sl, Circuit& C, uint32_t np, const Fr* d_w, size
         for (int i = 0; i < Slot::N_AUX; ++i) HIP_TRY(hipStreamWaitEvent(sl.aux[i], sl.ev_fork, 0));
     }
     if (!aux_montgomery) launch_fr_to_mont(s, d_w, w_stride, sl.wm.p, nv, np, sl.flags.p);
-    const Fr* in[3];
+    const Fr* in[3] = {nullptr, nullptr, nullptr};
     bool mont_in;
+    // the quotient in evaluation form: a batch of the circuit's own a, b, c whose circuit has the derived bases (Circuit::hl_eval)
+    const bool eval_form = !lone && !d_abc[0] && C.hl_eval.n != 0;
     if (d_abc[0]) {
         in[0] = d_abc[0];
         in[1] = d_abc[1];
@@ -218,7 +244,8 @@ static int enqueue_proofs(Slot& sl, Circuit& C, uint32_t np, const Fr* d_w, size
         mont_in = false;
     } else {
         R1csMatrices M;
-        for (int i = 0; i < 3; ++i) {
+        const int n_mat = eval_form ? 2 : 3;   // c is folded into hl_eval: never evaluated
+        for (int i = 0; i < n_mat; ++i) {
             if ((rc = sl.ev[i].reserve((size_t)C.nrows * np))) return rc;
             M.rowptr[i] = C.rowptr[i].p;
             M.order[i] = C.row_order[i].p;
@@ -228,7 +255,13 @@ static int enqueue_proofs(Slot& sl, Circuit& C, uint32_t np, const Fr* d_w, size
             M.out[i] = sl.ev[i].p;
             in[i] = sl.ev[i].p;
         }
-        launch_r1cs_eval(s, M, sl.wm.p, nv, C.n_constraints, C.n_inputs, np);  // a, b, c = A w, B w, C w in one launch
+        for (int i = n_mat; i < 3; ++i) {
+            M.rowptr[i] = M.order[i] = M.col[i] = nullptr;
+            M.coef[i] = nullptr;
+            M.out[i] = nullptr;
+            M.n_long[i] = 0;
+        }
+        launch_r1cs_eval(s, M, sl.wm.p, nv, C.n_constraints, C.n_inputs, np, (uint32_t)n_mat);  // a, b, c = A w, B w, C w in one launch
         mont_in = true;
     }
     if ((rc = sl.sa.reserve((size_t)C.na * np)) || (rc = sl.sb.reserve((size_t)C.nbq * np))) return rc;
@@ -313,15 +346,23 @@ static int enqueue_proofs(Slot& sl, Circuit& C, uint32_t np, const Fr* d_w, size
         // H and L as one MSM over the merged base set (Circuit::hl): the scalars of a proof are its m - 1 quotient coefficients
         // followed by its aux assignment (the quotient's m-th, unused, coefficient lands on the first aux slot and is then
         // overwritten by the copy)
-        const size_t hl_stride = C.hl.n;
+        // In evaluation form (Circuit::hl_eval) the scalars are the m coset evaluations E, the aux assignment and the inputs C uses.
+        const BasesG1& HL = eval_form ? C.hl_eval : C.hl;
+        const size_t hl_stride = HL.n, aux_at = eval_form ? C.m : C.m - 1;
         if ((rc = sl.hl.reserve(hl_stride * np + 1))) return rc;
-        if ((rc = enqueue_quotient(sl, *C.dom, in, C.nrows, C.nrows, mont_in, np, sl.hl.p, hl_stride))) return rc;
-        HIP_TRY(hipMemcpy2DAsync(sl.hl.p + (C.m - 1), hl_stride * sizeof(Fr), d_w + C.n_inputs, w_stride * sizeof(Fr), (size_t)C.n_aux * sizeof(Fr), np,
-                                 hipMemcpyDeviceToDevice, s));
+        if (eval_form) {
+            if ((rc = enqueue_quotient_eval(sl, *C.dom, in, C.nrows, C.nrows, np, sl.hl.p, hl_stride))) return rc;
+            if (C.n_eval_in) launch_gather_scalars(s, d_w, w_stride, C.eval_in_var.p, C.n_eval_in, sl.hl.p + C.m + C.n_aux, np, hl_stride);
+        } else if ((rc = enqueue_quotient(sl, *C.dom, in, C.nrows, C.nrows, mont_in, np, sl.hl.p, hl_stride))) {
+            return rc;
+        }
+        if (C.n_aux)
+            HIP_TRY(hipMemcpy2DAsync(sl.hl.p + aux_at, hl_stride * sizeof(Fr), d_w + C.n_inputs, w_stride * sizeof(Fr), (size_t)C.n_aux * sizeof(Fr), np,
+                                     hipMemcpyDeviceToDevice, s));
         // query scalars selected by density
         if (C.na) launch_gather_scalars(s, d_w, w_stride, C.a_var.p, C.na, sl.sa.p, np);
         if (C.nbq) launch_gather_scalars(s, d_w, w_stride, C.b_var.p, C.nbq, sl.sb.p, np);
-        if ((rc = msm_enqueue(s, C.hl, sl.ws1, (const uint32_t*)sl.hl.p, hl_stride * 8, sl.res1.p + 0, 4, np, prof))) return rc;
+        if ((rc = msm_enqueue(s, HL, sl.ws1, (const uint32_t*)sl.hl.p, hl_stride * 8, sl.res1.p + 0, 4, np, prof))) return rc;
         // L is inside H + L: its slot of every proof is the point at infinity (one strided fill, not np of them)
         HIP_TRY(hipMemset2DAsync(sl.res1.p + 1, 4 * sizeof(G1Xyzz), 0, sizeof(G1Xyzz), np, s));
         // (b_g2 on b_g1's window width is reduced from b_g1's sorted digit list; on a width of its own — masp_hip_options::window_bits_b2 — it sorts for itself)
@@ -775,6 +816,22 @@ int masp_hip_ctx_get_boolean_block_bits(const masp_hip_ctx* ctx, int32_t* out) {
     return MASP_HIP_OK;
 }
 
+int masp_hip_ctx_set_quotient_form(masp_hip_ctx* ctx, int32_t form) {
+    if (!ctx || (form != MASP_HIP_QUOTIENT_EVALUATION && form != MASP_HIP_QUOTIENT_COEFFICIENT)) return MASP_HIP_E_INVALID_ARG;
+    auto set = [&](masp_hip_ctx* c) {
+        std::unique_lock<std::shared_mutex> lock(c->mu);
+        c->quotient_form = form;
+    };
+    set(ctx);
+    for (masp_hip_ctx* c : ctx->children) set(c);
+    return MASP_HIP_OK;
+}
+int masp_hip_ctx_get_quotient_form(const masp_hip_ctx* ctx, int32_t* out) {
+    if (!ctx || !out) return MASP_HIP_E_INVALID_ARG;
+    *out = (ctx->children.empty() ? ctx : ctx->children[0])->quotient_form;
+    return MASP_HIP_OK;
+}
+
 int masp_hip_ctx_create(int device, masp_hip_ctx** out) {
     if (!out) return MASP_HIP_E_INVALID_ARG;
     return masp_hip_ctx_create_ex(&device, 1, nullptr, out);
@@ -1013,12 +1070,12 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
         const int c_lone = ctx->opt.window_bits_b2_lone;  // 0 = lone proofs share the batch tables (and B1's sort)
         if (c_lone > 0 && L.n_b2 && (rc = C->b2_lone.load_host(L.b_g2, L.n_b2, s, eff(L.n_b2), c_lone))) return fail(ctx, rc);
     }
+    const int c_hl = c_h ? c_h : ctx->opt.window_bits_h_lone ? 0 : C->h.g.c;
     {
         const size_t nh = C->m - 1;
         std::vector<uint8_t> cat(96 * (nh + L.n_l));
         memcpy(cat.data(), L.h, 96 * nh);
         memcpy(cat.data() + 96 * nh, L.l, 96 * (size_t)L.n_l);
-        const int c_hl = c_h ? c_h : ctx->opt.window_bits_h_lone ? 0 : C->h.g.c;
         // (subset rows over the l part only: the quotient's coefficients are uniform in Fr)
         if ((rc = C->hl.load_host(cat.data(), (uint32_t)(nh + L.n_l), s, 0xffffffffu, c_hl, sub_bits, (uint32_t)nh))) return fail(ctx, rc);
     }
@@ -1041,6 +1098,28 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
         C->g1_endo = outside == 0;
     }
     if ((rc = get_domain(ctx, C->logm, &C->dom))) return fail(ctx, rc);
+    if (ctx->quotient_form == 0) {
+        // the quotient in evaluation form: the derived base set next to `hl` (which jobs with their own a / b / c keep using).  A derived
+        // point at infinity — a toy CRS — is no error: the circuit silently keeps the coefficient form.
+        masp::EvalBases E;
+        if ((rc = build_eval_bases(ctx, *C->dom, L.h, L.l, cs, E))) return fail(ctx, rc);
+        if (E.usable) {
+            const masp::EvalLayout& lay = E.lay;
+            // (subset rows over the aux part only: the coset evaluations are as uniform in Fr as the coefficients were)
+            if ((rc = C->hl_eval.load_device(E.d_raw.p, (uint32_t)lay.n(), s, 0xffffffffu, c_hl, sub_bits, (uint32_t)lay.aux_off(), (uint32_t)lay.in_off())))
+                return fail(ctx, rc);
+            if ((rc = C->eval_in_var.upload(lay.used_inputs.data(), lay.used_inputs.size(), s))) return fail(ctx, rc);
+            if (hipStreamSynchronize(s) != hipSuccess) return fail(ctx, MASP_HIP_E_HIP);
+            C->eval_inputs = lay.used_inputs;
+            C->n_eval_in = (uint32_t)lay.used_inputs.size();
+            if (C->hl_eval.import_status) {   // (cannot happen for points this library wrote; never prove on a table that failed its import)
+                C->hl_eval.release();
+                C->hl_eval.n = 0;
+                C->eval_inputs.clear();
+                C->n_eval_in = 0;
+            }
+        }
+    }
     ctx->circ[slot] = std::move(C);
     return MASP_HIP_OK;
 }
@@ -1051,6 +1130,37 @@ int masp_hip_circuit_flags(const masp_hip_ctx* ctx, uint32_t slot, uint32_t* fla
     std::shared_lock<std::shared_mutex> lock(const_cast<masp_hip_ctx*>(ctx)->mu);
     if (slot >= MASP_HIP_MAX_CIRCUITS || !ctx->circ[slot]) return MASP_HIP_E_NOT_LOADED;
     *flags = ctx->circ[slot]->g1_endo ? MASP_HIP_CIRCUIT_G1_ENDOMORPHISM : 0u;
+    return MASP_HIP_OK;
+}
+
+int masp_hip_circuit_quotient_form(const masp_hip_ctx* ctx, uint32_t slot, int32_t* form) {
+    if (!ctx || !form) return MASP_HIP_E_INVALID_ARG;
+    if (!ctx->children.empty()) return masp_hip_circuit_quotient_form(ctx->children[0], slot, form);
+    std::shared_lock<std::shared_mutex> lock(const_cast<masp_hip_ctx*>(ctx)->mu);
+    if (slot >= MASP_HIP_MAX_CIRCUITS || !ctx->circ[slot]) return MASP_HIP_E_NOT_LOADED;
+    *form = ctx->circ[slot]->hl_eval.n ? MASP_HIP_QUOTIENT_EVALUATION : MASP_HIP_QUOTIENT_COEFFICIENT;
+    return MASP_HIP_OK;
+}
+int masp_hip_circuit_eval_bases(const masp_hip_ctx* ctx, uint32_t slot, uint8_t* bases, size_t cap_points, size_t* n_points, uint32_t* input_cols,
+                                size_t cap_inputs, size_t* n_input_cols) {
+    if (!ctx || !n_points || !n_input_cols) return MASP_HIP_E_INVALID_ARG;
+    if (!ctx->children.empty()) return masp_hip_circuit_eval_bases(ctx->children[0], slot, bases, cap_points, n_points, input_cols, cap_inputs, n_input_cols);
+    std::shared_lock<std::shared_mutex> lock(const_cast<masp_hip_ctx*>(ctx)->mu);
+    if (slot >= MASP_HIP_MAX_CIRCUITS || !ctx->circ[slot]) return MASP_HIP_E_NOT_LOADED;
+    const Circuit& C = *ctx->circ[slot];
+    *n_points = C.hl_eval.n;
+    *n_input_cols = C.eval_inputs.size();
+    if (!bases && !input_cols) return MASP_HIP_OK;   // (sizes only)
+    if (!bases || !input_cols || cap_points < *n_points || cap_inputs < *n_input_cols) return MASP_HIP_E_CAPACITY;
+    // no copy of the points is kept for this call: they are read back from the table's first n rows, which hold the points themselves
+    // (k_msm_import), and encoded here
+    if (C.hl_eval.n) {
+        std::vector<masp::TabRow<masp::FpOps>> rows(C.hl_eval.n);
+        hipSetDevice(ctx->device);
+        if (hipMemcpy(rows.data(), C.hl_eval.tab, sizeof(rows[0]) * rows.size(), hipMemcpyDeviceToHost) != hipSuccess) return MASP_HIP_E_HIP;
+        for (size_t i = 0; i < rows.size(); ++i) masp::g1_write_uncompressed(rows[i].p, bases + 96 * i);
+    }
+    memcpy(input_cols, C.eval_inputs.data(), 4 * C.eval_inputs.size());
     return MASP_HIP_OK;
 }
 

@@ -48,6 +48,7 @@ class JobStruct(C.Structure):
 
 assert C.sizeof(JobStruct) == 120 and JobStruct.r.offset == 48 and JobStruct.aux_form.offset == 112   # include/masp_hip.h asserts the same
 AUX_CANONICAL, AUX_MONTGOMERY = 0, 1     # masp_hip_job::aux_form
+QUOTIENT_EVALUATION, QUOTIENT_COEFFICIENT = 0, 1     # masp_hip_ctx_set_quotient_form
 
 
 def library_path():
@@ -122,6 +123,11 @@ def load_library():
         L.masp_hip_msm_g2_multi_ex.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_int, sz, sz, vp, vp]
         L.masp_hip_ctx_set_boolean_block_bits.argtypes = [vp, C.c_int32]
         L.masp_hip_ctx_get_boolean_block_bits.argtypes = [vp, C.POINTER(C.c_int32)]
+    if hasattr(L, "masp_hip_ctx_set_quotient_form"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
+        L.masp_hip_ctx_set_quotient_form.argtypes = [vp, C.c_int32]
+        L.masp_hip_ctx_get_quotient_form.argtypes = [vp, C.POINTER(C.c_int32)]
+        L.masp_hip_circuit_quotient_form.argtypes = [vp, u32, C.POINTER(C.c_int32)]
+        L.masp_hip_circuit_eval_bases.argtypes = [vp, u32, vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz)]
     L.masp_hip_quotient_h.argtypes = [vp, vp, vp, vp, sz, u32, vp]
     L.masp_hip_ntt.argtypes = [vp, vp, u32, C.c_int]
     L.masp_hip_vk_prepare.argtypes = [vp, vp, sz, C.POINTER(vp)]
@@ -589,6 +595,33 @@ class Context:
         v = C.c_int32(0)
         self._check(self._L.masp_hip_ctx_get_boolean_block_bits(self._h, C.byref(v)))
         return int(v.value)
+
+    def set_quotient_form(self, form):
+        """How the batches of circuits loaded FROM NOW ON compute their quotient: QUOTIENT_EVALUATION (0, the default: four transforms per
+        proof over bases derived when the circuit is loaded) or QUOTIENT_COEFFICIENT (1: six transforms over the h and l queries)."""
+        self._check(self._L.masp_hip_ctx_set_quotient_form(self._h, int(form)))
+
+    @property
+    def quotient_form(self):
+        v = C.c_int32(0)
+        self._check(self._L.masp_hip_ctx_get_quotient_form(self._h, C.byref(v)))
+        return int(v.value)
+
+    def circuit_quotient_form(self, slot):
+        """the form the batches of the circuit in `slot` really use (coefficient form also where a derived base came out at infinity)"""
+        v = C.c_int32(0)
+        self._check(self._L.masp_hip_circuit_quotient_form(self._h, int(slot), C.byref(v)))
+        return int(v.value)
+
+    def circuit_eval_bases(self, slot):
+        """masp_hip_circuit_eval_bases -> (u8[n, 96] uncompressed points: T' (m), L' (n_aux), one per used input; the used input columns)"""
+        n, k = C.c_size_t(0), C.c_size_t(0)
+        self._check(self._L.masp_hip_circuit_eval_bases(self._h, int(slot), None, 0, C.byref(n), None, 0, C.byref(k)))
+        pts = np.zeros((n.value, 96), dtype=np.uint8)
+        cols = np.zeros(max(k.value, 1), dtype=np.uint32)
+        if n.value:
+            self._check(self._L.masp_hip_circuit_eval_bases(self._h, int(slot), _p(pts), n.value, C.byref(n), _p(cols), cols.size, C.byref(k)))
+        return pts, [int(c) for c in cols[:k.value]]
 
     def current_options(self):
         """masp_hip_ctx_get_options now: the options with what lack of tree scratch has changed since creation — the
