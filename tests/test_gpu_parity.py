@@ -36,7 +36,9 @@ def _rand_scalars(rng, n, bool_share=0.0):
     return out
 
 
-@pytest.mark.parametrize("logm", [1, 4, 9, 10, 11, 13, 15, 16, 17])       # 15 / 16 / 17: the Output / Convert / Spend domains
+# every size the API accepts.  15 / 16 / 17: the Output / Convert / Spend domains; 2 and 3: the first two stages' shortcut reads the first or
+# second twiddle; 1 to 10: one pass; from 11 on a pass of ten stages and a second pass of 1 to 10 (NttDomain::passes)
+@pytest.mark.parametrize("logm", list(range(1, 21)))
 def test_ntt_matches_oracle(ctx, logm):
     rng = np.random.default_rng(logm)
     m = 1 << logm
