@@ -301,13 +301,29 @@ int masp_hip_ntt(masp_hip_ctx* ctx, uint8_t* data, uint32_t logm, int inverse);
  * n x 16 B of caller-supplied randomness z (one random linear combination, as bellman does).  Proof decompression, the
  * z_i-multiples and the n Miller loops (one wavefront per pairing) run on the device; the public-input combination, two
  * pairings and the single final exponentiation on the host.  *all_valid = 1 iff every proof verifies (up to 2^-127);
- * 0 says at least one does not, not which.  Re-entrant: runs next to proving calls on one of the context's two verifier streams (one
+ * 0 says at least one does not, not which (masp_hip_verify_each below says which).  Re-entrant: runs next to proving calls on one of the context's two verifier streams (one
  * verification at a time per key; keys beyond two share a stream).  A key must be freed before its context is destroyed. */
 typedef struct masp_hip_vk masp_hip_vk;
 int masp_hip_vk_prepare(masp_hip_ctx* ctx, const uint8_t* params, size_t params_len, masp_hip_vk** out);
 void masp_hip_vk_free(masp_hip_vk* vk);
 int masp_hip_verify_batch(masp_hip_ctx* ctx, masp_hip_vk* vk, size_t n, const uint8_t* proofs, const uint8_t* public_inputs,
                           uint32_t n_public, const uint8_t* z, int* all_valid);
+/* Per-proof verdicts <- `verify_proof` as SaplingVerificationContext calls it (masp_proofs/src/sapling/verifier/single.rs): what a
+ * mempool needs for every bundle, and a block validator once a batch has failed.  Same arguments as the batch call without z: nothing
+ * is randomised, the result is deterministic.  verdicts[i] (n bytes) is what masp_host_vk_verify returns for proof i alone:
+ *    1  the pairing equation holds                     (host: 1)
+ *    0  it does not                                    (host: 0)
+ *    2  `Proof::read` refuses the proof: flags, a non-canonical coordinate, off the curve, outside the subgroup, the identity  (host: -2)
+ *    3  a public input >= r                            (host: -3; 2 comes before 3)
+ * All of it runs on the device: decoding, IC_0 + sum_j x_ij IC_j from a table of the key's multiples (uploaded by the first call),
+ * three Miller loops per proof (one wavefront per pairing) and one final exponentiation per proof (one wavefront each, the same
+ * interpreter).  n = 0 is MASP_HIP_OK; n <= 2^20, processed 2^16 proofs at a time; a wrong n_public gives MASP_HIP_E_PARAMS_SHAPE.
+ * Runs on the key's verifier stream, one verification at a time per key, next to proving calls. */
+int masp_hip_verify_each(masp_hip_ctx* ctx, masp_hip_vk* vk, size_t n, const uint8_t* proofs, const uint8_t* public_inputs,
+                         uint32_t n_public, uint8_t* verdicts);
+/* of the key's last masp_hip_verify_each call, summed over its chunks from HIP events on its stream: ms[0] the copies in and the decoding,
+ * ms[1] the public-input combination, ms[2] the Miller loops, ms[3] the products and final exponentiations, ms[4] the copy out */
+int masp_hip_verify_each_last_timing(masp_hip_vk* vk, double ms[5]);
 
 /* ---- RedJubjub batch verification on the GPU ----
  * masp_hip_jubjub_msm — building block: out32 = the encoding of sum_i [scalars_i] points_i; points n x 32 (Jubjub encodings),
@@ -321,12 +337,17 @@ int masp_hip_verify_batch(masp_hip_ctx* ctx, masp_hip_vk* vk, size_t n, const ui
  * each z_i is set, so that no item drops out).  c_i = H*(Rbar_i || vk_i || sighash_i) (BLAKE2b-512, personal "MASP__RedJubjubH",
  * reduced mod r_J).  *all_valid = 1 iff every Rbar_i and vk_i decodes (ZIP 216), every S_i < r_J and
  *    [8] ( sum_i [z_i] R_i + [z_i c_i] vk_i - [sum_{spend auth} z_i S_i] G_spend - [sum_{binding} z_i S_i] G_binding ) = O,
- * i.e. (up to 2^-127) every signature verifies; 0 says at least one does not, not which.  n = 0 is valid; n <= 2^20.  H* and the
+ * i.e. (up to 2^-127) every signature verifies; 0 says at least one does not, not which (masp_hip_redjubjub_verify_each does).  n = 0 is valid; n <= 2^20.  H* and the
  * coefficients are computed on the host; the 2n + 2 point decodings, scalar multiplications and the sum run on the device.
  * Both: re-entrant next to proving and Groth16 verification calls, on the context's second verifier stream (one call at a time per context). */
 int masp_hip_jubjub_msm(masp_hip_ctx* ctx, size_t n, const uint8_t* points, const uint8_t* scalars, uint8_t out32[32], int64_t* bad_index);
 int masp_hip_redjubjub_verify_batch(masp_hip_ctx* ctx, size_t n, const uint8_t* vks, const uint8_t* sigs, const uint8_t* sighashes,
                                     const uint8_t* kinds, const uint8_t* z, int* all_valid);
+/* Per-signature verdicts <- redjubjub::PublicKey::verify (ZIP 216 on): the batch call's arguments without z.  verdicts[i] (n bytes) = 1
+ * iff Rbar_i and vk_i decode, S_i < r_J and [8] (R_i + [c_i] vk_i - [S_i] G_kind) = O, else 0.  c_i is computed on the host as in the
+ * batch call; everything else runs one lane per signature on the context's second verifier stream, under the batch call's lock. */
+int masp_hip_redjubjub_verify_each(masp_hip_ctx* ctx, size_t n, const uint8_t* vks, const uint8_t* sigs, const uint8_t* sighashes,
+                                   const uint8_t* kinds, uint8_t* verdicts);
 
 /* ---- Batch trial decryption of Sapling notes on the GPU ----
  * masp_hip_sapling_trial_decrypt <- the device half of masp_note_encryption::batch::try_note_decryption over SaplingDomain

@@ -98,6 +98,12 @@ int masp_host_vk_verify_batch(const void* h, size_t n, const uint8_t* proofs, co
 /* the GPU verifier's Miller-loop programs on a host interpreter against this library's own Miller loop, for one pair (P 96 B, Q 192 B
  * uncompressed); 0 = equal.  stats (may be NULL): 15 words, see host_api.cpp */
 int masp_host_pairing_program_selftest(const uint8_t* p96, const uint8_t* q192, uint32_t* stats);
+/* The final exponentiation's programs (product, squaring, Frobenius, Frobenius^2, the two halves of the inversion) run on the host
+ * interpreter in the device kernel's order on f (in576: 12 Fp, 48 bytes big-endian each) and compared with the library's own final
+ * exponentiation.  0 = equal, out576 = f^(3 (p^12 - 1) / r); 2 = f has norm zero, the branch in front of the inversion was taken:
+ * the verdict is "invalid" (out576 = zeros); 1 / 3 = the programs are wrong; -1 = a coefficient >= p.  stats (may be NULL, 32 words):
+ * ops / steps / steps with products / products / slots of each of the six, then the slots of the set and their bytes of LDS. */
+int masp_host_final_exp_program_selftest(const uint8_t* in576, uint8_t* out576, uint32_t* stats);
 
 /* ---- native primitives (pinned by the reference's vectors: tests/golden/) ---- */
 /* which: 0 proof_generation_key, 1 note_commitment_randomness, 2 nullifier_position, 3 value_commitment_randomness, 4 spending_key,

@@ -597,6 +597,47 @@ int masp_host_pairing_program_selftest(const uint8_t* p96, const uint8_t* q192, 
     return 0;
 }
 
+// The final exponentiation of the GPU per-proof verifier exists as programs too (host/pairing_prog.h: product, squaring, the two
+// Frobenius maps, the two halves of the inversion) under one driver that the device kernel shares.  This runs them on the host
+// interpreter in the kernel's order on f (in576: 12 Fp, 48 bytes big-endian each, in the flat order of bls::Fp12) and compares the
+// result, coefficient for coefficient, with bls::final_exp.  0 = equal, out576 = f^(3 (p^12 - 1) / r);  2 = f has norm zero (only
+// f = 0 has), the branch before the inversion was taken and the verdict of such a value is "invalid" (out576 = zeros);  1 = the two
+// differ;  3 = the zero-norm branch was taken for a value that has an inverse;  -1 = a coefficient >= p.
+// stats (may be NULL, 32 words): ops / steps / steps with products / products / slots of mul, sq, frob, frob2, inv1, inv2, then
+// the slots of the whole set (saved values and constants included) and the bytes of LDS they take on the device.
+int masp_host_final_exp_program_selftest(const uint8_t* in576, uint8_t* out576, uint32_t* stats) {
+    const prog::FinalExpPrograms& fp = prog::final_exp_programs();
+    if (stats) {
+        for (int i = 0; i < 6; ++i) {
+            const prog::Program* q = fp.all(i);
+            stats[5 * i] = (uint32_t)q->ops.size();
+            stats[5 * i + 1] = (uint32_t)q->step_start.size() - 1;
+            stats[5 * i + 2] = q->n_mul_steps;
+            stats[5 * i + 3] = q->n_mul;
+            stats[5 * i + 4] = q->n_slots;
+        }
+        stats[30] = fp.n_slots;
+        stats[31] = fp.n_slots * 48;
+    }
+    bls::Fp12 f, got;
+    bls::Fp* c = &f.a.a.a;
+    bool zero = true;
+    for (int i = 0; i < 12; ++i) {
+        if (!bls::Fp::from_be(c[i], in576 + 48 * i)) return -1;
+        zero = zero && c[i].is_zero();
+    }
+    memset(out576, 0, 576);
+    if (!prog::final_exp_by_program(f, got)) return zero ? 2 : 3;
+    if (!(got == bls::final_exp(f))) return 1;
+    const bls::Fp* g = &got.a.a.a;
+    for (int i = 0; i < 12; ++i) {
+        uint64_t v[6];
+        g[i].canon(v);
+        for (int k = 0; k < 48; ++k) out576[48 * i + k] = (uint8_t)(v[5 - k / 8] >> (8 * (7 - k % 8)));
+    }
+    return 0;
+}
+
 // ---- native primitives (pinned by the reference's vectors in tests/) ---------------------------------
 // which: 0 proof_generation_key 1 note_commitment_randomness 2 nullifier_position 3 value_commitment_randomness
 //        4 spending_key 5..10 pedersen[0..5]; out: u | v as 2 x 32 B LE

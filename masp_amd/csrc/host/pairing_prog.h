@@ -124,6 +124,40 @@ struct Fp12T {
         return {t0 + t1.mulv(), (a + b).mul_01(c0, c1 + c2) - t0 - t1};
     }
 };
+// ---- the final exponentiation's pieces (host/pairing.h's frobenius and Fp2 / Fp6 / Fp12 inv), over any base field ---------
+// x -> x^p: conj of every Fp2 coefficient, times gamma[i] for the coefficient of w^i (g[0..4] = gamma[1..5])
+template <class F>
+Fp12T<F> frobenius_t(const Fp12T<F>& f, const Fp2T<F>* g) {
+    auto cj = [](const Fp2T<F>& x) { return Fp2T<F>{x.a, x.b.neg()}; };
+    return {{cj(f.a.a), cj(f.a.b) * g[1], cj(f.a.c) * g[3]}, {cj(f.b.a) * g[0], cj(f.b.b) * g[2], cj(f.b.c) * g[4]}};
+}
+// x -> x^(p^2): the coefficient of w^i times gamma[i] conj(gamma[i]), which lies in Fp (n[0..4] for i = 1..5)
+template <class F>
+Fp12T<F> frobenius2_t(const Fp12T<F>& f, const F* n) {
+    return {{f.a.a, f.a.b.scale(n[1]), f.a.c.scale(n[3])}, {f.b.a.scale(n[0]), f.b.b.scale(n[2]), f.b.c.scale(n[4])}};
+}
+// f^-1 = conj(f) / (a^2 - v b^2); the Fp6 below is inverted through its Fp2 norm D, and D through its Fp norm n.  The first half
+// stops at n, the only value whose inverse has to be computed; the second half finishes from 1 / n.
+template <class F>
+struct Fp12InvT {
+    Fp2T<F> t0, t1, t2, D;
+    F n;
+    void first(const Fp12T<F>& f) {
+        const Fp6T<F> d = f.a * f.a - (f.b * f.b).mulv();
+        t0 = d.a.sq() - (d.b * d.c).xi();
+        t1 = d.c.sq().xi() - d.a * d.b;
+        t2 = d.b.sq() - d.a * d.c;
+        D = d.a * t0 + (d.c * t1 + d.b * t2).xi();
+        n = D.a.sq() + D.b.sq();
+    }
+    Fp12T<F> second(const Fp12T<F>& f, const F& ninv) const {
+        const Fp2T<F> Di = {D.a * ninv, (D.b * ninv).neg()};
+        const Fp6T<F> di = {t0 * Di, t1 * Di, t2 * Di};
+        const Fp6T<F> hb = f.b * di;
+        return {f.a * di, {hb.a.neg(), hb.b.neg(), hb.c.neg()}};
+    }
+};
+
 template <class F>
 struct MillerT {
     typedef Fp2T<F> E;
@@ -172,7 +206,8 @@ struct Program {
     static uint32_t enc(uint32_t op, uint32_t dst, uint32_t a, uint32_t b) { return op | dst << 2 | a << 12 | b << 22; }
 };
 // outputs: (node id, fixed slot it must end up in)
-inline Program levelize(const Tracer& t, const std::vector<std::pair<int, int>>& outputs) {
+// first_temp: the first slot temporaries may take (the final exponentiation keeps constants and saved values above N_FIXED)
+inline Program levelize(const Tracer& t, const std::vector<std::pair<int, int>>& outputs, int first_temp = N_FIXED) {
     const int n = (int)t.nodes.size();
     std::vector<char> live(n, 0);
     std::vector<int> stack;
@@ -233,7 +268,7 @@ inline Program levelize(const Tracer& t, const std::vector<std::pair<int, int>>&
     // its value's last reader, so no step reads and writes the same slot (lanes run the ops of a step in no order)
     std::vector<int> slot(n, -1);
     std::vector<int> free_list;
-    int next_slot = N_FIXED;
+    int next_slot = first_temp;
     std::vector<std::vector<int>> by_step(mov_step + 1), expiring(mov_step + 2);
     for (int v = 0; v < n; ++v) {
         if (!live[v]) continue;
@@ -368,6 +403,177 @@ inline bls::Fp12 miller_by_program(const bls::G1A& Pt, const bls::G2A& Q) {
     const bls::Fp* f = &sl[SLOT_F];
     bls::Fp12 r = {{{f[0], f[1]}, {f[2], f[3]}, {f[4], f[5]}}, {{f[6], f[7]}, {f[8], f[9]}, {f[10], f[11]}}};
     return r.conj();
+}
+
+// ---- the final exponentiation as programs -------------------------------------------------------------------------------
+// bls::final_exp (host/pairing.h) is a fixed sequence of Fp12 products, squarings, Frobenius maps, conjugations and one
+// inversion.  Each of those is a program here; the sequence itself is a schedule (final_exp_schedule below) that the host
+// interpreter and the device kernel k_final_exp (device/pairing.hpp) both walk.  Slots:
+//   0 ZERO | 1..12 F | 13..24 Y (second operand; between the halves of the inversion t0 t1 t2 D n) |
+//   25..34 gamma[1..5] | 35..39 gamma[i] conj(gamma[i]) | 40..75 three saved values of 12 | temporaries
+enum : int {
+    FE_T0 = SLOT_Y,          // 6: t0 t1 t2 of the Fp6 inversion
+    FE_D = SLOT_Y + 6,       // 2: its Fp2 norm
+    FE_N = SLOT_Y + 8,       // 1: the Fp norm, replaced by its inverse between the halves
+    FE_GAMMA = 25,           // 10
+    FE_NORM = 35,            // 5
+    FE_BANK = 40,            // 3 x 12
+    FE_N_BANKS = 3,
+    FE_FIRST_TEMP = FE_BANK + 12 * FE_N_BANKS,
+};
+struct FinalExpPrograms {
+    Program mul;    // F <- F * Y
+    Program sq;     // F <- F^2
+    Program frob;   // F <- F^p
+    Program frob2;  // F <- F^(p^2)
+    Program inv1;   // F -> t0 t1 t2 D n (FE_T0 .. FE_N); F stays
+    Program inv2;   // F <- F^-1 from those, with 1 / n in FE_N
+    uint32_t n_slots = 0;
+    const Program* all(int i) const {
+        const Program* p[6] = {&mul, &sq, &frob, &frob2, &inv1, &inv2};
+        return p[i];
+    }
+};
+inline const FinalExpPrograms& final_exp_programs() {
+    static const FinalExpPrograms P = [] {
+        FinalExpPrograms fp;
+        typedef std::vector<std::pair<int, int>> Outs;
+        auto in = [](Tracer& t, int s) { return S{t.input(s)}; };
+        auto trace = [&](Program& dst, auto&& body) {
+            Tracer t;
+            Tracer::cur() = &t;
+            Outs outs;
+            body(t, outs);
+            dst = levelize(t, outs, FE_FIRST_TEMP);
+        };
+        trace(fp.mul, [&](Tracer& t, Outs& o) { detail::out_f(o, detail::sym_f(t, SLOT_F) * detail::sym_f(t, SLOT_Y)); });
+        trace(fp.sq, [&](Tracer& t, Outs& o) { detail::out_f(o, detail::sym_f(t, SLOT_F).sq()); });
+        trace(fp.frob, [&](Tracer& t, Outs& o) {
+            Fp2T<S> g[5];
+            for (int i = 0; i < 5; ++i) g[i] = {in(t, FE_GAMMA + 2 * i), in(t, FE_GAMMA + 2 * i + 1)};
+            detail::out_f(o, frobenius_t(detail::sym_f(t, SLOT_F), g));
+        });
+        trace(fp.frob2, [&](Tracer& t, Outs& o) {
+            S n[5] = {in(t, FE_NORM), in(t, FE_NORM + 1), in(t, FE_NORM + 2), in(t, FE_NORM + 3), in(t, FE_NORM + 4)};
+            detail::out_f(o, frobenius2_t(detail::sym_f(t, SLOT_F), n));
+        });
+        trace(fp.inv1, [&](Tracer& t, Outs& o) {
+            Fp12InvT<S> h;
+            h.first(detail::sym_f(t, SLOT_F));
+            const S v[9] = {h.t0.a, h.t0.b, h.t1.a, h.t1.b, h.t2.a, h.t2.b, h.D.a, h.D.b, h.n};
+            for (int i = 0; i < 9; ++i) o.push_back({v[i].id, FE_T0 + i});
+        });
+        trace(fp.inv2, [&](Tracer& t, Outs& o) {
+            Fp12InvT<S> h;
+            h.t0 = {in(t, FE_T0), in(t, FE_T0 + 1)};
+            h.t1 = {in(t, FE_T0 + 2), in(t, FE_T0 + 3)};
+            h.t2 = {in(t, FE_T0 + 4), in(t, FE_T0 + 5)};
+            h.D = {in(t, FE_D), in(t, FE_D + 1)};
+            detail::out_f(o, h.second(detail::sym_f(t, SLOT_F), in(t, FE_N)));
+        });
+        Tracer::cur() = nullptr;
+        for (int i = 0; i < 6; ++i) fp.n_slots = std::max(fp.n_slots, fp.all(i)->n_slots);
+        return fp;
+    }();
+    return P;
+}
+// the 15 constants of the two Frobenius maps in slot order (FE_GAMMA .. FE_NORM + 4), from pairing_k()
+inline void final_exp_constants(bls::Fp* out15) {
+    const bls::Fp2* g = bls::pairing_k().gamma;
+    for (int i = 1; i <= 5; ++i) {
+        out15[2 * (i - 1)] = g[i].a;
+        out15[2 * (i - 1) + 1] = g[i].b;
+        out15[10 + i - 1] = g[i].a.sq() + g[i].b.sq();
+    }
+}
+
+// The driver: bls::final_exp as a SCHEDULE of four kinds of step over the slots — run a program; copy 12 slots (conjugating or
+// not); conjugate F in place; replace FE_N by its inverse unless it is zero.  The schedule is written once, here; the host
+// interpreter below and the device kernel k_final_exp (device/pairing.hpp) both walk it, so what the host tests is the order the
+// kernel runs.  word: kind | a << 2 | b << 12 | conj << 22
+//   t = conj(f) / f ; t = t^(p^2) t ; a = t^x conj(t) ; b = a^x conj(a) ; c = b^x b^p ; d = c^(x^2) conj(c) c^(p^2) ; d t^2 t
+enum : uint32_t { FE_RUN = 0, FE_COPY = 1, FE_CONJ = 2, FE_INVERT = 3 };
+enum : uint32_t { FE_P_MUL = 0, FE_P_SQ = 1, FE_P_FROB = 2, FE_P_FROB2 = 3, FE_P_INV1 = 4, FE_P_INV2 = 5 };
+inline const std::vector<uint32_t>& final_exp_schedule() {
+    static const std::vector<uint32_t> sched = [] {
+        std::vector<uint32_t> w;
+        enum { B0 = FE_BANK, B1 = FE_BANK + 12, B2 = FE_BANK + 24 };
+        auto run = [&](uint32_t p) { w.push_back(FE_RUN | p << 2); };
+        auto copy = [&](uint32_t dst, uint32_t src, bool conj = false) { w.push_back(FE_COPY | dst << 2 | src << 12 | (conj ? 1u << 22 : 0u)); };
+        auto mul_by = [&](uint32_t bank, bool conj = false) {
+            copy(SLOT_Y, bank, conj);
+            run(FE_P_MUL);
+        };
+        auto pow_x = [&] {  // F <- F^x (x < 0: the power by |x|, conjugated); the base stays in B1
+            copy(B1, SLOT_F);
+            for (int b = 62; b >= 0; --b) {
+                run(FE_P_SQ);
+                if ((0xd201000000010000ull >> b) & 1) mul_by(B1);
+            }
+            w.push_back(FE_CONJ);
+        };
+        copy(B0, SLOT_F);
+        run(FE_P_INV1);
+        w.push_back(FE_INVERT);
+        run(FE_P_INV2);
+        mul_by(B0, true);        // ^(p^6 - 1)
+        copy(B0, SLOT_F);
+        run(FE_P_FROB2);
+        mul_by(B0);              // ^(p^2 + 1)
+        copy(B0, SLOT_F);        // B0 = t from here on
+        pow_x();
+        mul_by(B1, true);        // a = t^x conj(t)
+        pow_x();
+        mul_by(B1, true);        // b = a^x conj(a)
+        pow_x();                 // b^x, B1 = b
+        copy(B2, SLOT_F);
+        copy(SLOT_F, B1);
+        run(FE_P_FROB);
+        mul_by(B2);              // c = b^p b^x
+        copy(B2, SLOT_F);        // B2 = c
+        pow_x();
+        pow_x();                 // c^(x^2)
+        mul_by(B2, true);
+        copy(B1, SLOT_F);
+        copy(SLOT_F, B2);
+        run(FE_P_FROB2);
+        mul_by(B1);              // d = c^(p^2) c^(x^2) conj(c)
+        copy(B1, SLOT_F);
+        copy(SLOT_F, B0);
+        run(FE_P_SQ);
+        mul_by(B0);              // t^3
+        mul_by(B1);
+        return w;
+    }();
+    return sched;
+}
+// the schedule on the host interpreter; sl: the slots with f in F and the constants in place.  false: the norm was zero
+inline bool run_final_exp_schedule(const FinalExpPrograms& fp, bls::Fp* sl) {
+    for (uint32_t w : final_exp_schedule()) {
+        const uint32_t kind = w & 3, a = (w >> 2) & 1023, b = (w >> 12) & 1023, conj = (w >> 22) & 1;
+        if (kind == FE_RUN) {
+            run_program(*fp.all((int)a), sl);
+        } else if (kind == FE_COPY) {
+            for (int i = 0; i < 12; ++i) sl[a + i] = conj && i >= 6 ? sl[b + i].neg() : sl[b + i];
+        } else if (kind == FE_CONJ) {
+            for (int i = 6; i < 12; ++i) sl[SLOT_F + i] = sl[SLOT_F + i].neg();
+        } else {
+            if (sl[FE_N].is_zero()) return false;
+            sl[FE_N] = sl[FE_N].inv();
+        }
+    }
+    return true;
+}
+// f^(3 (p^12 - 1) / r) through the programs; false for f of norm zero
+inline bool final_exp_by_program(const bls::Fp12& f, bls::Fp12& out) {
+    static_assert(sizeof(bls::Fp12) == 12 * sizeof(bls::Fp), "Fp12 is 12 packed residues in slot order");
+    const FinalExpPrograms& fp = final_exp_programs();
+    std::vector<bls::Fp> sl(fp.n_slots, bls::Fp::zero());
+    final_exp_constants(&sl[FE_GAMMA]);
+    memcpy(&sl[SLOT_F], &f, 12 * sizeof(bls::Fp));
+    if (!run_final_exp_schedule(fp, sl.data())) return false;
+    memcpy(&out, &sl[SLOT_F], 12 * sizeof(bls::Fp));
+    return true;
 }
 
 }  // namespace prog

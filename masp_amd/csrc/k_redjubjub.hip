@@ -97,6 +97,56 @@ struct RjCfg {
 };
 typedef Fe<RjCfg> Rj;
 
+// One lane per signature, no sum across lanes: items[i] = Rbar | vk | c | S (4 x 32 bytes; c = H*(Rbar || vk || sighash) reduced mod
+// r_J by the host), kinds[i] picks one of the two basepoint encodings at `bases`.  verdict[i] = 1 iff Rbar and vk decode (ZIP 216),
+// S < r_J and [8] (R + [c] vk - [S] G) = O: PublicKey::verify.  [c] vk - [S] G is one double-and-add over both scalars (the doublings
+// are shared; the three possible addends vk, -G, vk - G are ready before the loop), with the scalars shifted out of registers as in jj_mul.
+__global__ __launch_bounds__(64) void k_jj_verify_each(const uint4* __restrict__ items, const uint8_t* __restrict__ kinds, const uint4* __restrict__ bases,
+                                                       uint32_t n, uint8_t* __restrict__ verdict) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    auto words = [](const uint4* p, uint32_t* w) {
+        const uint4 a = p[0], b = p[1];
+        w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w; w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
+    };
+    uint32_t w[8], c[8], sc[8];
+    JExt R, vk, G;
+    words(items + 8 * (size_t)i, w);
+    bool ok = jj_decode(R, w) == JJ_OK;
+    words(items + 8 * (size_t)i + 2, w);
+    ok = (jj_decode(vk, w) == JJ_OK) && ok;
+    words(items + 8 * (size_t)i + 4, c);
+    words(items + 8 * (size_t)i + 6, sc);
+    bool s_ge = true;   // S >= r_J, decided at the first word that differs from the top
+    for (int k = 7; k >= 0; --k)
+        if (sc[k] != RjCfg::MOD[k]) {
+            s_ge = sc[k] > RjCfg::MOD[k];
+            break;
+        }
+    ok = ok && !s_ge;
+    words(bases + 2 * (kinds[i] ? 1 : 0), w);
+    ok = (jj_decode(G, w) == JJ_OK) && ok;
+    if (!ok) {
+        verdict[i] = 0;
+        return;
+    }
+    const JExt nG = {fe_neg(G.U), G.V, G.Z, fe_neg(G.T)}, both = jj_add(vk, nG);
+    JExt r = jj_identity();
+    for (int bit = 0; bit < 256; ++bit) {
+        const uint32_t cb = c[7] >> 31, sb = sc[7] >> 31;
+#pragma unroll
+        for (int k = 7; k > 0; --k) {
+            c[k] = (c[k] << 1) | (c[k - 1] >> 31);
+            sc[k] = (sc[k] << 1) | (sc[k - 1] >> 31);
+        }
+        c[0] <<= 1;
+        sc[0] <<= 1;
+        r = jj_dbl(r);
+        if (cb | sb) r = jj_add(r, cb && sb ? both : cb ? vk : nG);
+    }
+    verdict[i] = jj_is_identity(jj_mul_by_cofactor(jj_add(r, R))) ? 1 : 0;
+}
+
 Rj rj_words(const uint8_t* le32) {
     Rj a;
     memcpy(a.v, le32, 32);   // (little-endian host)
@@ -211,6 +261,43 @@ int masp_hip_redjubjub_verify_batch(masp_hip_ctx* ctx, size_t n, const uint8_t* 
     for (int st : status)
         if (st) return MASP_HIP_OK;   // an R or vk that does not decode: not valid
     *all_valid = out9[8] == 1;
+    return MASP_HIP_OK;
+}
+
+int masp_hip_redjubjub_verify_each(masp_hip_ctx* ctx, size_t n, const uint8_t* vks, const uint8_t* sigs, const uint8_t* sighashes,
+                                   const uint8_t* kinds, uint8_t* verdicts) {
+    if (!ctx || (n && (!vks || !sigs || !sighashes || !kinds || !verdicts)) || n > (1u << 20)) return MASP_HIP_E_INVALID_ARG;
+    for (size_t i = 0; i < n; ++i)
+        if (kinds[i] > 1) return MASP_HIP_E_INVALID_ARG;
+    if (n == 0) return MASP_HIP_OK;
+    // host: c_i = H*(Rbar_i || vk_i || sighash_i); items Rbar | vk | c | S, then the two basepoints
+    std::vector<uint8_t> items(128 * n + 64);
+    for (size_t i = 0; i < n; ++i) {
+        const uint8_t *sig = sigs + 64 * i, *vk = vks + 32 * i;
+        uint8_t* it = &items[128 * i];
+        memcpy(it, sig, 32);
+        memcpy(it + 32, vk, 32);
+        rj_store(it + 64, h_star(sig, vk, sighashes + 32 * i));
+        memcpy(it + 96, sig + 32, 32);
+    }
+    memcpy(&items[128 * n], basepoints(), 64);
+    const ApiLaunchScope api_scope;
+    ctx = FIRST_DEVICE(ctx);
+    std::shared_lock<std::shared_mutex> lock(ctx->mu);
+    std::lock_guard<std::mutex> jlock(ctx->jj_mu);
+    hipSetDevice(ctx->device);
+    hipStream_t s = ctx->streams.vk[1];
+    const uint32_t nn = (uint32_t)n;
+    int rc;
+    if ((rc = ctx->jj_points.upload(items.data(), items.size(), s)) || (rc = ctx->jj_scalars.upload(kinds, n, s)) || (rc = ctx->jj_partial.reserve(n)))
+        return fail(ctx, rc);
+    MASP_LAUNCH(k_jj_verify_each, dim3((nn + 63) / 64), dim3(64), 0, s, (const uint4*)ctx->jj_points.p, (const uint8_t*)ctx->jj_scalars.p,
+                (const uint4*)(ctx->jj_points.p + 128 * n), nn, ctx->jj_partial.p);
+    if (hipMemcpyAsync(verdicts, ctx->jj_partial.p, n, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        last_hip_error() = std::string("per-signature verification failed: ") + hipGetErrorString(hipGetLastError());
+        return fail(ctx, MASP_HIP_E_HIP);
+    }
+    if (launch_status() != MASP_HIP_OK) return fail(ctx, MASP_HIP_E_HIP);  // a refused launch: the bytes read back mean nothing
     return MASP_HIP_OK;
 }
 

@@ -27,10 +27,58 @@ struct masp_hip_vk {
     DevBuf<G1Xyzz> d_zc;
     DevBuf<int> d_status;
     DevBuf<Fp> d_f;
+    // masp_hip_verify_each (built by its first call, under mu): the final exponentiation's programs, schedule and constants, the
+    // key's own points in device form, and that call's work buffers
+    bool each_ready = false, each_lds_ok = false;
+    DevBuf<uint32_t> fe_ops, fe_steps, fe_sched;
+    DevBuf<PairingProgramDev> fe_prog;
+    DevBuf<Fp> fe_consts;          // 15 Frobenius constants, then conj(alpha_beta)
+    DevBuf<G2Affine> d_gamma_delta;
+    DevBuf<G1Affine> d_ic;         // IC_0, then per input the 64 x 15 multiples d 16^w IC_j
+    FinalExpDev fe{};
+    DevBuf<uint8_t> d_inputs, d_pre, d_verdict;
+    DevBuf<G1Affine> d_pp;
+    DevBuf<G2Affine> d_qp;
+    hipEvent_t each_ev[6] = {};    // around the stages of a chunk (masp_hip_verify_each_last_timing); created with the tables, destroyed with the key
+    double each_ms[5] = {0, 0, 0, 0, 0};
     hipStream_t stream = nullptr;  // verification runs next to the provers' batches, on one of the context's two verifier streams (not owned:
                                    // masp_hip_ctx::streams — created and kept off the batch streams' hardware queues with the context)
     std::mutex mu;                 // one verification at a time per key
 };
+
+namespace {
+
+constexpr size_t EACH_CHUNK = (size_t)1 << 16;  // proofs per pass of masp_hip_verify_each: bounds its scratch (2.6 KB per proof)
+
+// what masp_hip_verify_each needs beyond the batch call's, uploaded once per key.  Caller: ctx->mu shared, vk->mu held, device set.
+int prepare_each(masp_hip_ctx* ctx, masp_hip_vk* vk) {
+    if (vk->each_ready) return MASP_HIP_OK;
+    const FinalExpTables ft = final_exp_tables();
+    Fp consts[15 + 12];
+    memcpy(consts, ft.consts, sizeof(ft.consts));
+    const masp_host::bls::Fp12 ab = vk->vk.alpha_beta.conj();
+    memcpy(consts + 15, &ab, 12 * 48);
+    const G2Affine gd[2] = {dev_g2(vk->vk.gamma), dev_g2(vk->vk.delta)};
+    const std::vector<G1Affine> ic = ic_table(vk->vk);
+    hipStream_t s = vk->stream;
+    int rc;
+    if ((rc = vk->fe_ops.upload(ft.ops.data(), ft.ops.size(), s)) || (rc = vk->fe_steps.upload(ft.steps.data(), ft.steps.size(), s)) ||
+        (rc = vk->fe_sched.upload(ft.sched.data(), ft.sched.size(), s)) || (rc = vk->fe_consts.upload(consts, 27, s)) ||
+        (rc = vk->d_gamma_delta.upload(gd, 2, s)) || (rc = vk->d_ic.upload(ic.data(), ic.size(), s)) || (rc = vk->fe_prog.reserve(6)))
+        return rc;
+    PairingProgramDev progs[6];
+    for (int i = 0; i < 6; ++i) progs[i] = ft.dev(i, vk->fe_ops.p, vk->fe_steps.p);
+    if ((rc = vk->fe_prog.upload(progs, 6, s))) return rc;
+    HIP_TRY(hipStreamSynchronize(s));  // the host arrays above go out of scope
+    vk->fe = {vk->fe_prog.p, vk->fe_sched.p, (uint32_t)ft.sched.size(), ft.n_slots, vk->fe_consts.p};
+    for (hipEvent_t& e : vk->each_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    vk->each_lds_ok = hipFuncSetAttribute((const void*)k_final_exp, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;
+    vk->each_ready = true;
+    return MASP_HIP_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -74,6 +122,8 @@ int masp_hip_vk_prepare(masp_hip_ctx* ctx, const uint8_t* params, size_t params_
 void masp_hip_vk_free(masp_hip_vk* vk) {
     if (!vk) return;
     hipSetDevice(vk->device);
+    for (hipEvent_t e : vk->each_ev)
+        if (e) (void)hipEventDestroy(e);
     delete vk;
 }
 
@@ -136,6 +186,67 @@ int masp_hip_verify_batch(masp_hip_ctx* ctx, masp_hip_vk* vk, size_t n, const ui
     int v = masp_host::batch_verify_finish(vk->vk, n, public_inputs, n_public, z, f, csum);
     if (v < 0) return MASP_HIP_E_SCALAR_RANGE;
     *all_valid = v;
+    return MASP_HIP_OK;
+}
+
+int masp_hip_verify_each(masp_hip_ctx* ctx, masp_hip_vk* vk, size_t n, const uint8_t* proofs, const uint8_t* public_inputs, uint32_t n_public,
+                         uint8_t* verdicts) {
+    if (!ctx || !vk || (n && (!proofs || !verdicts || (n_public && !public_inputs))) || n > (1u << 20)) return MASP_HIP_E_INVALID_ARG;
+    if ((size_t)n_public + 1 != vk->vk.ic.size()) return MASP_HIP_E_PARAMS_SHAPE;
+    if (n == 0) return MASP_HIP_OK;
+    const ApiLaunchScope api_scope;
+    ctx = FIRST_DEVICE(ctx);
+    if (ctx->device != vk->device) return MASP_HIP_E_INVALID_ARG;
+    std::shared_lock<std::shared_mutex> lock(ctx->mu);  // concurrent with provers (and with verifications under other keys)
+    std::lock_guard<std::mutex> vlock(vk->mu);
+    hipSetDevice(ctx->device);
+    hipStream_t s = vk->stream;
+    int rc;
+    if ((rc = prepare_each(ctx, vk))) return fail(ctx, rc);
+    const uint32_t lds = vk->n_slots * 48, lds_fe = vk->fe.n_slots * 48;
+    if (!vk->lds_ok || !vk->each_lds_ok || lds > 64 * 1024 || lds_fe > 64 * 1024) {
+        last_hip_error() = "pairing interpreter: LDS configuration failed";
+        return fail(ctx, MASP_HIP_E_HIP);
+    }
+    for (double& t : vk->each_ms) t = 0;
+    for (size_t lo = 0; lo < n; lo += EACH_CHUNK) {
+        const size_t m = std::min(EACH_CHUNK, n - lo);
+        const uint32_t mm = (uint32_t)m;
+        hipEvent_t* ev = vk->each_ev;
+        HIP_TRY(hipEventRecord(ev[0], s));
+        if ((rc = vk->d_proofs.upload(proofs + 192 * lo, 192 * m, s)) ||
+            (rc = vk->d_inputs.upload(n_public ? public_inputs + 32 * (size_t)n_public * lo : nullptr, 32 * (size_t)n_public * m, s)) ||
+            (rc = vk->d_status.reserve(m)) || (rc = vk->d_pp.reserve(3 * m)) || (rc = vk->d_qp.reserve(3 * m)) || (rc = vk->d_f.reserve(36 * m)) ||
+            (rc = vk->d_pre.reserve(m)) || (rc = vk->d_verdict.reserve(m)))
+            return fail(ctx, rc);
+        HIP_TRY(hipMemsetAsync(vk->d_status.p, 0, sizeof(int) * m, s));
+        MASP_LAUNCH(k_verify_decode, dim3((mm + 63) / 64, 3), dim3(64), 0, s, vk->d_proofs.p, mm, vk->d_gamma_delta.p, vk->d_pp.p, vk->d_qp.p, vk->d_status.p);
+        HIP_TRY(hipEventRecord(ev[1], s));
+        MASP_LAUNCH(k_verify_acc, dim3((mm + 63) / 64), dim3(64), 0, s, vk->d_inputs.p, mm, n_public, vk->d_ic.p, vk->d_ic.p + 1, vk->d_status.p, vk->d_pp.p,
+                    vk->d_pre.p);
+        HIP_TRY(hipEventRecord(ev[2], s));
+        MASP_LAUNCH(k_miller_pairs, dim3(3 * mm), dim3(64), lds, s, vk->dbl, vk->add, vk->n_slots, vk->d_pp.p, vk->d_qp.p, vk->d_f.p);
+        HIP_TRY(hipEventRecord(ev[3], s));
+        MASP_LAUNCH(k_final_exp, dim3(mm), dim3(64), lds_fe, s, vk->fe, vk->d_f.p, 3u, vk->fe_consts.p + 15, vk->d_pre.p, (Fp*)nullptr, vk->d_verdict.p);
+        HIP_TRY(hipEventRecord(ev[4], s));
+        if (hipMemcpyAsync(verdicts + lo, vk->d_verdict.p, m, hipMemcpyDeviceToHost, s) != hipSuccess || hipEventRecord(ev[5], s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess) {
+            last_hip_error() = std::string("per-proof verification failed: ") + hipGetErrorString(hipGetLastError());
+            return fail(ctx, MASP_HIP_E_HIP);
+        }
+        if (launch_status() != MASP_HIP_OK) return fail(ctx, MASP_HIP_E_HIP);  // a refused launch: the bytes read back mean nothing
+        for (int k = 0; k < 5; ++k) {
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) vk->each_ms[k] += ms;
+        }
+    }
+    return MASP_HIP_OK;
+}
+
+int masp_hip_verify_each_last_timing(masp_hip_vk* vk, double ms[5]) {
+    if (!vk || !ms) return MASP_HIP_E_INVALID_ARG;
+    std::lock_guard<std::mutex> vlock(vk->mu);
+    for (int k = 0; k < 5; ++k) ms[k] = vk->each_ms[k];
     return MASP_HIP_OK;
 }
 

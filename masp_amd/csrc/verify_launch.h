@@ -1,9 +1,15 @@
 // Launch schedule of the batch verifier's last device stage, shared by masp_hip_verify_batch (k_verify.hip) and the test-side unit
 // tests/native/verify_dev.hip, so that the stage tests run the schedule that ships.  Only enqueues on `s`.
+// Below it: the host tables of masp_hip_verify_each (the final exponentiation's programs and schedule, the key's points in device
+// form), shared with tests/native/verify_each_dev.hip for the same reason.
 #pragma once
 #include <algorithm>
+#include <cstring>
+#include <vector>
 
 #include "device/pairing.hpp"
+#include "host/groth16_vk.h"
+#include "host/pairing_prog.h"
 #include "util.h"
 
 namespace masp {
@@ -14,6 +20,82 @@ inline void launch_fp12_product(hipStream_t s, const PairingProgramDev& mul12, u
     const uint32_t g = std::min<uint32_t>(n, 64);
     MASP_LAUNCH(k_fp12_product, dim3(g), dim3(64), lds, s, mul12, n_slots, vals, n, g);
     if (g > 1) MASP_LAUNCH(k_fp12_product, dim3(1), dim3(64), lds, s, mul12, n_slots, vals, g, 1u);
+}
+
+// ---- masp_hip_verify_each ---------------------------------------------------------------------------------------------------
+// host points -> device form.  Both sides keep Montgomery residues to the radix 2^384, so a coordinate is the same 48 bytes.
+inline G1Affine dev_g1(const masp_host::bls::G1A& p) {
+    G1Affine r;
+    if (p.inf) return {fe_zero<FpCfg>(), fe_zero<FpCfg>()};
+    memcpy(&r.x, &p.x, 48);
+    memcpy(&r.y, &p.y, 48);
+    return r;
+}
+inline G2Affine dev_g2(const masp_host::bls::G2A& p) {
+    G2Affine r;
+    if (p.inf) return {Fp2Ops::zero(), Fp2Ops::zero()};
+    memcpy(&r.x.c0, &p.x.a, 48);
+    memcpy(&r.x.c1, &p.x.b, 48);
+    memcpy(&r.y.c0, &p.y.a, 48);
+    memcpy(&r.y.c1, &p.y.b, 48);
+    return r;
+}
+// the Jacobian points of a table in affine form with ONE inversion (the product of all Z, unwound)
+inline void batch_affine(const std::vector<masp_host::bls::G1J>& in, G1Affine* out) {
+    namespace hb = masp_host::bls;
+    std::vector<hb::Fp> pre(in.size());
+    hb::Fp run = hb::Fp::one();
+    for (size_t i = 0; i < in.size(); ++i) {
+        pre[i] = run;
+        if (!in[i].Z.is_zero()) run = run * in[i].Z;
+    }
+    hb::Fp inv = run.inv();
+    for (size_t i = in.size(); i-- > 0;) {
+        if (in[i].Z.is_zero()) {
+            out[i] = dev_g1({hb::Fp::zero(), hb::Fp::zero(), true});
+            continue;
+        }
+        const hb::Fp zi = inv * pre[i], zi2 = zi.sq();
+        inv = inv * in[i].Z;
+        out[i] = dev_g1({in[i].X * zi2, in[i].Y * zi2 * zi, false});
+    }
+}
+
+// IC_0, then per public input j the 64 x 15 multiples d 16^w IC_j (PreparedVk::ic_tab) in affine form: k_verify_acc's `ic0` and `tab`
+inline std::vector<G1Affine> ic_table(const masp_host::PreparedVk& vk) {
+    const size_t n_public = vk.ic.size() - 1;
+    std::vector<G1Affine> ic(1 + 960 * n_public);
+    ic[0] = dev_g1(vk.ic[0]);
+    for (size_t j = 0; j < n_public; ++j) batch_affine(vk.ic_tab[j + 1], &ic[1 + 960 * j]);
+    return ic;
+}
+// the six programs of the final exponentiation concatenated (mul, sq, frob, frob2, inv1, inv2), its schedule and the 15 Frobenius
+// constants, as k_final_exp reads them
+struct FinalExpTables {
+    std::vector<uint32_t> ops, steps, sched;
+    size_t st_off[6];
+    uint32_t n_steps[6], n_slots;
+    Fp consts[15];
+    PairingProgramDev dev(int i, const uint32_t* d_ops, const uint32_t* d_steps) const { return {d_ops, d_steps + st_off[i], n_steps[i]}; }
+};
+inline FinalExpTables final_exp_tables() {
+    namespace mp = masp_host::prog;
+    const mp::FinalExpPrograms& fp = mp::final_exp_programs();
+    FinalExpTables t;
+    for (int i = 0; i < 6; ++i) {
+        const size_t op_off = t.ops.size();
+        t.st_off[i] = t.steps.size();
+        for (uint32_t s : fp.all(i)->step_start) t.steps.push_back(s + (uint32_t)op_off);  // absolute indices into the concatenation
+        t.ops.insert(t.ops.end(), fp.all(i)->ops.begin(), fp.all(i)->ops.end());
+        t.n_steps[i] = (uint32_t)fp.all(i)->step_start.size() - 1;
+    }
+    t.sched = mp::final_exp_schedule();
+    t.n_slots = fp.n_slots;
+    masp_host::bls::Fp c[15];
+    mp::final_exp_constants(c);
+    static_assert(sizeof(masp_host::bls::Fp) == sizeof(Fp), "one residue is 48 bytes on both sides");
+    memcpy(t.consts, c, sizeof(c));
+    return t;
 }
 
 }  // namespace masp

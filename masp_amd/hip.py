@@ -134,6 +134,10 @@ def load_library():
     L.masp_hip_vk_free.argtypes = [vp]
     L.masp_hip_vk_free.restype = None
     L.masp_hip_verify_batch.argtypes = [vp, vp, sz, vp, vp, u32, vp, C.POINTER(C.c_int)]
+    if hasattr(L, "masp_hip_verify_each"):
+        L.masp_hip_verify_each.argtypes = [vp, vp, sz, vp, vp, u32, C.c_char_p]
+        L.masp_hip_verify_each_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
+        L.masp_hip_redjubjub_verify_each.argtypes = [vp, sz, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]
     if hasattr(L, "masp_hip_redjubjub_verify_batch"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
         L.masp_hip_jubjub_msm.argtypes = [vp, sz, vp, vp, vp, C.POINTER(C.c_int64)]
         L.masp_hip_redjubjub_verify_batch.argtypes = [vp, sz, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int)]
@@ -373,6 +377,20 @@ class Context:
         ok = C.c_int(0)
         self._check(self._L.masp_hip_redjubjub_verify_batch(self._h, n, vks, sigs, sighashes, kinds, bytes(z), C.byref(ok)))
         return ok.value == 1
+
+    def redjubjub_verify_each(self, items):
+        """items as for redjubjub_verify_batch -> one bool per item: `redjubjub.verify` of each on its own (masp_hip_redjubjub_verify_each).
+        An item whose vk, signature or sighash has the wrong length is False."""
+        items = [tuple(it) for it in items]
+        shaped = [len(bytes(it[0])) == 32 and len(bytes(it[1])) == 64 and len(bytes(it[2])) == 32 for it in items]
+        sel = [it for it, ok in zip(items, shaped) if ok]
+        n = len(sel)
+        out = C.create_string_buffer(max(n, 1))
+        if n:
+            vks, sigs, sighashes = (b"".join(bytes(it[k]) for it in sel) for k in range(3))
+            self._check(self._L.masp_hip_redjubjub_verify_each(self._h, n, vks, sigs, sighashes, bytes(int(it[3]) for it in sel), out))
+        got = iter(out.raw[:n])
+        return [next(got) == 1 if ok else False for ok in shaped]
 
     def jubjub_msm(self, points, scalars):
         """sum_i [scalars_i] points_i over Jubjub (masp_hip_jubjub_msm): points = 32-byte encodings, scalars = ints below 2^256 or 32-byte
@@ -788,6 +806,27 @@ class GpuVerifyingKey:
             return False
         self._ctx._check(rc)
         return ok.value == 1
+
+    def verify_each(self, proofs, public_inputs):
+        """proofs and public_inputs as for verify_batch -> one verdict per proof (masp_hip_verify_each), what host.PreparedVerifyingKey's
+        masp_host_vk_verify says of it alone: 1 valid, 0 the pairing equation fails, 2 `Proof::read` refuses the proof, 3 a public input
+        >= r.  Deterministic.  Every proof is 192 bytes and has n_public inputs (ValueError otherwise: there is no verdict for those)."""
+        n = len(proofs)
+        if len(public_inputs) != n or any(len(pi) != self.n_public for pi in public_inputs) or any(len(bytes(p)) != 192 for p in proofs):
+            raise ValueError("verify_each: every proof is 192 bytes and comes with n_public inputs")
+        if n == 0:
+            return []
+        pr = np.frombuffer(b"".join(bytes(p) for p in proofs), dtype=np.uint8)
+        pi = np.frombuffer(b"".join(_scalar32(x) for row in public_inputs for x in row), dtype=np.uint8) if self.n_public else None
+        out = C.create_string_buffer(n)
+        self._ctx._check(self._ctx._L.masp_hip_verify_each(self._ctx._h, self._h, n, _p(pr), _p(pi), self.n_public, out))
+        return list(out.raw[:n])
+
+    def verify_each_last_timing(self):
+        """HIP-event milliseconds of the last verify_each: decode (with the copies in), acc, miller, final_exp, copy out"""
+        ms = (C.c_double * 5)()
+        self._ctx._check(self._ctx._L.masp_hip_verify_each_last_timing(self._h, ms))
+        return dict(zip(("decode", "acc", "miller", "final_exp", "copy_out"), ms))
 
     def close(self):
         if getattr(self, "_h", None) and getattr(self._ctx, "_h", None):

@@ -8,7 +8,8 @@ Types cross this API in their wire encodings, as in prover.py: Jubjub points as 
 ints or 32-byte little-endian values, proofs as 192 bytes, RedJubjub signatures as 64 bytes Rbar || Sbar.  A cv, rk or epk that does
 not decode (ZIP 216 rules) makes its bundle invalid, as the reference's deserialisation of the bundle would.  The consensus checks are
 host-side; `BatchValidator.validate` makes one RedJubjub batch call on the GPU (masp_hip_redjubjub_verify_batch) and one Groth16 batch
-call per non-empty circuit batch (masp_hip_verify_batch).
+call per non-empty circuit batch (masp_hip_verify_batch).  `BatchValidator.validate_each` says WHICH bundle is bad: the same queues
+through the per-item calls (masp_hip_redjubjub_verify_each, masp_hip_verify_each), one verdict per check_bundle call.
 """
 import secrets
 from dataclasses import dataclass
@@ -187,6 +188,10 @@ class BatchValidator:
         self._bundles_added = False
         self._proofs = {"spend": ([], []), "convert": ([], []), "output": ([], [])}
         self._signatures = []            # (vk, sig, sighash, kind)
+        self._bundles = []               # per check_bundle call: (what it returned, where its items start in the four queues)
+
+    def _queue_marks(self):
+        return (len(self._signatures),) + tuple(len(self._proofs[k][0]) for k in ("spend", "convert", "output"))
 
     def _queue_proof(self, kind, proof, public_inputs):
         self._proofs[kind][0].append(bytes(proof))
@@ -201,6 +206,12 @@ class BatchValidator:
         """batch.rs:78-193.  False if the bundle breaks a consensus rule checked here (a proof `Proof::read` refuses, a cv / rk / epk that
         does not decode or has small order, a bad value balance); what was queued before that stays queued, as in the reference."""
         self._bundles_added = True
+        start = self._queue_marks()
+        ok = self._check_bundle(bundle, sighash)
+        self._bundles.append((ok, start))
+        return ok
+
+    def _check_bundle(self, bundle, sighash):
         sighash = bytes(sighash)
         ctx = _Inner()
         for d in bundle.spends:
@@ -236,3 +247,27 @@ class BatchValidator:
             if proofs and not vk.verify_batch(proofs, inputs, randomness=rng(16 * len(proofs))):
                 return False
         return True
+
+    def validate_each(self, spend_vk, convert_vk, output_vk):
+        """One bool per check_bundle call, in order: True iff that call returned True and every signature and proof it queued verifies
+        on its own (Context.redjubjub_verify_each, GpuVerifyingKey.verify_each: no randomness, the answer is exact).  A mempool calls
+        this instead of `validate`; a block validator calls it once `validate` has said False, to name the transaction.  What a refused
+        bundle had queued before it was refused is not verified and counts against no other bundle.  `validate` is unaffected."""
+        ends = [start for _, start in self._bundles[1:]] + [self._queue_marks()]
+        spans = [(ok, start, end) for (ok, start), end in zip(self._bundles, ends)]
+        queues = [self._signatures] + [list(zip(*self._proofs[k])) for k in ("spend", "convert", "output")]
+        verdicts = []
+        for q, items in enumerate(queues):
+            # the items of the bundles check_bundle accepted, and where each sits in its queue
+            wanted = [i for ok, start, end in spans if ok for i in range(start[q], end[q])]
+            sel = [items[i] for i in wanted]
+            if not sel:
+                got = []
+            elif q == 0:
+                got = [bool(v) for v in self._ctx.redjubjub_verify_each(sel)]
+            else:
+                vk = (spend_vk, convert_vk, output_vk)[q - 1]
+                got = [v == 1 for v in vk.verify_each([p for p, _ in sel], [pi for _, pi in sel])]
+            assert len(got) == len(sel)
+            verdicts.append(dict(zip(wanted, got)))
+        return [ok and all(verdicts[q][i] for q in range(4) for i in range(start[q], end[q])) for ok, start, end in spans]
