@@ -109,14 +109,17 @@ typedef struct {
     int32_t witness_nontrivial_percent; /* share of a witness that is neither 0 nor 1, for window selection (default 30) */
     int32_t bucket_tree_levels;      /* levels of shared-inversion affine additions in front of the bucket accumulation of a batch
                                         (default 4, fewer for very short bucket runs); -1 = none (XYZZ accumulation only) */
-    int32_t bucket_tree_sub_batch;   /* proofs that go through the tree at a time (default 86: a 256-proof batch in three; its scratch is ~0.4 GB per Spend proof) */
+    int32_t bucket_tree_sub_batch;   /* proofs that go through the tree at a time, at most, for every MSM (its scratch is ~0.3 GB per Spend proof).  Default 0:
+                                        every MSM of a batch in as few equal sub-batches as fit the scratch that 86 proofs of ITS worst case would take
+                                        — the merged h + l MSM of 256 Spend proofs in three, the witness queries in one; masp_hip_ctx_get_options
+                                        reports the smallest in use */
     int32_t bucket_tree_levels_g2;   /* the same for the G2 MSM if it should differ (default: bucket_tree_levels) */
     int32_t bucket_tree_scratch_mb;  /* upper bound of the tree's scratch per slot in MiB (default 0: whatever the device gives).  If the
                                         scratch of a sub-batch does not fit — this bound, or the device is out of memory — the sub-batch
                                         is halved (down to 8 proofs), then the rest of the batch goes through the XYZZ accumulation: same
                                         bytes, fewer proofs per second, never an error */
     int32_t bucket_tree_fallback_proofs; /* OUTPUT of masp_hip_ctx_get_options (ignored on input): proofs whose bucket runs went through
-                                        the XYZZ accumulation for lack of tree scratch; bucket_tree_sub_batch there = the sub-batch in use now */
+                                        the XYZZ accumulation for lack of tree scratch, or for more entries than masp_hip_ctx_set_tree_entry_share allows; bucket_tree_sub_batch there = the sub-batch in use now */
     int32_t lone_proof_graph;        /* 1: a batch of fewer than 8 proofs replays a captured HIP graph of its ~250 launches from its third
                                         call on.  Default off: with ROCm 7.2 the replay of this five-stream graph takes 11.5 ms where the
                                         launches enqueued one by one take 5.7 (profiles/r04_lone_proof_graph_ab.txt); the bytes are the same */
@@ -193,6 +196,24 @@ int masp_hip_ctx_get_boolean_block_bits(const masp_hip_ctx* ctx, int32_t* out);
 #define MASP_HIP_QUOTIENT_COEFFICIENT 1
 int masp_hip_ctx_set_quotient_form(masp_hip_ctx* ctx, int32_t form);
 int masp_hip_ctx_get_quotient_form(const masp_hip_ctx* ctx, int32_t* out);
+/* The scratch of the bucket tree (masp_hip_options::bucket_tree_levels) is cut for the entries a witness can put into an MSM's digit list, not
+ * for every scalar at full width: one window digit per window for a quotient value, a coset evaluation, an input and a witness value that
+ * can be anything; one entry for a witness value that the R1CS proves boolean (masp_hip_r1cs_boolean_variables).  percent: of the witness
+ * values NOT proven boolean, the share taken to be full width — 1..100, 0 = the default (see MEASUREMENTS.md "Entry bound": the largest share
+ * observed over the three MASP circuits, a quarter added).  A proof with more entries than that is found on the device and goes through the
+ * XYZZ accumulation alone: the same bytes, counted in masp_hip_options::bucket_tree_fallback_proofs, never an error.  Applies to circuits
+ * loaded AFTER the call.  (A call and not a field of masp_hip_options, as masp_hip_ctx_set_boolean_block_bits.) */
+int masp_hip_ctx_set_tree_entry_share(masp_hip_ctx* ctx, int32_t percent);
+int masp_hip_ctx_get_tree_entry_share(const masp_hip_ctx* ctx, int32_t* out);
+/* out[v] = 1 for every variable v < n_inputs + n_aux that `cs` proves boolean — ONE, and every v with a constraint k v (c - c v) = 0 whose C
+ * row is empty (bellman's AllocatedBit) — else 0.  Host only: needs no device. */
+int masp_hip_r1cs_boolean_variables(const masp_hip_r1cs* cs, uint8_t* out);
+/* The entry bound of a base set of n points on windows of window_bits (2..16): ceil(256 / window_bits) entries for each scalar that can be full
+ * width — the n - n_witness that are no witness values and ceil((n_witness - n_boolean) share_percent / 100) more — and one for each of the
+ * others.  share_percent 0 = the default.  Host only; 0 for arguments out of range. */
+uint64_t masp_hip_tree_entry_bound(uint32_t n, int32_t window_bits, uint32_t n_witness, uint32_t n_boolean, int32_t share_percent);
+/* the entry bounds a loaded circuit's batch MSMs go by, and their window widths (may be NULL): the merged h + l set in use, a, b_g1, b_g2 */
+int masp_hip_circuit_tree_entry_bounds(const masp_hip_ctx* ctx, uint32_t slot, uint64_t bounds[4], int32_t window_bits[4]);
 /* number of device contexts behind `ctx` (1 for masp_hip_ctx_create) */
 int masp_hip_ctx_device_count(const masp_hip_ctx* ctx);
 /* counts[d] = proofs written so far by device context d (d < min(cap, masp_hip_ctx_device_count)): lets a caller (and the

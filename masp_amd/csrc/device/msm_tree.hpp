@@ -95,15 +95,38 @@ __device__ __forceinline__ void plane_st(F* __restrict__ base, size_t cap, size_
 // grid (T + 1, np), 1024 threads.  Level L = blockIdx.x of proof p = blockIdx.y:
 //   D[(L np + p)(nb + 1) + b] = sum_{b' < b} len_L(b')        (D[0] = start; D[L][nb] = points of level L)
 //   Q[(L np + p)(nb + 1) + b] = sum_{b' < b} len_L(b') >> 1   (Q[L][nb] = pairs of level L)
+// cap_ent: the entries per proof that the tree's views were cut for (msm_tree_enqueue).  The host's bounds of every level — points <=
+// E / 2^L + nb, pairs <= E / 2^(L+1) + nb / 2 — are sums over the buckets of ceil(len / 2^L) and of half that, so they hold for every
+// level of a proof exactly when its digit list has E <= cap_ent entries: that one comparison decides, the same in all T + 1 blocks of
+// the proof.  A proof over the capacity gets D = Q = 0 on every level (no points, no pairs: the records, both passes, the copies and
+// k_msm_accumulate_pts have nothing to index), its row of over_start = its `start` (else zeros: k_msm_accumulate over the digit list
+// then runs for such proofs alone) and one more in *over_count.  keep[p][b]: the offsets the bucket tails go by — level T's, or `start`.
 // (curve-independent kernels are `static`: the header is compiled into one translation unit per curve)
-static __global__ void __launch_bounds__(1024) k_tree_plan(const uint32_t* __restrict__ start, uint32_t nb, uint32_t* __restrict__ D, uint32_t* __restrict__ Q) {
+static __global__ void __launch_bounds__(1024)
+k_tree_plan(const uint32_t* __restrict__ start, uint32_t nb, uint32_t* __restrict__ D, uint32_t* __restrict__ Q, uint32_t cap_ent,
+            uint32_t* __restrict__ over_start, uint32_t* __restrict__ keep, uint32_t* __restrict__ over_count) {
     __shared__ uint32_t wsum[2][16];
     __shared__ uint32_t base[2];
     const uint32_t L = blockIdx.x, p = blockIdx.y, np = gridDim.y;
     start += (size_t)p * (nb + 1);
     uint32_t* Dl = D + ((size_t)L * np + p) * (nb + 1);
     uint32_t* Ql = Q + ((size_t)L * np + p) * (nb + 1);
+    over_start += (size_t)p * (nb + 1);
+    keep += (size_t)p * (nb + 1);
     const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, round = (1u << L) - 1u;
+    const bool over = start[nb] - start[0] > cap_ent, last = L + 1 == gridDim.x;
+    if (L == 0) {
+        for (uint32_t b = tid; b <= nb; b += blockDim.x) over_start[b] = over ? start[b] : 0u;
+        if (over && tid == 0 && over_count) atomicAdd(over_count, 1u);
+    }
+    if (over) {
+        for (uint32_t b = tid; b <= nb; b += blockDim.x) {
+            Dl[b] = 0;
+            Ql[b] = 0;
+            if (last) keep[b] = start[b];
+        }
+        return;
+    }
     if (tid == 0) base[0] = base[1] = 0;
     __syncthreads();
     for (uint32_t b0 = 0; b0 < nb; b0 += blockDim.x) {
@@ -133,6 +156,7 @@ static __global__ void __launch_bounds__(1024) k_tree_plan(const uint32_t* __res
         if (b < nb) {
             Dl[b] = bs0 + w0 + x0 - v0;
             Ql[b] = bs1 + w1 + x1 - v1;
+            if (last) keep[b] = bs0 + w0 + x0 - v0;
         }
         __syncthreads();
         if (tid == blockDim.x - 1) {
@@ -144,6 +168,7 @@ static __global__ void __launch_bounds__(1024) k_tree_plan(const uint32_t* __res
     if (tid == 0) {
         Dl[nb] = base[0];
         Ql[nb] = base[1];
+        if (last) keep[nb] = base[0];
     }
 }
 

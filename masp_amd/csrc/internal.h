@@ -34,6 +34,13 @@
 #define MASP_SUBSET_BITS 2
 #endif
 static_assert(MASP_SUBSET_BITS == 0 || MASP_SUBSET_BITS == 2 || MASP_SUBSET_BITS == 3, "subset blocks are 4 or 8 bases wide");
+// Of a query's witness scalars that the R1CS does not prove boolean, the percentage taken to be full width where the bucket tree's scratch
+// is sized (masp_hip_ctx_set_tree_entry_share, include/masp_hip.h).  MEASUREMENTS.md "Entry bound" has the shares observed over the three
+// circuits: the largest, 98 %, with a quarter on top is past 100, so the default is every one of them.
+#ifndef MASP_TREE_ENTRY_SHARE
+#define MASP_TREE_ENTRY_SHARE 100
+#endif
+static_assert(MASP_TREE_ENTRY_SHARE >= 1 && MASP_TREE_ENTRY_SHARE <= 100, "a percentage");
 
 
 namespace masp {
@@ -238,7 +245,7 @@ struct Slot {
         ws1.tree_levels = o.bucket_tree_levels;
         ws2.tree_levels = o.bucket_tree_levels_g2;
         ws1.tree_levels_shared = o.bucket_tree_levels_g2;  // B2 is reduced from B1's sort (ws1.sort): padded if either wants a tree
-        ws1.tree_sub = ws2.tree_sub = (uint32_t)o.bucket_tree_sub_batch;
+        ws1.tree_sub = ws2.tree_sub = (uint32_t)o.bucket_tree_sub_batch;   // (0: resolved per base set, msm_reduce_enqueue)
         ws2.tree.arena = &ws1.tree.own;   // the G1 and G2 MSMs of a batch follow each other on the slot's stream: one tree arena
         ws1.tree.own.limit = (size_t)o.bucket_tree_scratch_mb << 20;
         lone_graph = o.lone_proof_graph > 0;
@@ -341,6 +348,9 @@ struct masp_hip_ctx {
     int boolean_block_bits = MASP_SUBSET_BITS;
     // the quotient's form for circuits loaded from now on: 0 = evaluation form, 1 = coefficient form (masp_hip_ctx_set_quotient_form)
     int quotient_form = 0;
+    // of a query's witness scalars that the R1CS does not prove boolean, the percentage that the bucket tree's scratch takes to be full
+    // width, for circuits loaded from now on (masp_hip_ctx_set_tree_entry_share; the default: MASP_TREE_ENTRY_SHARE)
+    int tree_entry_share = MASP_TREE_ENTRY_SHARE;
     int n_slots = 4;          // = opt.slots
     size_t batch_cap = 256;   // = opt.batch_cap
     std::shared_mutex mu;

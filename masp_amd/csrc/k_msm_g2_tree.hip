@@ -3,6 +3,6 @@
 
 namespace masp {
 template struct MsmTreeWs<Fp2Ops>;
-template int msm_tree_enqueue<Fp2Ops, 192>(hipStream_t, const MsmBases<Fp2Ops, 192>&, const MsmSortBuf&, MsmTreeWs<Fp2Ops>&, uint32_t, uint32_t, uint32_t);
+template int msm_tree_enqueue<Fp2Ops, 192>(hipStream_t, const MsmBases<Fp2Ops, 192>&, const MsmSortBuf&, MsmTreeWs<Fp2Ops>&, uint32_t, uint32_t, uint32_t, uint32_t*, uint32_t*);
 template void msm_launch_accumulate_pts<Fp2Ops>(hipStream_t, const Fp2*, const Fp2*, size_t, const uint32_t*, uint32_t, uint32_t, Xyzz<Fp2Ops>*, uint32_t);
 }  // namespace masp

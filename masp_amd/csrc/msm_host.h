@@ -25,6 +25,21 @@ struct MsmBases {
     MsmGeom g{};
     uint32_t n = 0;
     uint32_t n_eff = 0;        // scalars expected to be neither 0 nor 1 (<= n): the mean length of a bucket's run follows from it
+    // Entries of the digit list that a proof's scalars can produce, the sort's padding not counted (0: n * W, every scalar full width).
+    // Fixed where the base set is loaded by a caller that knows its scalars (masp_hip_circuit_load: a witness is mostly boolean); it sizes
+    // the scratch of the bucket tree, which leaves a proof with more entries to the XYZZ accumulation (k_tree_plan) — never the sort.
+    uint64_t ent_bound = 0;
+    // W entries for each of the n_full scalars that can be full width, one for each of the others (0 none, 1 one: a digit of window 0)
+    static uint64_t entry_bound(uint32_t n_, const MsmGeom& g_, uint64_t n_full) {
+        n_full = std::min<uint64_t>(n_full, n_);
+        return n_full * (uint32_t)g_.W + (n_ - n_full);
+    }
+    // ... per proof of a sort padded to 2^pad_log entries per run: what the tree's views hold (<= MsmSortBuf::padded_entries)
+    size_t tree_entries(uint32_t pad_log) const {
+        const size_t unit = (size_t)1 << pad_log, worst = ((size_t)n * g.W + (size_t)g.nb * (unit - 1) + unit - 1) / unit * unit;
+        if (!ent_bound) return worst;
+        return std::min<size_t>(worst, ((size_t)ent_bound + (size_t)g.nb * (unit - 1) + unit - 1) / unit * unit);
+    }
     TabRow<O>* tab = nullptr;  // rows() rows of 128 / 256 bytes: g.W * n window rows, then the subset rows
     int import_status = 0;     // PT_* bits seen while decoding
     // Subset rows behind the window tables (MsmSubset, device/msm_geom.h): for the aligned blocks of 2^sub_bits consecutive bases that lie
@@ -199,8 +214,13 @@ struct MsmTreeWs {
     uint32_t q = 0, nb = 0, T = 0;
     size_t stride[2] = {0, 0};
     size_t pre_cap = 0;  // elements of the plane `pre`
+    // [q][nb + 1] the offsets of the digit list for the proofs whose entries exceed the views (k_tree_plan), zeros for the others: the
+    // XYZZ accumulation over the digit list reads them as its `start` and so runs for those proofs alone
+    uint32_t* over_start = nullptr;
     struct MsmProfile* prof = nullptr;  // set by msm_reduce_enqueue while a profiled MSM runs through the tree (MsmProfile::mark)
 
+    // E_ub: entries per proof the views hold (MsmBases::tree_entries)
+    static size_t scratch_bytes(uint64_t E_ub, uint32_t nb, uint32_t q, uint32_t T);  // [msm_tree_impl.hpp] what reserve() asks the arena for
     int reserve(uint64_t E_ub, uint32_t nb, uint32_t q, uint32_t T);                 // [msm_tree_impl.hpp]
     void batch_invert(hipStream_t s, const F* in, uint32_t n, F* out);              // [msm_tree_impl.hpp]
     const F* points_x() const { return px[T & 1]; }
@@ -220,12 +240,29 @@ struct MsmWorkspace {
 
     MsmSortBuf sort;  // used unless the caller shares another workspace's sort
     // batch-affine pre-reduction of the bucket runs (batches only): tree_levels < 0 off, 0 = the default (4, fewer for very
-    // short runs), else that many levels; tree_sub proofs go through the tree at a time (its scratch is ~0.4 GB per Spend proof)
+    // short runs), else that many levels; tree_sub proofs go through the tree at a time (its scratch is ~0.3 GB per Spend proof)
     MsmTreeWs<O> tree;
     int tree_levels = 0;
     int tree_levels_shared = -1;  // levels of another workspace that reduces THIS workspace's sort (B2 over B1's): it is padded for both
+    // tree_sub: 0 = the largest equal share of the batch (np, np / 2, np / 3, ...) whose scratch, cut for the base set's entry bound
+    // (MsmBases::ent_bound), fits what sub-batches of 86 proofs of the worst case would take — each base set resolved on its own
+    // (msm_reduce_enqueue); else a cap for every base set
     uint32_t tree_sub = 64;
+    uint32_t tree_sub_used = 0xffffffffu;  // the smallest sub-batch an MSM of this workspace has gone through the tree with
     uint64_t tree_fallbacks = 0;  // proofs whose bucket runs went to the XYZZ accumulation because the tree's scratch did not fit
+    // ... and those with more entries than the tree's views were cut for: counted on the device (k_tree_plan), mirrored into page-locked
+    // memory behind every MSM — read it once the stream has been synchronised
+    uint32_t* d_tree_over = nullptr;
+    uint32_t* h_tree_over = nullptr;
+    uint64_t tree_over() const { return h_tree_over ? *(volatile const uint32_t*)h_tree_over : 0; }
+    int reserve_tree_over(hipStream_t s) {
+        if (d_tree_over) return MASP_HIP_OK;
+        HIP_TRY(hipHostMalloc((void**)&h_tree_over, sizeof(uint32_t), hipHostMallocDefault));
+        *h_tree_over = 0;
+        HIP_TRY(dev_malloc(&d_tree_over, sizeof(uint32_t)));
+        HIP_TRY(hipMemsetAsync(d_tree_over, 0, sizeof(uint32_t), s));
+        return MASP_HIP_OK;
+    }
     uint32_t* startT = nullptr;  // [np][nb + 1] bucket offsets of the points the tree leaves
     size_t cap_nb = 0, cap_np = 0, cap_part = 0;  // cap_part: elements of `part` (np x (chunks + nb) of the largest launch)
     uint32_t *heavy = nullptr, *n_heavy = nullptr;
@@ -233,7 +270,11 @@ struct MsmWorkspace {
     Xyzz<O>* tsum = nullptr;
     Xyzz<O>* hparts = nullptr;  // [min(np, 7)][MSM_HEAVY_SLOTS]: the shares of a lone proof's heavy buckets
 
-    ~MsmWorkspace() { release(); }
+    ~MsmWorkspace() {
+        release();
+        if (d_tree_over) dev_free(d_tree_over);
+        if (h_tree_over) (void)hipHostFree(h_tree_over);
+    }
     void release() {
         void* ptrs[] = {heavy, n_heavy, part, bkt, S[0], S[1], T, R[0], R[1], tsum, startT, hparts};
         for (void* p : ptrs)
@@ -414,7 +455,8 @@ void msm_launch_accumulate(hipStream_t s, const TabRow<O>* tab, const uint32_t* 
 
 // Batch-affine pre-reduction (device/msm_tree.hpp) of proofs [p0, p0 + q) of the sort `sb`: T levels.   [msm_tree_impl.hpp]
 template <class O, int BYTES>
-int msm_tree_enqueue(hipStream_t s, const MsmBases<O, BYTES>& B, const MsmSortBuf& sb, MsmTreeWs<O>& tw, uint32_t p0, uint32_t q, uint32_t T);
+int msm_tree_enqueue(hipStream_t s, const MsmBases<O, BYTES>& B, const MsmSortBuf& sb, MsmTreeWs<O>& tw, uint32_t p0, uint32_t q, uint32_t T,
+                     uint32_t* keep_start, uint32_t* over_count);
 // k_msm_accumulate over explicit points instead of gathered table rows                                   [msm_tree_impl.hpp]
 template <class O>
 void msm_launch_accumulate_pts(hipStream_t s, const typename O::T* xs, const typename O::T* ys, size_t pt_stride, const uint32_t* start, uint32_t nb,

@@ -242,19 +242,34 @@ int msm_reduce_enqueue(hipStream_t s, const MsmBases<O, BYTES>& B, const MsmSort
     const uint32_t tree_T = sb.pad_log >= 1 ? msm_tree_levels(B.n_eff, g, np, ws.tree_levels) : 0;
     const uint32_t* start = sb.start;
     if (tree_T) {
-        uint32_t sub = std::max(1u, std::min(ws.tree_sub, np));
+        // may a proof have more entries than the tree's views are cut for?  (never with the worst case as the bound)
+        const bool bounded = sb.ent_stride > B.tree_entries(sb.pad_log);
+        if (bounded && (rc = ws.reserve_tree_over(s))) return rc;
+        uint32_t sub = std::max(1u, std::min(ws.tree_sub ? ws.tree_sub : 256u, np));
+        if (!ws.tree_sub) {
+            // automatic: the batch in as few equal shares as fit the arena that sub-batches of 86 worst-case proofs would take (or
+            // the arena as it is, or its limit) — the views are cut for the base set's entry bound, so a witness MSM goes in one
+            const MsmTreeArena& ar = *ws.tree.arena;
+            const size_t budget = ar.limit ? ar.limit : std::max(ar.cap, MsmTreeWs<O>::scratch_bytes(sb.ent_stride, nb, std::min(86u, np), tree_T));
+            const uint64_t E = std::min<uint64_t>(sb.ent_stride, B.tree_entries(sb.pad_log));
+            for (uint32_t k = 1;; ++k) {
+                sub = (np + k - 1) / k;
+                if (sub <= 8 || MsmTreeWs<O>::scratch_bytes(E, nb, sub, tree_T) <= budget) break;
+            }
+        }
         ws.tree.prof = prof;
         for (uint32_t p0 = 0; p0 < np;) {
             uint32_t q = std::min(sub, np - p0);
-            rc = msm_tree_enqueue<O, BYTES>(s, B, sb, ws.tree, p0, q, tree_T);
-            // the tree's scratch (~0.4 GB per Spend proof) does not fit — a smaller GPU, more slots, a second prover on the device:
+            uint32_t* const keep = ws.startT + (size_t)p0 * (nb + 1);
+            rc = msm_tree_enqueue<O, BYTES>(s, B, sb, ws.tree, p0, q, tree_T, keep, ws.d_tree_over);
+            // the tree's scratch (~0.3 GB per Spend proof) does not fit — a smaller GPU, more slots, a second prover on the device:
             // halve the sub-batch (and keep it so: the next batch does not try again), below 8 proofs leave the rest of the
             // batch to the XYZZ accumulation over the digit list (it skips the padding entries)
             while (rc == MASP_HIP_E_TREE_SCRATCH && sub > 8) {
                 sub = std::max(8u, sub / 2);
                 ws.tree_sub = sub;
                 q = std::min(sub, np - p0);
-                rc = msm_tree_enqueue<O, BYTES>(s, B, sb, ws.tree, p0, q, tree_T);
+                rc = msm_tree_enqueue<O, BYTES>(s, B, sb, ws.tree, p0, q, tree_T, keep, ws.d_tree_over);
             }
             if (rc == MASP_HIP_E_TREE_SCRATCH) {
                 const uint32_t rest = np - p0;
@@ -266,14 +281,19 @@ int msm_reduce_enqueue(hipStream_t s, const MsmBases<O, BYTES>& B, const MsmSort
                 break;
             }
             if (rc) return rc;
+            ws.tree_sub_used = std::min(ws.tree_sub_used, sub);
+            // (the bucket tails run over the whole batch: k_tree_plan left this sub-batch's offsets in ws.startT)
             msm_launch_accumulate_pts<O>(s, ws.tree.points_x(), ws.tree.points_y(), ws.tree.point_stride(), ws.tree.plan_D(tree_T), nb, nchunks,
                                          ws.part + (size_t)p0 * ((size_t)nchunks + nb), q);
+            // the proofs with more entries than the views hold (none for a witness within MsmBases::ent_bound): the XYZZ accumulation over
+            // their digit lists — over_start is all zeros for every other proof, whose lanes leave at once
+            if (bounded)
+                msm_launch_accumulate<O>(s, B.tab, sb.sorted + (size_t)p0 * sb.ent_stride, sb.ent_stride, ws.tree.over_start, nb, nchunks,
+                                         ws.part + (size_t)p0 * ((size_t)nchunks + nb), q);
             if (prof) prof->mark(s, MsmProfile::PH_ACC);
-            // the bucket tails run over the whole batch: keep this sub-batch's offsets (the next one overwrites the plan)
-            HIP_TRY(hipMemcpyAsync(ws.startT + (size_t)p0 * (nb + 1), ws.tree.plan_D(tree_T), sizeof(uint32_t) * q * (nb + 1), hipMemcpyDeviceToDevice, s));
-            if (prof) prof->mark(s, MsmProfile::PH_PLAN);
             p0 += q;
         }
+        if (bounded) HIP_TRY(hipMemcpyAsync(ws.h_tree_over, ws.d_tree_over, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         ws.tree.prof = nullptr;
         start = ws.startT;
     } else {

@@ -31,45 +31,63 @@ static inline uint32_t tree_lanes(uint64_t E_ub, uint32_t nb, uint32_t L) {
     return std::max<uint32_t>(256u, ((pairs + MSM_TREE_KP - 1) / MSM_TREE_KP + 255u) & ~255u);
 }
 
+// the views of the arena for q proofs of at most E_ub entries each (the padding included): byte offsets, every view 256-byte aligned
+template <class O>
+struct MsmTreeLayout {
+    typedef typename O::T F;
+    size_t pres, total;
+    size_t oD, oQ, oOver, oRec, oPre, oTp, oTinv, oBpre, oBtot, oBitot, oBpre2, oX1, oY1, oX0, oY0;
+    MsmTreeLayout(uint64_t E_ub, uint32_t nb, uint32_t q, uint32_t T) {
+        constexpr uint32_t BINV_C = MsmTreeWs<O>::BINV_C;
+        const size_t plan = (size_t)(T + 1) * q * (nb + 1);
+        const size_t recs = (size_t)q * tree_pairs_ub(E_ub, nb, 1);
+        const size_t NT0 = tree_lanes(E_ub, nb, 0);
+        const size_t lanes = (size_t)q * NT0;
+        // pre[(j q + p) NT + t], j < ceil(pairs / NT) <= KP (+1 for the rounding of NT): bounded by level 0
+        pres = (size_t)((tree_pairs_ub(E_ub, nb, 0) + NT0 - 1) / NT0) * lanes;
+        const size_t pts1 = (size_t)q * tree_points_ub(E_ub, nb, 1), pts2 = T >= 2 ? (size_t)q * tree_points_ub(E_ub, nb, 2) : 0;
+        const size_t m1 = (lanes + BINV_C - 1) / BINV_C;
+        size_t off = 0;
+        auto take = [&](size_t bytes) {
+            const size_t at = off;
+            off += (bytes + 255) & ~(size_t)255;
+            return at;
+        };
+        oD = take(4 * plan), oQ = take(4 * plan), oOver = take(4 * (size_t)q * (nb + 1)), oRec = take(sizeof(uint2) * recs), oPre = take(sizeof(F) * pres),
+        oTp = take(sizeof(F) * lanes), oTinv = take(sizeof(F) * lanes), oBpre = take(sizeof(F) * lanes), oBtot = take(sizeof(F) * m1),
+        oBitot = take(sizeof(F) * m1), oBpre2 = take(sizeof(F) * m1), oX1 = take(sizeof(F) * pts1), oY1 = take(sizeof(F) * pts1),
+        oX0 = take(sizeof(F) * pts2), oY0 = take(sizeof(F) * pts2);
+        total = off;
+    }
+};
+
+template <class O>
+size_t MsmTreeWs<O>::scratch_bytes(uint64_t E_ub, uint32_t nb, uint32_t q, uint32_t T) {
+    return MsmTreeLayout<O>(E_ub, nb, q, T).total;
+}
+
 template <class O>
 int MsmTreeWs<O>::reserve(uint64_t E_ub, uint32_t nb, uint32_t q, uint32_t T) {
-    const size_t plan = (size_t)(T + 1) * q * (nb + 1);
-    const size_t recs = (size_t)q * tree_pairs_ub(E_ub, nb, 1);
-    const size_t NT0 = tree_lanes(E_ub, nb, 0);
-    const size_t lanes = (size_t)q * NT0;
-    // pre[(j q + p) NT + t], j < ceil(pairs / NT) <= KP (+1 for the rounding of NT): bounded by level 0
-    const size_t pres = (size_t)((tree_pairs_ub(E_ub, nb, 0) + NT0 - 1) / NT0) * lanes;
-    pre_cap = pres;
-    const size_t pts1 = (size_t)q * tree_points_ub(E_ub, nb, 1), pts2 = T >= 2 ? (size_t)q * tree_points_ub(E_ub, nb, 2) : 0;
-    const size_t m1 = (lanes + BINV_C - 1) / BINV_C;
-    // carve: every view 256-byte aligned
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
-    const size_t oD = take(4 * plan), oQ = take(4 * plan), oRec = take(sizeof(uint2) * recs), oPre = take(sizeof(F) * pres), oTp = take(sizeof(F) * lanes),
-                 oTinv = take(sizeof(F) * lanes), oBpre = take(sizeof(F) * lanes), oBtot = take(sizeof(F) * m1), oBitot = take(sizeof(F) * m1),
-                 oBpre2 = take(sizeof(F) * m1), oX1 = take(sizeof(F) * pts1), oY1 = take(sizeof(F) * pts1), oX0 = take(sizeof(F) * pts2),
-                 oY0 = take(sizeof(F) * pts2);
-    int rc = arena->reserve(off);
+    const MsmTreeLayout<O> l(E_ub, nb, q, T);
+    int rc = arena->reserve(l.total);
     if (rc) return rc;
+    pre_cap = l.pres;
     uint8_t* b = arena->p;
-    D = (uint32_t*)(b + oD);
-    Q = (uint32_t*)(b + oQ);
-    rec = (uint2*)(b + oRec);
-    pre = (F*)(b + oPre);
-    tp = (F*)(b + oTp);
-    tinv = (F*)(b + oTinv);
-    bpre = (F*)(b + oBpre);
-    btot = (F*)(b + oBtot);
-    bitot = (F*)(b + oBitot);
-    bpre2 = (F*)(b + oBpre2);
-    px[1] = (F*)(b + oX1);
-    py[1] = (F*)(b + oY1);
-    px[0] = (F*)(b + oX0);
-    py[0] = (F*)(b + oY0);
+    D = (uint32_t*)(b + l.oD);
+    Q = (uint32_t*)(b + l.oQ);
+    over_start = (uint32_t*)(b + l.oOver);
+    rec = (uint2*)(b + l.oRec);
+    pre = (F*)(b + l.oPre);
+    tp = (F*)(b + l.oTp);
+    tinv = (F*)(b + l.oTinv);
+    bpre = (F*)(b + l.oBpre);
+    btot = (F*)(b + l.oBtot);
+    bitot = (F*)(b + l.oBitot);
+    bpre2 = (F*)(b + l.oBpre2);
+    px[1] = (F*)(b + l.oX1);
+    py[1] = (F*)(b + l.oY1);
+    px[0] = (F*)(b + l.oX0);
+    py[0] = (F*)(b + l.oY0);
     return MASP_HIP_OK;
 }
 
@@ -94,15 +112,21 @@ void MsmTreeWs<O>::batch_invert(hipStream_t s, const F* in, uint32_t n, F* out) 
 // T levels of pairwise affine additions over the digit lists of proofs [p0, p0 + q) of the sort `sb`.  Afterwards the points of
 // proof p0 + i lie at points_x() / points_y() + i * point_stride(), bucket b of it at [DT[b], DT[b + 1]) with
 // DT = plan_D(T) + i * (nb + 1).  No host synchronisation.
+// The views hold B.tree_entries() entries per proof, which may be fewer than the sort's stride.  A proof with more is decided on the
+// device (k_tree_plan): it has no points and no pairs on any level, so every kernel of the tree and k_msm_accumulate_pts pass it by,
+// its row of tw.over_start holds the digit list's own offsets (zeros for every other proof) and *over_count is one higher.
+// keep_start: [q][nb + 1] the offsets the bucket tails go by — DT, or the digit list's for such a proof.
 template <class O, int BYTES>
-int msm_tree_enqueue(hipStream_t s, const MsmBases<O, BYTES>& B, const MsmSortBuf& sb, MsmTreeWs<O>& tw, uint32_t p0, uint32_t q, uint32_t T) {
+int msm_tree_enqueue(hipStream_t s, const MsmBases<O, BYTES>& B, const MsmSortBuf& sb, MsmTreeWs<O>& tw, uint32_t p0, uint32_t q, uint32_t T,
+                     uint32_t* keep_start, uint32_t* over_count) {
     typedef typename O::T F;
     const uint32_t nb = (uint32_t)B.g.nb;
     if (sb.pad_log < 1) {
         last_hip_error() = "msm_tree_enqueue: the sort must pad every run to an even length (MsmSortBuf::pad_log >= 1)";
         return MASP_HIP_E_INVALID_ARG;
     }
-    const uint64_t E_ub = sb.ent_stride;  // entries per proof, the padding included
+    // entries per proof the views are cut for, the padding included: every bound of a level below follows from it
+    const uint64_t E_ub = std::min<uint64_t>(sb.ent_stride, B.tree_entries(sb.pad_log));
     int rc = tw.reserve(E_ub, nb, q, T);
     if (rc) return rc;
     tw.q = q;
@@ -110,11 +134,11 @@ int msm_tree_enqueue(hipStream_t s, const MsmBases<O, BYTES>& B, const MsmSortBu
     tw.T = T;
     tw.stride[1] = tree_points_ub(E_ub, nb, 1);
     tw.stride[0] = tree_points_ub(E_ub, nb, 2);
-    const size_t ent_stride = E_ub;
+    const size_t ent_stride = sb.ent_stride;  // of the digit list: the sort keeps room for the worst case
     const uint32_t* sorted = sb.sorted + (size_t)p0 * ent_stride;
     const uint32_t* start = sb.start + (size_t)p0 * (nb + 1);
     MsmProfile* const prof = tw.prof;
-    MASP_LAUNCH(k_tree_plan, dim3(T + 1, q), dim3(1024), 0, s, start, nb, tw.D, tw.Q);
+    MASP_LAUNCH(k_tree_plan, dim3(T + 1, q), dim3(1024), 0, s, start, nb, tw.D, tw.Q, (uint32_t)E_ub, tw.over_start, keep_start, over_count);
     if (prof) prof->mark(s, MsmProfile::PH_PLAN);
     const size_t lvl = (size_t)q * (nb + 1);
     const size_t rec_stride = tree_pairs_ub(E_ub, nb, 1);

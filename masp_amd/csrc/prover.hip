@@ -53,7 +53,8 @@ static masp_hip_options resolve_options(const masp_hip_options* in) {
     // ~30 % of a MASP witness is neither 0 nor 1; measured +3..5 % throughput vs 100
     o.witness_nontrivial_percent = o.witness_nontrivial_percent > 0 ? std::min<int>(o.witness_nontrivial_percent, 100) : 30;
     o.bucket_tree_levels = o.bucket_tree_levels > 0 ? std::min<int>(o.bucket_tree_levels, 12) : o.bucket_tree_levels < 0 ? -1 : 0;  // resolved: 0 = automatic
-    o.bucket_tree_sub_batch = o.bucket_tree_sub_batch > 0 ? std::min<int>(o.bucket_tree_sub_batch, 256) : 86;   // a 256-proof batch in three sub-batches
+    // resolved: 0 = automatic — every base set in as few equal sub-batches as its bounded scratch allows (MsmWorkspace::tree_sub); a value caps them all
+    o.bucket_tree_sub_batch = o.bucket_tree_sub_batch > 0 ? std::min<int>(o.bucket_tree_sub_batch, 256) : 0;
     o.bucket_tree_levels_g2 = o.bucket_tree_levels_g2 > 0 ? std::min<int>(o.bucket_tree_levels_g2, 12) : o.bucket_tree_levels_g2 < 0 ? -1 : o.bucket_tree_levels;
     o.bucket_tree_scratch_mb = std::max(o.bucket_tree_scratch_mb, 0);
     o.bucket_tree_fallback_proofs = 0;   // output only
@@ -65,6 +66,101 @@ static masp_hip_options resolve_options(const masp_hip_options* in) {
     o.window_bits_b2 = o.window_bits_b2 > 0 ? std::max(2, std::min<int>(o.window_bits_b2, 16)) : o.window_bits_b2 < 0 ? -1 : 0;
     return o;
 }
+// ---- what a witness can put into a digit list --------------------------------------------------------------------------------
+// out[v] = 1 where the R1CS proves variable v boolean, by the constraints bellman's boolean gadgets leave:
+//   ONE itself;
+//   k v (c - c v) = 0, the C row empty (AllocatedBit::alloc): one of the A and B rows the single term v, the other ONE and v with
+//     coefficients that cancel;
+//   f(x) g(y) = z with f, g each t or 1 - t over variables already proven boolean (AllocatedBit::and, and_not, nor);
+//   2 x y = x + y - z over such variables (AllocatedBit::xor).
+// Such a scalar is 0 or 1 in every satisfying witness: at most one entry of a digit list, whatever the window width.  (Passes over the
+// constraints until nothing changes: a gadget's operands are allocated before its result, so the second pass finds nothing new.)
+static void r1cs_boolean_variables(const masp_hip_r1cs* cs, uint8_t* out) {
+    // r, little-endian: two canonical non-zero coefficients cancel exactly when their sum as integers is r
+    static const uint8_t R_LE[32] = {0x01, 0x00, 0x00, 0x00, 0xff, 0xff, 0xff, 0xff, 0xfe, 0x5b, 0xfe, 0xff, 0x02, 0xa4, 0xbd, 0x53,
+                                     0x05, 0xd8, 0xa1, 0x09, 0x08, 0xd8, 0x39, 0x33, 0x48, 0x7d, 0x9d, 0x29, 0x53, 0xa7, 0xed, 0x73};
+    static const uint8_t ONE_LE[32] = {1};
+    const uint32_t nv = cs->n_inputs + cs->n_aux, NONE = 0xffffffffu;
+    memset(out, 0, nv);
+    out[0] = 1;
+    auto cancel = [&](const uint8_t* x, const uint8_t* y) {
+        unsigned carry = 0;
+        for (int i = 0; i < 32; ++i) {
+            const unsigned t = (unsigned)x[i] + y[i] + carry;
+            if ((uint8_t)t != R_LE[i]) return false;
+            carry = t >> 8;
+        }
+        return carry == 0;
+    };
+    auto small = [&](const uint8_t* x, uint8_t k) {
+        if (x[0] != k) return false;
+        for (int i = 1; i < 32; ++i)
+            if (x[i]) return false;
+        return true;
+    };
+    auto minus_one = [&](const uint8_t* x) { return cancel(x, ONE_LE); };
+    const uint32_t* rp[3] = {cs->a_rowptr, cs->b_rowptr, cs->c_rowptr};
+    const uint32_t* cl[3] = {cs->a_col, cs->b_col, cs->c_col};
+    const uint8_t* cf[3] = {cs->a_coef, cs->b_coef, cs->c_coef};
+    auto len = [&](int mi, uint32_t i) { return rp[mi][i + 1] - rp[mi][i]; };
+    auto col = [&](int mi, uint32_t i, uint32_t k) { return cl[mi][rp[mi][i] + k]; };
+    auto coef = [&](int mi, uint32_t i, uint32_t k) { return cf[mi] + 32 * (size_t)(rp[mi][i] + k); };
+    // row i of matrix mi as t or 1 - t: the variable t (not ONE), else NONE
+    auto form = [&](int mi, uint32_t i) -> uint32_t {
+        if (len(mi, i) == 1) return col(mi, i, 0) != 0 && small(coef(mi, i, 0), 1) ? col(mi, i, 0) : NONE;
+        if (len(mi, i) != 2) return NONE;
+        for (uint32_t k = 0; k < 2; ++k)
+            if (col(mi, i, k) == 0 && col(mi, i, k ^ 1) != 0 && small(coef(mi, i, k), 1) && minus_one(coef(mi, i, k ^ 1))) return col(mi, i, k ^ 1);
+        return NONE;
+    };
+    for (int pass = 0; pass < 8; ++pass) {
+        bool changed = false;
+        auto prove = [&](uint32_t v) {
+            if (v < nv && !out[v]) {
+                out[v] = 1;
+                changed = true;
+            }
+        };
+        for (uint32_t i = 0; i < cs->n_constraints; ++i) {
+            if (len(2, i) == 0) {
+                for (int one = 0; one < 2; ++one) {   // `one`: the matrix with the single term
+                    const int two = one ^ 1;
+                    if (len(one, i) != 1 || len(two, i) != 2) continue;
+                    const uint32_t v = col(one, i, 0), x = col(two, i, 0), y = col(two, i, 1);
+                    if (v == 0 || v >= nv || !((x == 0 && y == v) || (x == v && y == 0))) continue;
+                    if (cancel(coef(two, i, 0), coef(two, i, 1))) prove(v);
+                }
+            } else if (len(2, i) == 1) {
+                const uint32_t z = col(2, i, 0), x = form(0, i), y = form(1, i);
+                if (z != 0 && small(coef(2, i, 0), 1) && x != NONE && y != NONE && x < nv && y < nv && out[x] && out[y]) prove(z);
+            } else if (len(2, i) == 3 && len(0, i) == 1 && len(1, i) == 1) {
+                const uint32_t x = col(0, i, 0), y = col(1, i, 0);
+                if (x == 0 || y == 0 || x == y || x >= nv || y >= nv || !out[x] || !out[y] || !small(coef(0, i, 0), 2) || !small(coef(1, i, 0), 1)) continue;
+                uint32_t z = NONE;
+                bool ok = true, sx = false, sy = false;
+                for (uint32_t k = 0; k < 3; ++k) {
+                    const uint32_t v = col(2, i, k);
+                    if (v == x && small(coef(2, i, k), 1)) sx = true;
+                    else if (v == y && small(coef(2, i, k), 1)) sy = true;
+                    else if (v != 0 && z == NONE && minus_one(coef(2, i, k))) z = v;
+                    else ok = false;
+                }
+                if (ok && sx && sy && z != NONE) prove(z);
+            }
+        }
+        if (!changed) break;
+    }
+}
+// The entry bound of a base set of n points on windows of `window_bits` (MsmBases::ent_bound): n_witness of its scalars are witness values,
+// n_boolean of those proven boolean, and of the rest share_percent in a hundred can be full width — like every scalar that is no witness value
+static uint64_t tree_entry_bound(uint32_t n, int window_bits, uint32_t n_witness, uint32_t n_boolean, int share_percent) {
+    n_witness = std::min(n_witness, n);
+    n_boolean = std::min(n_boolean, n_witness);
+    const uint64_t rest = n_witness - n_boolean;
+    const uint64_t n_full = (n - n_witness) + (rest * (uint64_t)share_percent + 99) / 100;
+    return BasesG1::entry_bound(n, msm_geom(window_bits), n_full);
+}
+
 // [0, n) cut into ceil(n / cap) groups whose sizes differ by at most one: (first, count) pairs
 static std::vector<std::pair<size_t, size_t>> even_groups(size_t n, size_t cap) {
     std::vector<std::pair<size_t, size_t>> out;
@@ -777,13 +873,17 @@ int masp_hip_ctx_get_options(const masp_hip_ctx* ctx, masp_hip_options* out) {
     out = &full;
     // what lack of tree scratch has changed since the context was created: the smallest sub-batch any slot works with now, and
     // the proofs whose bucket runs went through the XYZZ accumulation instead (all device contexts)
+    // (bucket_tree_sub_batch automatic: the smallest sub-batch any MSM has gone through the tree with, 256 before the first)
     uint64_t fb = 0;
-    int sub = out->bucket_tree_sub_batch;
+    int sub = out->bucket_tree_sub_batch ? out->bucket_tree_sub_batch : 256;
     auto scan = [&](const masp_hip_ctx* d) {
         std::lock_guard<std::mutex> g(d->slot_mu);
         for (const auto& sl : d->slots) {
-            fb += sl->ws1.tree_fallbacks + sl->ws2.tree_fallbacks;
-            sub = std::min<int>(sub, (int)std::min(sl->ws1.tree_sub, sl->ws2.tree_sub));
+            // (tree_over: proofs with more entries than the tree's views were cut for, counted on the device — exact once the calls
+            // that proved them have returned)
+            fb += sl->ws1.tree_fallbacks + sl->ws2.tree_fallbacks + sl->ws1.tree_over() + sl->ws2.tree_over();
+            for (const uint32_t v : {sl->ws1.tree_sub, sl->ws2.tree_sub, sl->ws1.tree_sub_used, sl->ws2.tree_sub_used})
+                if (v) sub = std::min<int>(sub, (int)std::min<uint32_t>(v, 256u));
         }
     };
     if (ctx->children.empty())
@@ -829,6 +929,47 @@ int masp_hip_ctx_set_quotient_form(masp_hip_ctx* ctx, int32_t form) {
 int masp_hip_ctx_get_quotient_form(const masp_hip_ctx* ctx, int32_t* out) {
     if (!ctx || !out) return MASP_HIP_E_INVALID_ARG;
     *out = (ctx->children.empty() ? ctx : ctx->children[0])->quotient_form;
+    return MASP_HIP_OK;
+}
+
+int masp_hip_ctx_set_tree_entry_share(masp_hip_ctx* ctx, int32_t percent) {
+    if (!ctx || percent < 0 || percent > 100) return MASP_HIP_E_INVALID_ARG;
+    const int resolved = percent == 0 ? (int)(MASP_TREE_ENTRY_SHARE) : percent;
+    auto set = [&](masp_hip_ctx* c) {
+        std::unique_lock<std::shared_mutex> lock(c->mu);
+        c->tree_entry_share = resolved;
+    };
+    set(ctx);
+    for (masp_hip_ctx* c : ctx->children) set(c);
+    return MASP_HIP_OK;
+}
+int masp_hip_ctx_get_tree_entry_share(const masp_hip_ctx* ctx, int32_t* out) {
+    if (!ctx || !out) return MASP_HIP_E_INVALID_ARG;
+    *out = (ctx->children.empty() ? ctx : ctx->children[0])->tree_entry_share;
+    return MASP_HIP_OK;
+}
+int masp_hip_r1cs_boolean_variables(const masp_hip_r1cs* cs, uint8_t* out) {
+    if (!cs || !out || cs->n_inputs == 0) return MASP_HIP_E_INVALID_ARG;
+    r1cs_boolean_variables(cs, out);
+    return MASP_HIP_OK;
+}
+uint64_t masp_hip_tree_entry_bound(uint32_t n, int32_t window_bits, uint32_t n_witness, uint32_t n_boolean, int32_t share_percent) {
+    if (window_bits < 2 || window_bits > 16 || share_percent < 0 || share_percent > 100) return 0;
+    return tree_entry_bound(n, window_bits, n_witness, n_boolean, share_percent == 0 ? (int)(MASP_TREE_ENTRY_SHARE) : share_percent);
+}
+int masp_hip_circuit_tree_entry_bounds(const masp_hip_ctx* ctx, uint32_t slot, uint64_t bounds[4], int32_t window_bits[4]) {
+    if (!ctx || !bounds) return MASP_HIP_E_INVALID_ARG;
+    if (!ctx->children.empty()) return masp_hip_circuit_tree_entry_bounds(ctx->children[0], slot, bounds, window_bits);
+    std::shared_lock<std::shared_mutex> lock(const_cast<masp_hip_ctx*>(ctx)->mu);
+    if (slot >= MASP_HIP_MAX_CIRCUITS || !ctx->circ[slot]) return MASP_HIP_E_NOT_LOADED;
+    const Circuit& C = *ctx->circ[slot];
+    const BasesG1& HL = C.hl_eval.n ? C.hl_eval : C.hl;
+    const uint64_t b[4] = {HL.ent_bound, C.a.ent_bound, C.b1.ent_bound, C.b2.ent_bound};
+    const int c[4] = {HL.g.c, C.a.g.c, C.b1.g.c, C.b2.g.c};
+    for (int i = 0; i < 4; ++i) {
+        bounds[i] = b[i];
+        if (window_bits) window_bits[i] = c[i];
+    }
     return MASP_HIP_OK;
 }
 
@@ -1119,6 +1260,28 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
                 C->n_eval_in = 0;
             }
         }
+    }
+    {
+        // What a witness can put into a digit list (MsmBases::ent_bound): the scratch of the bucket tree is cut for it, not for n x W
+        // entries.  Quotient values, coset evaluations and inputs count as full width; of the witness values, those the R1CS proves
+        // boolean cost one entry, and of the others tree_entry_share in a hundred are taken to be full width.
+        std::vector<uint8_t> is_bool(nv);
+        r1cs_boolean_variables(cs, is_bool.data());
+        const int share = ctx->tree_entry_share;
+        auto count = [&](const uint32_t* vars, size_t k) {
+            uint32_t nbool = 0;
+            for (size_t i = 0; i < k; ++i) nbool += is_bool[vars ? vars[i] : cs->n_inputs + i];
+            return nbool;
+        };
+        const uint32_t aux_bool = count(nullptr, cs->n_aux);
+        auto bound = [&](auto& B, uint32_t n_wit, uint32_t n_bool) {
+            if (B.n) B.ent_bound = tree_entry_bound(B.n, B.g.c, n_wit, n_bool, share);
+        };
+        bound(C->hl, cs->n_aux, aux_bool);
+        bound(C->hl_eval, cs->n_aux, aux_bool);
+        bound(C->a, (uint32_t)a_var.size(), count(a_var.data(), a_var.size()));
+        bound(C->b1, (uint32_t)b_var.size(), count(b_var.data(), b_var.size()));
+        bound(C->b2, (uint32_t)b_var.size(), count(b_var.data(), b_var.size()));
     }
     ctx->circ[slot] = std::move(C);
     return MASP_HIP_OK;
@@ -1536,7 +1699,7 @@ static int msm_multi(masp_hip_ctx* ctx, const uint8_t* bases, size_t n, const ui
         MsmWorkspace<O>& w;
         ~Report() {
             c->block_tree_fallbacks += w.tree_fallbacks;
-            c->block_tree_sub = std::min<uint32_t>(c->block_tree_sub, w.tree_sub);
+            c->block_tree_sub = std::min<uint32_t>(c->block_tree_sub, std::min(w.tree_sub ? w.tree_sub : 256u, w.tree_sub_used));
         }
     } report{ctx, ws};
     DevBuf<Xyzz<O>> res;

@@ -128,6 +128,13 @@ def load_library():
         L.masp_hip_ctx_get_quotient_form.argtypes = [vp, C.POINTER(C.c_int32)]
         L.masp_hip_circuit_quotient_form.argtypes = [vp, u32, C.POINTER(C.c_int32)]
         L.masp_hip_circuit_eval_bases.argtypes = [vp, u32, vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz)]
+    if hasattr(L, "masp_hip_ctx_set_tree_entry_share"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
+        L.masp_hip_ctx_set_tree_entry_share.argtypes = [vp, C.c_int32]
+        L.masp_hip_ctx_get_tree_entry_share.argtypes = [vp, C.POINTER(C.c_int32)]
+        L.masp_hip_r1cs_boolean_variables.argtypes = [vp, vp]
+        L.masp_hip_tree_entry_bound.argtypes = [u32, C.c_int32, u32, u32, C.c_int32]
+        L.masp_hip_tree_entry_bound.restype = C.c_uint64
+        L.masp_hip_circuit_tree_entry_bounds.argtypes = [vp, u32, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
     L.masp_hip_quotient_h.argtypes = [vp, vp, vp, vp, sz, u32, vp]
     L.masp_hip_ntt.argtypes = [vp, vp, u32, C.c_int]
     L.masp_hip_vk_prepare.argtypes = [vp, vp, sz, C.POINTER(vp)]
@@ -641,6 +648,23 @@ class Context:
             self._check(self._L.masp_hip_circuit_eval_bases(self._h, int(slot), _p(pts), n.value, C.byref(n), _p(cols), cols.size, C.byref(k)))
         return pts, [int(c) for c in cols[:k.value]]
 
+    def set_tree_entry_share(self, percent):
+        """Of the witness scalars that the R1CS does not prove boolean, the share (1..100, 0 = the default) that the scratch of the bucket
+        tree takes to be full width, for circuits loaded FROM NOW ON; a proof with more entries goes through the XYZZ accumulation."""
+        self._check(self._L.masp_hip_ctx_set_tree_entry_share(self._h, int(percent)))
+
+    @property
+    def tree_entry_share(self):
+        v = C.c_int32(0)
+        self._check(self._L.masp_hip_ctx_get_tree_entry_share(self._h, C.byref(v)))
+        return int(v.value)
+
+    def circuit_tree_entry_bounds(self, slot):
+        """-> {"hl" | "a" | "b_g1" | "b_g2": (entry bound of the batch MSM, its window width)} of the circuit in `slot`"""
+        b, c = (C.c_uint64 * 4)(), (C.c_int32 * 4)()
+        self._check(self._L.masp_hip_circuit_tree_entry_bounds(self._h, int(slot), b, c))
+        return {k: (int(b[i]), int(c[i])) for i, k in enumerate(("hl", "a", "b_g1", "b_g2"))}
+
     def current_options(self):
         """masp_hip_ctx_get_options now: the options with what lack of tree scratch has changed since creation — the
         `bucket_tree_sub_batch` in use and `bucket_tree_fallback_proofs` (proofs that went through the XYZZ accumulation)."""
@@ -838,3 +862,17 @@ class GpuVerifyingKey:
             self.close()
         except Exception:
             pass
+
+
+def r1cs_boolean_variables(cs):
+    """masp_hip_r1cs_boolean_variables -> u8[n_inputs + n_aux]: 1 where the R1CS proves the variable boolean (host only: no device)."""
+    out = np.zeros(cs.n_inputs + cs.n_aux, dtype=np.uint8)
+    rc = load_library().masp_hip_r1cs_boolean_variables(cs.ref, _p(out))
+    if rc:
+        raise MaspHipError(rc)
+    return out
+
+
+def tree_entry_bound(n, window_bits, n_witness, n_boolean, share_percent=0):
+    """masp_hip_tree_entry_bound: the entries a witness can put into the digit list of an n-point MSM (host only: no device)."""
+    return int(load_library().masp_hip_tree_entry_bound(int(n), int(window_bits), int(n_witness), int(n_boolean), int(share_percent)))
