@@ -101,7 +101,9 @@ typedef struct {
                                         for Spend batches; profiles/r06_slots_3_4_5_at_16_hardware_queues.txt) */
     int32_t batch_cap;               /* proofs per launch sequence: 1..256 (default 256 = BASELINE.json configs[3]) */
     int32_t ntt_sub_batch;           /* proofs per sub-batch of the quotient's transforms (default 8: 160 MiB of work buffers
-                                        stay in the Infinity Cache); -1 = the whole batch at once */
+                                        stay in the Infinity Cache); -1 = the whole batch at once.  A batch in evaluation form on the
+                                        three-kernel schedule (masp_hip_ctx_set_quotient_schedule) works in one buffer where the
+                                        separate passes need two, and takes TWICE this many proofs per sub-batch: the same bytes */
     int32_t window_bits_h;           /* window width of the h query (default: 16 from 49 152 points, 15 from 16 384) */
     int32_t window_bits_la;          /* ... of the l and a queries (default: from the expected non-trivial scalars) */
     int32_t window_bits_b;           /* ... of b_g1 / b_g2 */
@@ -196,6 +198,16 @@ int masp_hip_ctx_get_boolean_block_bits(const masp_hip_ctx* ctx, int32_t* out);
 #define MASP_HIP_QUOTIENT_COEFFICIENT 1
 int masp_hip_ctx_set_quotient_form(masp_hip_ctx* ctx, int32_t form);
 int masp_hip_ctx_get_quotient_form(const masp_hip_ctx* ctx, int32_t* out);
+/* How a batch in evaluation form schedules its four transforms per proof.  MASP_HIP_QUOTIENT_FUSED (0, the default): for domains of 2^11 to
+ * 2^20 points, three launches per sub-batch and no permutation pass — the inverse transforms as decimation in frequency, both transforms'
+ * low stages in one kernel with the coset scale between them, the forward transforms' top stages fused with the product.
+ * MASP_HIP_QUOTIENT_SEPARATE (1): seven launches — every transform behind a bit-reversal pass — which is also what other domain sizes run.
+ * Same scalars, same proof bytes.  Read when a batch is enqueued: one context can be tested and profiled both ways.  (A call and not a
+ * field of masp_hip_options, as masp_hip_ctx_set_boolean_block_bits.) */
+#define MASP_HIP_QUOTIENT_FUSED 0
+#define MASP_HIP_QUOTIENT_SEPARATE 1
+int masp_hip_ctx_set_quotient_schedule(masp_hip_ctx* ctx, int32_t schedule);
+int masp_hip_ctx_get_quotient_schedule(const masp_hip_ctx* ctx, int32_t* out);
 /* The scratch of the bucket tree (masp_hip_options::bucket_tree_levels) is cut for the entries a witness can put into an MSM's digit list, not
  * for every scalar at full width: one window digit per window for a quotient value, a coset evaluation, an input and a witness value that
  * can be anything; one entry for a witness value that the R1CS proves boolean (masp_hip_r1cs_boolean_variables).  percent: of the witness

@@ -87,6 +87,7 @@ struct NttDomain {
     uint32_t logm = 0;
     size_t m = 0;
     DevBuf<Fr> tw_fwd, tw_inv, coset_scale, h_scale;
+    DevBuf<Fr> coset_scale_rev;  // coset_scale in bit-reversed order: g^rev(i) / m (k_ntt_mid); only where ntt_fused_ok(logm)
     Fr c_scale;  // 1 / (m (g^m - 1)), plain form
     Fr e_scale;  // 1 / (g^m - 1), plain form (the evaluation form's only factor: k_ntt_ab_eval)
     int init(uint32_t logm_, hipStream_t s) {
@@ -110,6 +111,10 @@ struct NttDomain {
         launch_fr_powers(s, tw_inv.p, (uint32_t)half, omega_inv, one, 0);
         launch_fr_powers(s, coset_scale.p, (uint32_t)m, g, minv, 0);
         launch_fr_powers(s, h_scale.p, (uint32_t)m, ginv, mzinv, 1);  // g^-k / (m (g^m - 1)), plain form
+        if (ntt_fused_ok(logm)) {
+            if ((rc = coset_scale_rev.reserve(m))) return rc;
+            launch_fr_powers_bitrev(s, coset_scale_rev.p, logm, g, minv);
+        }
         HIP_TRY(hipStreamSynchronize(s));
         return MASP_HIP_OK;
     }
@@ -197,6 +202,7 @@ struct Slot {
         if (id == N_LONE_MARKS - 1) lone_marked = true;
     }
     uint32_t ntt_sub = 8;        // masp_hip_options::ntt_sub_batch of the owning context (0 = whole batch)
+    const std::atomic<int>* quotient_schedule = nullptr;  // the owning context's (masp_hip_ctx_set_quotient_schedule)
     uint8_t* h_stage = nullptr;  // pinned staging for the assignment
     size_t h_stage_cap = 0;
     uint8_t* h_proof = nullptr;  // pinned, batch_cap x 192
@@ -348,6 +354,9 @@ struct masp_hip_ctx {
     int boolean_block_bits = MASP_SUBSET_BITS;
     // the quotient's form for circuits loaded from now on: 0 = evaluation form, 1 = coefficient form (masp_hip_ctx_set_quotient_form)
     int quotient_form = 0;
+    // how a batch in evaluation form runs its transforms: 0 = the three fused kernels, 1 = the separate passes (masp_hip_ctx_set_quotient_schedule);
+    // read when a batch is enqueued
+    std::atomic<int> quotient_schedule{0};
     // of a query's witness scalars that the R1CS does not prove boolean, the percentage that the bucket tree's scratch takes to be full
     // width, for circuits loaded from now on (masp_hip_ctx_set_tree_entry_share; the default: MASP_TREE_ENTRY_SHARE)
     int tree_entry_share = MASP_TREE_ENTRY_SHARE;

@@ -10,6 +10,18 @@ namespace masp {
 void launch_fr_powers(hipStream_t s, Fr* table, uint32_t n, const Fr& base, const Fr& scale, int plain) {
     MASP_LAUNCH(k_fr_powers, dim3((n + 255) / 256), dim3(256), 0, s, table, n, base, scale, plain);
 }
+void launch_fr_powers_bitrev(hipStream_t s, Fr* table, uint32_t logn, const Fr& base, const Fr& scale) {
+    MASP_LAUNCH(k_fr_powers_bitrev, dim3(((1u << logn) + 255) / 256), dim3(256), 0, s, table, logn, base, scale);
+}
+void launch_ntt_dif_top(hipStream_t s, const Fr* a, const Fr* b, size_t in_stride, uint32_t nrows, Fr* y, const Fr* tw, uint32_t logm, uint32_t q) {
+    MASP_LAUNCH(k_ntt_dif_top, dim3(1u << (logm - NTT_LT), 2 * q), dim3(256), 0, s, a, b, in_stride, nrows, q, y, tw, logm);
+}
+void launch_ntt_mid(hipStream_t s, Fr* data, const Fr* tw_inv, const Fr* scale_rev, const Fr* tw_fwd, uint32_t logm, uint32_t np) {
+    MASP_LAUNCH(k_ntt_mid, dim3(1u << (logm - NTT_LT), np), dim3(256), 0, s, data, tw_inv, scale_rev, tw_fwd, logm);
+}
+void launch_ntt_dit_top_ab(hipStream_t s, const Fr* x, size_t b_off, const Fr* tw, const Fr& scale, Fr* y, size_t y_stride, uint32_t logm, uint32_t q) {
+    MASP_LAUNCH(k_ntt_dit_top_ab, dim3(1u << (logm - NTT_LT), q), dim3(512), 0, s, x, b_off, tw, scale, y, y_stride, logm);
+}
 void launch_ntt_pass(hipStream_t s, Fr* data, const Fr* tw, uint32_t logm, uint32_t s0, uint32_t nst, uint32_t np) {
     const uint32_t lt = (uint32_t)NTT_LT < logm ? (uint32_t)NTT_LT : logm;
     MASP_LAUNCH(k_ntt_pass, dim3(1u << (logm - lt), np), dim3(256), 0, s, data, tw, logm, s0, nst);

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device/curve.hpp"
+#include "device/ntt_geom.h"
 
 namespace masp {
 
@@ -18,6 +19,18 @@ void launch_ntt_scale_bitrev(hipStream_t s, const Fr* x, const Fr* scale, Fr* y,
 void launch_ntt_ab_bitrev(hipStream_t s, const Fr* a, const Fr* b, Fr* y, uint32_t logm, uint32_t np);
 // y_p[k] = a_p[k] * b_p[k] * scale for k < n (a, b: np vectors of n back to back; plain-form scale: canonical results), y_p = y + p * y_stride
 void launch_ntt_ab_eval(hipStream_t s, const Fr* a, const Fr* b, const Fr& scale, Fr* y, uint32_t n, uint32_t np, size_t y_stride);
+// The evaluation-form quotient without permutation passes, for NTT_LT < logm <= 2 * NTT_LT (ntt_fused_ok; device/ntt.hpp):
+// table[i] = scale * base^rev(i), rev over logn bits
+void launch_fr_powers_bitrev(hipStream_t s, Fr* table, uint32_t logn, const Fr& base, const Fr& scale);
+static inline bool ntt_fused_ok(uint32_t logm) { return logm > (uint32_t)NTT_LT && logm <= 2u * NTT_LT; }
+// the inverse transform's stages logm - 1 ... NTT_LT of q vectors of a and q of b (Montgomery, natural order, in_stride apart, zero from
+// nrows on) -> y: [a | b], 2 q transforms of 2^logm
+void launch_ntt_dif_top(hipStream_t s, const Fr* a, const Fr* b, size_t in_stride, uint32_t nrows, Fr* y, const Fr* tw, uint32_t logm, uint32_t q);
+// in place on np transforms: the inverse's stages NTT_LT - 1 ... 0, times scale_rev[i], the forward's stages 0 ... NTT_LT - 1
+void launch_ntt_mid(hipStream_t s, Fr* data, const Fr* tw_inv, const Fr* scale_rev, const Fr* tw_fwd, uint32_t logm, uint32_t np);
+// the forward's stages NTT_LT ... logm - 1 of a_p = x + p * 2^logm and b_p = a_p + b_off, then y_p[k] = a_p[k] * b_p[k] * scale (plain-form
+// scale: canonical results), y_p = y + p * y_stride, p < q
+void launch_ntt_dit_top_ab(hipStream_t s, const Fr* x, size_t b_off, const Fr* tw, const Fr& scale, Fr* y, size_t y_stride, uint32_t logm, uint32_t q);
 void launch_fr_scale_sub(hipStream_t s, const Fr* x, const Fr* scale, const Fr* c, const Fr& cscale, Fr* y, uint32_t n, uint32_t np, size_t y_stride = 0);
 // y_p = y + p * y_stride (0: n)
 void launch_fr_scale(hipStream_t s, const Fr* x, const Fr* scale, Fr* y, uint32_t n, uint32_t np, size_t y_stride = 0);

@@ -181,6 +181,7 @@ static int add_slot(masp_hip_ctx* ctx, char busy) {
     int rc = s->init(ctx->streams.slot[ctx->slots.size()]);
     if (rc) return rc;
     s->profiling = ctx->profiling;
+    s->quotient_schedule = &ctx->quotient_schedule;
     s->configure(ctx->opt);
     ctx->slots.push_back(std::move(s));
     ctx->slot_busy.push_back(busy);
@@ -282,19 +283,32 @@ static int enqueue_quotient(Slot& sl, const NttDomain& D, const Fr* const in[3],
 
 // The quotient of a batch in EVALUATION form (Circuit::hl_eval): a and b only — to coefficients, onto the coset g H — and then their
 // pointwise product E = a b / (g^m - 1), canonical, straight into the merged scalar buffer (e_out + p * e_stride); four transforms per
-// proof, no permutation behind the last.  in[0], in[1] + p * in_stride: Montgomery evaluation vectors of `nrows` entries.
+// proof.  in[0], in[1] + p * in_stride: Montgomery evaluation vectors of `nrows` entries.
+// Where the domain allows it (ntt_fused_ok) a sub-batch is three launches over one work buffer: the inverse transforms as decimation in
+// frequency straight from `in`, both transforms' low stages with the coset scale between them, the forward transforms' top stages with the
+// product (device/ntt.hpp).  Otherwise, or with masp_hip_ctx_set_quotient_schedule(1): seven launches — two copies into bit-reversed order,
+// the inverse passes, the scale with another permutation into a second buffer, the forward passes, the product.
 static int enqueue_quotient_eval(Slot& sl, const NttDomain& D, const Fr* const in[2], size_t in_stride, uint32_t nrows, uint32_t np, Fr* e_out,
                                  size_t e_stride) {
     hipStream_t s = sl.stream;
     const uint32_t m = (uint32_t)D.m, logm = D.logm;
-    const uint32_t sub_max = sl.ntt_sub;  // as in enqueue_quotient: the work buffers (here sub x 4 x 32 m bytes) stay in the Infinity Cache
+    const bool fused = ntt_fused_ok(logm) && D.coset_scale_rev.p && !(sl.quotient_schedule && sl.quotient_schedule->load(std::memory_order_relaxed));
+    // as in enqueue_quotient: the work buffers stay in the Infinity Cache — sub x 4 x 32 m bytes for the separate passes; the three kernels
+    // work in ONE buffer of [a | b] and take twice the proofs in the same bytes (16 Spend proofs: 128 MiB; measured against 8 in MEASUREMENTS.md)
+    const uint32_t sub_max = fused ? 2 * sl.ntt_sub : sl.ntt_sub;
     const uint32_t sub = sub_max ? std::min(sub_max, np) : np;
     int rc;
-    if ((rc = sl.x0.reserve((size_t)2 * m * sub)) || (rc = sl.x1.reserve((size_t)2 * m * sub))) return rc;
+    if ((rc = sl.x0.reserve((size_t)2 * m * sub)) || (!fused && (rc = sl.x1.reserve((size_t)2 * m * sub)))) return rc;
     Fr *x0 = sl.x0.p, *x1 = sl.x1.p;
     for (uint32_t p0 = 0; p0 < np; p0 += sub) {
         const uint32_t q = std::min(sub, np - p0);
         const size_t part = (size_t)q * m;  // one of a / b for the whole sub-batch
+        if (fused) {
+            launch_ntt_dif_top(s, in[0] + (size_t)p0 * in_stride, in[1] + (size_t)p0 * in_stride, in_stride, nrows, x0, D.tw_inv.p, logm, q);
+            launch_ntt_mid(s, x0, D.tw_inv.p, D.coset_scale_rev.p, D.tw_fwd.p, logm, 2 * q);   // A, B on the coset g H but for the top stages
+            launch_ntt_dit_top_ab(s, x0, part, D.tw_fwd.p, D.e_scale, e_out + (size_t)p0 * e_stride, e_stride, logm, q);
+            continue;
+        }
         for (int i = 0; i < 2; ++i) launch_ntt_copy_bitrev(s, in[i] + (size_t)p0 * in_stride, in_stride, nrows, x0 + i * part, logm, q);
         D.passes(s, x0, D.tw_inv.p, 2 * q);                                     // m A, m B (coefficients)
         launch_ntt_scale_bitrev(s, x0, D.coset_scale.p, x1, logm, 2 * q);       // * g^k / m
@@ -929,6 +943,18 @@ int masp_hip_ctx_set_quotient_form(masp_hip_ctx* ctx, int32_t form) {
 int masp_hip_ctx_get_quotient_form(const masp_hip_ctx* ctx, int32_t* out) {
     if (!ctx || !out) return MASP_HIP_E_INVALID_ARG;
     *out = (ctx->children.empty() ? ctx : ctx->children[0])->quotient_form;
+    return MASP_HIP_OK;
+}
+
+int masp_hip_ctx_set_quotient_schedule(masp_hip_ctx* ctx, int32_t schedule) {
+    if (!ctx || (schedule != MASP_HIP_QUOTIENT_FUSED && schedule != MASP_HIP_QUOTIENT_SEPARATE)) return MASP_HIP_E_INVALID_ARG;
+    ctx->quotient_schedule.store(schedule, std::memory_order_relaxed);
+    for (masp_hip_ctx* c : ctx->children) c->quotient_schedule.store(schedule, std::memory_order_relaxed);
+    return MASP_HIP_OK;
+}
+int masp_hip_ctx_get_quotient_schedule(const masp_hip_ctx* ctx, int32_t* out) {
+    if (!ctx || !out) return MASP_HIP_E_INVALID_ARG;
+    *out = (ctx->children.empty() ? ctx : ctx->children[0])->quotient_schedule.load(std::memory_order_relaxed);
     return MASP_HIP_OK;
 }
 

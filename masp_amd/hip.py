@@ -49,6 +49,7 @@ class JobStruct(C.Structure):
 assert C.sizeof(JobStruct) == 120 and JobStruct.r.offset == 48 and JobStruct.aux_form.offset == 112   # include/masp_hip.h asserts the same
 AUX_CANONICAL, AUX_MONTGOMERY = 0, 1     # masp_hip_job::aux_form
 QUOTIENT_EVALUATION, QUOTIENT_COEFFICIENT = 0, 1     # masp_hip_ctx_set_quotient_form
+QUOTIENT_FUSED, QUOTIENT_SEPARATE = 0, 1             # masp_hip_ctx_set_quotient_schedule
 
 
 def library_path():
@@ -128,6 +129,9 @@ def load_library():
         L.masp_hip_ctx_get_quotient_form.argtypes = [vp, C.POINTER(C.c_int32)]
         L.masp_hip_circuit_quotient_form.argtypes = [vp, u32, C.POINTER(C.c_int32)]
         L.masp_hip_circuit_eval_bases.argtypes = [vp, u32, vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz)]
+    if hasattr(L, "masp_hip_ctx_set_quotient_schedule"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
+        L.masp_hip_ctx_set_quotient_schedule.argtypes = [vp, C.c_int32]
+        L.masp_hip_ctx_get_quotient_schedule.argtypes = [vp, C.POINTER(C.c_int32)]
     if hasattr(L, "masp_hip_ctx_set_tree_entry_share"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
         L.masp_hip_ctx_set_tree_entry_share.argtypes = [vp, C.c_int32]
         L.masp_hip_ctx_get_tree_entry_share.argtypes = [vp, C.POINTER(C.c_int32)]
@@ -630,6 +634,17 @@ class Context:
     def quotient_form(self):
         v = C.c_int32(0)
         self._check(self._L.masp_hip_ctx_get_quotient_form(self._h, C.byref(v)))
+        return int(v.value)
+
+    def set_quotient_schedule(self, schedule):
+        """How a batch in evaluation form runs its transforms FROM THE NEXT BATCH ON: QUOTIENT_FUSED (0, the default: three kernels per
+        sub-batch, no permutation pass) or QUOTIENT_SEPARATE (1: seven launches, a bit-reversal pass in front of every transform)."""
+        self._check(self._L.masp_hip_ctx_set_quotient_schedule(self._h, int(schedule)))
+
+    @property
+    def quotient_schedule(self):
+        v = C.c_int32(0)
+        self._check(self._L.masp_hip_ctx_get_quotient_schedule(self._h, C.byref(v)))
         return int(v.value)
 
     def circuit_quotient_form(self, slot):
