@@ -185,6 +185,18 @@ int masp_hip_ctx_create_multi(const int* devices, int n_devices, masp_hip_ctx** 
 int masp_hip_ctx_set_boolean_block_bits(masp_hip_ctx* ctx, int32_t bits);
 /* the resolved setting: 0 = no subset rows, 2 or 3 */
 int masp_hip_ctx_get_boolean_block_bits(const masp_hip_ctx* ctx, int32_t* out);
+/* Doubled window rows.  Next to every window row 2^(c j) P the loader also stores 2 * 2^(c j) P; a window digit of odd 2-adic valuation is
+ * then an entry of the doubled row in the bucket of half its magnitude, and an MSM needs a bucket only for the magnitudes of even
+ * valuation: two thirds as many buckets (21 845 instead of 32 768 on 16-bit windows), so two thirds of the per-bucket work — the bucket
+ * tails, the sort's padding of every bucket's run —, for the same additions per scalar.  Same proof bytes.  The rows of a table that opts in
+ * double (Spend: the merged h + l table 0.47 -> 0.94 GB).  v: 0 = the build's default, -1 = off, 1 = every table that batches use (the
+ * merged h + l tables, a, b_g1, b_g2), 2 = the merged h + l tables only.  The tables only lone proofs use are never doubled; a table with
+ * a point at infinity stays as it is.  Applies to circuits loaded AFTER the call; the building-block MSMs (masp_hip_msm_g1_multi and
+ * its kin) build their table per call and double its rows only after an explicit v = 1.  (A call and not a field of masp_hip_options, as
+ * masp_hip_ctx_set_boolean_block_bits.) */
+int masp_hip_ctx_set_window_row_multiples(masp_hip_ctx* ctx, int32_t v);
+/* the resolved setting as a mask: bit 0 = the merged h + l tables, bit 1 = a, b_g1, b_g2 */
+int masp_hip_ctx_get_window_row_multiples(const masp_hip_ctx* ctx, int32_t* out);
 /* The form in which a BATCH (eight proofs or more of a circuit's own a, b, c) computes its quotient.  Only the group element
  * sum_k h_k H_k enters a proof, and it is linear in h: in EVALUATION form the loader derives, once per circuit, a second merged base set —
  * the h query carried through a group-valued inverse DFT, and C's share of the quotient folded into the l query — and a proof then needs
@@ -276,6 +288,10 @@ int masp_hip_circuit_flags(const masp_hip_ctx* ctx, uint32_t slot, uint32_t* fla
  * for and a derived base came out as the point at infinity (negligible for a real CRS, possible for a toy one): such a circuit loads
  * without error and keeps the coefficient form. */
 int masp_hip_circuit_quotient_form(const masp_hip_ctx* ctx, uint32_t slot, int32_t* form);
+/* *sets = the tables of the circuit in `slot` that really have doubled window rows (masp_hip_ctx_set_window_row_multiples): bit 0 the merged
+ * h + l table, bit 1 the merged table of the evaluation form, bit 2 a, bit 3 b_g1, bit 4 b_g2.  A table with a point at infinity stays
+ * plain whatever was asked for. */
+int masp_hip_circuit_window_row_multiples(const masp_hip_ctx* ctx, uint32_t slot, int32_t* sets);
 /* The derived bases of the circuit in `slot`, uncompressed (96 bytes each), in table order: m = 2^logm points T'_i, then n_aux points L'_j,
  * then one point per input column that C uses — input_cols lists those columns, ascending.  *n_points / *n_input_cols always receive the
  * counts (both 0 for a circuit in coefficient form); bases == NULL and input_cols == NULL asks for the counts only; a capacity that is

@@ -60,18 +60,21 @@ __global__ void k_msm_import(const uint8_t* __restrict__ raw, TabRow<O>* __restr
     }
     tab[i].p = p;
 }
-// T[j][i] = 2^c * T[j-1][i]
+// T[j][i] = 2^c * T[j-1][i]; twin: also the doubled rows T[W + j][i] = 2 * T[j][i] (msm_geom_twin, msm_geom.h), each one complete
+// doubling of the window's row brought to affine form — the same doubling the next window's row starts from
 template <class O>
-__global__ void __launch_bounds__(64) k_msm_precompute(TabRow<O>* __restrict__ tab, uint32_t n, int c, int W) {
+__global__ void __launch_bounds__(64) k_msm_precompute(TabRow<O>* __restrict__ tab, uint32_t n, int c, int W, int twin = 0) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Affine<O> p = tab[i].p;
     for (int j = 1; j < W; ++j) {
         Xyzz<O> q = xyzz_dbl_affine(p);
+        if (twin) tab[(size_t)(W + j - 1) * n + i].p = xyzz_to_affine(q);
         for (int k = 1; k < c; ++k) q = xyzz_dbl(q);
         p = xyzz_to_affine(q);
         tab[(size_t)j * n + i].p = p;
     }
+    if (twin) tab[(size_t)(2 * W - 1) * n + i].p = xyzz_to_affine(xyzz_dbl_affine(p));
 }
 // The subset rows behind the window tables (MsmSubset, msm_geom.h): one lane per row sums the bases of its bit pattern with the complete
 // mixed addition (two equal bases in a block are a doubling) and stores the sum in affine form.  A sum at infinity marks its block in `bad`:
@@ -317,7 +320,13 @@ template <class O>
 constexpr uint32_t wsum_points_log() {
     return O::LANES > 4 ? WSUM_L_LOG - 1 : WSUM_L_LOG;
 }
-template <class O, uint32_t G_LOG>
+// TWIN (a base set with doubled window rows: msm_geom_twin, msm_geom.h): ONE launch over the whole bucket array, level 0 of every class.
+// Workgroups [0, gridDim.x - 1) each own a chunk of a class with at least CS buckets — such a class is whole chunks — with off = 0:
+// S[ch] = sum B, T[ch] = sum l B over the chunk (k_msm_twin_combine turns them into the class's 2 V + S).  The last workgroup owns the
+// classes s >= s0 behind them, fewer than CS buckets together, as the DENSE array of their values divided by 4^s0: element d holds the
+// bucket of value 4^s0 (d + 1) if d + 1 has an even valuation and nothing otherwise, d < m (m = 2^(c-1) / 4^s0 <= CS), off = 1 —
+// T[last] = the weighted sum of those classes / 4^s0.  `off` is not used.
+template <class O, uint32_t G_LOG, bool TWIN = false>
 __global__ void __launch_bounds__((1u << wsum_points_log<O>()) * O::LANES, (O::LANES > 1 ? MASP_WSUM_PAIR_WAVES : sizeof(Xyzz<O>) > 200 || G_LOG < 3 ? MASP_TAIL_MIN_WAVES : 2))
 k_msm_wsum_level(const Xyzz<typename O::Base>* __restrict__ B, size_t b_stride, uint32_t m, uint32_t off, Xyzz<typename O::Base>* __restrict__ S,
                  Xyzz<typename O::Base>* __restrict__ T, size_t st_stride) {
@@ -331,9 +340,22 @@ k_msm_wsum_level(const Xyzz<typename O::Base>* __restrict__ B, size_t b_stride, 
     // phase 1: lane-local running sum, top element first:  run = sum B_l,  acc = sum (l + off) B_l  (l local)
     const uint32_t base = blockIdx.x * CS + e * G;
     Xyzz<O> run = xyzz_inf<O>(), acc = xyzz_inf<O>();
-    for (uint32_t l = G; l-- > 0;) {
-        if (base + l < m) xyzz_add_nc(run, xyzz_load<O>(B + base + l, h));
-        if (l > 0 || off) xyzz_add_nc(acc, run);
+    if constexpr (TWIN) {
+        const bool tail = blockIdx.x == gridDim.x - 1;
+        for (uint32_t l = G; l-- > 0;) {
+            if (!tail) {
+                xyzz_add_nc(run, xyzz_load<O>(B + base + l, h));
+            } else {
+                const uint32_t v = e * G + l + 1u, t = (uint32_t)__builtin_ctz(v);  // the value / 4^s0: class s0 + t / 2 if t is even
+                if (v <= m && !(t & 1u)) xyzz_add_nc(run, xyzz_load<O>(B + blockIdx.x * CS + 2u * (m - (m >> t)) / 3u + ((v >> t) >> 1), h));
+            }
+            if (l > 0 || tail) xyzz_add_nc(acc, run);
+        }
+    } else {
+        for (uint32_t l = G; l-- > 0;) {
+            if (base + l < m) xyzz_add_nc(run, xyzz_load<O>(B + base + l, h));
+            if (l > 0 || off) xyzz_add_nc(acc, run);
+        }
     }
     // phase 2: lanes.  sum_e (e * G) * run_e = G * sum_{i >= 1} x_i  with x = inclusive suffix scan of run over the WSUM_L
     // points: a shuffle scan inside each wave, then every wave adds the totals of the waves behind it
@@ -413,6 +435,38 @@ __global__ void __launch_bounds__(64) k_msm_combine(const Xyzz<O>* __restrict__ 
     for (int l = levels - 1; l >= 0; --l) {
         for (int k = 0; k < cs_log; ++k) acc = xyzz_dbl(acc);
         xyzz_add_nc(acc, tsum[l]);
+    }
+    *out = acc;
+}
+
+// Doubled window rows (msm_geom_twin, msm_geom.h): the weighted sum over the classes from what ONE launch of k_msm_wsum_level<.., TWIN> left
+// in S[ch], T[ch] (chunks of 2^cs_log buckets).  Class s < s0 is the nch = size / 2^cs_log chunks from off / 2^cs_log on, its buckets the
+// weights 4^s (2 k + 1):  C_s = 2 (sum_ch T[ch] + 2^cs_log sum_j j S[ch0 + j]) + sum_ch S[ch];  the classes s >= s0 are T[last] (already
+// weighted, / 4^s0).  V = sum_s 4^s C_s by Horner from the top.  A handful of chunks per proof (a batch takes chunks of nb / 4 or more
+// buckets): one lane per proof, as k_msm_combine.
+template <class O>
+__global__ void __launch_bounds__(64) k_msm_twin_combine(const Xyzz<O>* __restrict__ S, const Xyzz<O>* __restrict__ T, size_t st_stride, int c, uint32_t s0,
+                                                         int cs_log, Xyzz<O>* __restrict__ out, size_t out_stride) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    S += MSM_P * st_stride;
+    T += MSM_P * st_stride;
+    out += MSM_P * out_stride;
+    Xyzz<O> acc = T[s0 ? msm_twin_class(c, s0).off >> cs_log : 0u];
+    for (uint32_t s = s0; s-- > 0;) {
+        const MsmTwinClass k = msm_twin_class(c, s);
+        const uint32_t ch0 = k.off >> cs_log, nch = k.size >> cs_log;
+        Xyzz<O> run = xyzz_inf<O>(), jsum = xyzz_inf<O>(), tsum = xyzz_inf<O>();
+        for (uint32_t j = nch; j-- > 0;) {
+            xyzz_add_nc(run, S[ch0 + j]);
+            xyzz_add_nc(tsum, T[ch0 + j]);
+            if (j > 0) xyzz_add_nc(jsum, run);
+        }
+        for (int i = 0; i < cs_log; ++i) jsum = xyzz_dbl(jsum);
+        xyzz_add_nc(jsum, tsum);
+        jsum = xyzz_dbl(jsum);
+        xyzz_add_nc(jsum, run);
+        acc = xyzz_dbl(xyzz_dbl(acc));
+        xyzz_add_nc(acc, jsum);
     }
     *out = acc;
 }

@@ -9,13 +9,54 @@ namespace masp {
 struct MsmGeom {
     int c;        // window width in bits (signed digits)
     int W;        // windows of a 256-bit scalar: ceil(256 / c) — also the number of tables of a base set (table j holds 2^(c j) P)
-    int nb;       // buckets = 2^(c-1)  (|digit| in 1..2^(c-1))
+    int nb;       // buckets = 2^(c-1)  (|digit| in 1..2^(c-1)); twin: msm_twin_buckets(c), rounded up to whole sorting bins
+    int twin;     // 1: every window has a second table of doubled rows (table W + j holds 2 * 2^(c j) P) and only the digit magnitudes
+                  // of even 2-adic valuation have a bucket (msm_geom_twin below); 0: none
+    __host__ __device__ int tables() const { return twin ? 2 * W : W; }
 };
 static inline MsmGeom msm_geom(int c) {
     MsmGeom g;
     g.c = c;
     g.W = (256 + c - 1) / c;
     g.nb = 1 << (c - 1);
+    g.twin = 0;
+    return g;
+}
+// Doubled window rows.  A digit magnitude v = 2^t o (o odd, 1 <= v <= H = 2^(c-1)) is the entry (row multiple 2^(t & 1), bucket value
+// v >> (t & 1)): the bucket values are B = { 4^s o <= H }, |B| = (2 H + 1) / 3 rounded down (21 845 of 32 768 at c = 16).  B is laid out by CLASS s = t >> 1: class s holds the values
+// 4^s (2 k + 1), k = 0 .. size - 1, at the bucket ids off + k — dense odd weights, so that the weighted sum of a class is
+// 4^s (2 V(B_s, 0) + sum B_s).  The sizes are H / 2, H / 8, ... (powers of two; the last class is the single value 4^s = H where c - 1 is
+// even), so every class starts at a multiple of four times its size and the value 1 keeps bucket id 0.
+struct MsmTwinClass {
+    uint32_t off, size, weight;  // first bucket id, buckets, 4^s
+};
+__host__ __device__ static inline uint32_t msm_twin_classes(int c) { return (uint32_t)(c - 1) / 2u + 1u; }  // the s with 4^s <= 2^(c-1)
+__host__ __device__ static inline MsmTwinClass msm_twin_class(int c, uint32_t s) {
+    const uint32_t H = 1u << (c - 1), sz = H >> (2u * s + 1u);
+    MsmTwinClass k;
+    k.off = 2u * (H - (H >> (2u * s))) / 3u;  // = H / 2 + H / 8 + ... (s terms)
+    k.size = sz ? sz : 1u;
+    k.weight = 1u << (2u * s);
+    return k;
+}
+__host__ __device__ static inline uint32_t msm_twin_buckets(int c) { return ((2u << (c - 1)) + 1u) / 3u; }  // |B| = 2 H / 3 rounded to the nearest integer
+// digit magnitude v (1 .. 2^(c-1)) -> bucket id; mult: 0 = the window's own row, 1 = its doubled row
+__host__ __device__ static inline uint32_t msm_twin_bucket(int c, uint32_t v, uint32_t& mult) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t t = (uint32_t)__builtin_ctz(v);
+#else
+    uint32_t t = 0;
+    while (!((v >> t) & 1u)) ++t;
+#endif
+    mult = t & 1u;
+    return msm_twin_class(c, t >> 1).off + ((v >> t) >> 1);
+}
+// nb: |B|, in whole bins of 128 buckets where the sort places in two passes (MSM_FINE, device/msm_sort.hpp); the buckets behind |B| stay empty
+static inline MsmGeom msm_geom_twin(int c) {
+    MsmGeom g = msm_geom(c);
+    const uint32_t nbk = msm_twin_buckets(c);
+    g.nb = (int)(nbk < 128u ? nbk : (nbk + 127u) & ~127u);
+    g.twin = 1;
     return g;
 }
 // digits a scalar that is neither 0 nor 1 is expected to have (x 16: fixed point)
@@ -35,7 +76,7 @@ __host__ __device__ static inline uint32_t msm_chunk_len(uint32_t total, uint32_
 struct MsmSubset {
     uint32_t bits = 0;              // log2 of the block width: 0 = none, else 2 or 3 (blocks tile a 64-lane wave)
     uint32_t b_first = 0, b_end = 0;  // covered blocks [b_first, b_end)
-    uint32_t row0 = 0;              // the first subset row = W n
+    uint32_t row0 = 0;              // the first subset row = W n (2 W n behind doubled window rows: MsmGeom::tables)
     uint32_t* bad = nullptr;        // [bad_words()] device words (written at load time only)
     __host__ __device__ uint32_t bad_words() const { return (b_end - b_first + 31) / 32; }
     __host__ __device__ uint32_t patterns() const { return (1u << (1u << bits)) - 1u; }

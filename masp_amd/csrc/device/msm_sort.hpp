@@ -26,10 +26,10 @@ namespace masp {
 // removed in round 6 — the tables it needs are beyond an XCD's TLB reach: EXPERIMENTS.md, profiles/r05_naf_digits_*.txt.)
 struct MsmDigitIter {
     const uint32_t* sw;
-    uint32_t carry, mask, half, pos, j;
+    uint32_t carry, mask, half, pos, j, twin_w;  // twin_w: 0, or W where the base set has doubled window rows (MsmGeom::twin)
     int c;
     __device__ __forceinline__ MsmDigitIter(const uint32_t* sw_, const MsmGeom& g)
-        : sw(sw_), carry(0), mask((1u << g.c) - 1u), half(1u << (g.c - 1)), pos(0), j(0), c(g.c) {}
+        : sw(sw_), carry(0), mask((1u << g.c) - 1u), half(1u << (g.c - 1)), pos(0), j(0), twin_w(g.twin ? (uint32_t)g.W : 0u), c(g.c) {}
     // 32 bits of the scalar from bit `bit` on, zeros beyond bit 255 (re-read from L1/L2 instead of indexing a register array dynamically;
     // the last window starts below bit 256)
     __device__ __forceinline__ uint32_t bits(uint32_t bit) const {
@@ -37,7 +37,8 @@ struct MsmDigitIter {
         const uint64_t two = ((uint64_t)(w + 1 < 8 ? sw[w + 1] : 0u) << 32) | sw[w];
         return (uint32_t)(two >> off);
     }
-    // The next digit: call W times, window after window; false = this window's digit is zero.  table: the window.
+    // The next digit: call W times, window after window; false = this window's digit is zero.  table: the window — or, with doubled
+    // rows, W + the window for a magnitude of odd valuation, whose bucket is that of half the magnitude (msm_twin_bucket, msm_geom.h).
     __device__ __forceinline__ bool next(uint32_t& table, uint32_t& bucket, uint32_t& neg) {
         uint32_t v = (bits(pos) & mask) + carry;
         table = j++;
@@ -50,6 +51,11 @@ struct MsmDigitIter {
             carry = 1;
         }
         bucket = v - 1;
+        if (twin_w && v != 0) {
+            uint32_t mult;
+            bucket = msm_twin_bucket(c, v, mult);
+            if (mult) table += twin_w;
+        }
         return v != 0;
     }
 };

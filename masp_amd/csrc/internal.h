@@ -34,6 +34,15 @@
 #define MASP_SUBSET_BITS 2
 #endif
 static_assert(MASP_SUBSET_BITS == 0 || MASP_SUBSET_BITS == 2 || MASP_SUBSET_BITS == 3, "subset blocks are 4 or 8 bases wide");
+// Doubled window rows (msm_geom_twin, device/msm_geom.h) behind the tables that batches use, when a context is not told otherwise
+// (masp_hip_ctx_set_window_row_multiples, include/masp_hip.h): bit 0 = the merged h + l sets, bit 1 = a, b_g1, b_g2.  A compile-time default,
+// so that two builds can be compared with bench.py.  3, and with it 13-bit windows for a / b where the width is the loader's choice and
+// would be 12: + 2.3 % proofs/s on Spend; h + l alone (+ 1.0 %) and every table at 12 bits (+ 0.7 %) did not clear the run-to-run spread
+// (MEASUREMENTS.md "Doubled window rows").
+#ifndef MASP_TWIN_ROWS
+#define MASP_TWIN_ROWS 3
+#endif
+static_assert(MASP_TWIN_ROWS >= 0 && MASP_TWIN_ROWS <= 3, "bit 0: h + l, bit 1: a, b_g1, b_g2");
 // Of a query's witness scalars that the R1CS does not prove boolean, the percentage taken to be full width where the bucket tree's scratch
 // is sized (masp_hip_ctx_set_tree_entry_share, include/masp_hip.h).  MEASUREMENTS.md "Entry bound" has the shares observed over the three
 // circuits: the largest, 98 %, with a quarter on top is past 100, so the default is every one of them.
@@ -159,6 +168,10 @@ struct Circuit {
     // a lone proof (every G2 addition is 40 dependent 384-bit products on one lane), and with 128 instead of 2 048 buckets
     // the gather / weighted-sum levels nearly vanish for 45 % more (chip-filling) accumulation work; n = 0: not built
     BasesG2 b2_lone;
+    // a and b_g1 in the plain geometry, for lone proofs only, where the batch tables have doubled window rows: the class-wise weighted
+    // sum of such a set has no quad-lane form (k_msm_twin_combine is one lane), and a lone proof waits for exactly those chains — with
+    // the batch tables it took 4.0 instead of 3.8 ms.  n = 0: not built, lone proofs use a / b1.
+    BasesG1 a_lone, b1_lone;
     // alpha_g1, beta_g1, delta_g1 and every point of the a / b_g1 queries lie in the prime-order subgroup (tested when the
     // circuit is loaded): s*A and r*B1 may then go through the endomorphism (k_groth16_var_mul).  A CRS with a curve point
     // outside the subgroup — the reference reads it unchecked — keeps the plain double-and-add, whose bytes are the reference's
@@ -352,6 +365,11 @@ struct masp_hip_ctx {
     // block width (log2) of the subset rows behind the tables of circuits loaded from now on, resolved: 0 = none, 2 or 3
     // (masp_hip_ctx_set_boolean_block_bits; the build's default is MASP_SUBSET_BITS)
     int boolean_block_bits = MASP_SUBSET_BITS;
+    // which of the next loaded circuit's batch tables get doubled window rows: bit 0 = h + l, bit 1 = a, b_g1, b_g2
+    // (masp_hip_ctx_set_window_row_multiples; the build's default is MASP_TWIN_ROWS)
+    int twin_rows = MASP_TWIN_ROWS;
+    // the building-block MSM entry points (masp_hip_msm_g1_multi ...) double their rows only when told so explicitly: set(ctx, 1)
+    bool twin_rows_msm = false;
     // the quotient's form for circuits loaded from now on: 0 = evaluation form, 1 = coefficient form (masp_hip_ctx_set_quotient_form)
     int quotient_form = 0;
     // how a batch in evaluation form runs its transforms: 0 = the three fused kernels, 1 = the separate passes (masp_hip_ctx_set_quotient_schedule);

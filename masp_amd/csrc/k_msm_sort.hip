@@ -13,12 +13,12 @@ int msm_sort_enqueue(hipStream_t s, uint32_t n, const MsmGeom& g, MsmSortBuf& sb
         last_hip_error() = "MSM window width must be 2..16 bits: the bucket histogram lives in LDS";
         return MASP_HIP_E_INVALID_ARG;
     }
-    const uint64_t rows = (uint64_t)n * (uint32_t)g.W + sub.rows();  // the window rows and the subset rows behind them
+    const uint64_t rows = (uint64_t)n * (uint32_t)g.tables() + sub.rows();  // the window rows (doubled ones included) and the subset rows behind them
     if (rows > 0x7ffffffeull) {
         last_hip_error() = "msm_sort_enqueue: the base set has more table rows than an entry's 31 bits can name";
         return MASP_HIP_E_INVALID_ARG;
     }
-    if (sub.bits && ((sub.bits != 2 && sub.bits != 3) || sub.b_end < sub.b_first || ((uint64_t)sub.b_end << sub.bits) > n || sub.row0 != n * (uint32_t)g.W ||
+    if (sub.bits && ((sub.bits != 2 && sub.bits != 3) || sub.b_end < sub.b_first || ((uint64_t)sub.b_end << sub.bits) > n || sub.row0 != n * (uint32_t)g.tables() ||
                      !sub.bad)) {
         last_hip_error() = "msm_sort_enqueue: subset rows that do not belong to this base set";
         return MASP_HIP_E_INVALID_ARG;

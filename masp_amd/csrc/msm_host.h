@@ -40,14 +40,14 @@ struct MsmBases {
         if (!ent_bound) return worst;
         return std::min<size_t>(worst, ((size_t)ent_bound + (size_t)g.nb * (unit - 1) + unit - 1) / unit * unit);
     }
-    TabRow<O>* tab = nullptr;  // rows() rows of 128 / 256 bytes: g.W * n window rows, then the subset rows
+    TabRow<O>* tab = nullptr;  // rows() rows of 128 / 256 bytes: g.W * n window rows (twin: as many doubled ones behind them), then the subset rows
     int import_status = 0;     // PT_* bits seen while decoding
     // Subset rows behind the window tables (MsmSubset, device/msm_geom.h): for the aligned blocks of 2^sub_bits consecutive bases that lie
     // wholly inside [sub_lo, sub_hi), every sum of a non-empty subset — a block of boolean scalars is one entry of bucket 0.
     MsmSubset sub;                       // sub.bits == 0: none; sub.bad is owned by this object
     uint32_t sub_lo = 0, sub_hi = 0;     // the covered index range the blocks of `sub` were cut from
     const MsmSubset& subset() const { return sub; }
-    uint64_t rows() const { return (uint64_t)n * (uint32_t)g.W + sub.rows(); }
+    uint64_t rows() const { return (uint64_t)n * (uint32_t)g.tables() + sub.rows(); }
 
     ~MsmBases() { release(); }
     void release() {
@@ -59,22 +59,28 @@ struct MsmBases {
     // Window width by the number of scalars expected to be neither 0 nor 1 (`n_eff`; the caller knows the witness
     // statistics of its circuit, a generic caller passes n): per non-trivial scalar the accumulation costs W = 256/c
     // mixed additions, per bucket the gather + weighted sum cost ~5.5 full additions.
-    static MsmGeom pick_geom(uint32_t n_eff) {
-        int c = n_eff >= (1u << 16) ? 16 : n_eff >= (1u << 12) ? 12 : n_eff >= (1u << 8) ? 10 : 7;
+    // twin (doubled window rows, msm_geom_twin): a window bit more costs two thirds of the buckets it did, which moves the balance by
+    // log2(3/2) = 0.6 bit: the sets that took 12 bits take 13 (2 731 buckets against 2 048, 20 windows against 22 — measured on a / b of
+    // all three MASP circuits, MEASUREMENTS.md "Doubled window rows"); 16 bits is the widest the sort takes, and the widths below 12 serve
+    // sets of fewer than 4 096 non-trivial scalars, which no MASP circuit has: they stay as they are, unmeasured.
+    // (the geometry returned is the plain one of that width: load_device applies the doubling)
+    static MsmGeom pick_geom(uint32_t n_eff, bool twin = false) {
+        int c = n_eff >= (1u << 16) ? 16 : n_eff >= (1u << 12) ? (twin ? 13 : 12) : n_eff >= (1u << 8) ? 10 : 7;
         return msm_geom(c);
     }
     // raw: device pointer to n uncompressed points (bellman wire format)          [msm_impl.hpp]
     // force_c: window width (0: pick_geom).  sub_bits_ / [sub_lo_, sub_hi_): subset rows (0: none; the range is cut to [0, n))
+    // twin_: doubled window rows (msm_geom_twin, device/msm_geom.h) — not for a base set with a point at infinity, which stays as it was
     int load_device(const uint8_t* d_raw, uint32_t n_, hipStream_t s, uint32_t n_eff = 0xffffffffu, int force_c = 0, int sub_bits_ = 0,
-                    uint32_t sub_lo_ = 0, uint32_t sub_hi_ = 0xffffffffu);
+                    uint32_t sub_lo_ = 0, uint32_t sub_hi_ = 0xffffffffu, bool twin_ = false);
     int load_host(const uint8_t* raw, uint32_t n_, hipStream_t s, uint32_t n_eff = 0xffffffffu, int force_c = 0, int sub_bits_ = 0, uint32_t sub_lo_ = 0,
-                  uint32_t sub_hi_ = 0xffffffffu) {
+                  uint32_t sub_hi_ = 0xffffffffu, bool twin_ = false) {
         uint8_t* d_raw = nullptr;
         if (n_) {
             HIP_TRY(dev_malloc(&d_raw, (size_t)n_ * BYTES));
             HIP_TRY(hipMemcpyAsync(d_raw, raw, (size_t)n_ * BYTES, hipMemcpyHostToDevice, s));
         }
-        int rc = load_device(d_raw, n_, s, n_eff, force_c, sub_bits_, sub_lo_, sub_hi_);
+        int rc = load_device(d_raw, n_, s, n_eff, force_c, sub_bits_, sub_lo_, sub_hi_, twin_);
         if (d_raw) dev_free(d_raw);
         return rc;
     }
@@ -131,7 +137,7 @@ struct MsmSortBuf {
         const size_t need_ent = std::max(padded_entries(n_, g_, pad_log_), cap_ent), ng = ranges_for(n_, np_);
         const size_t bins = std::max<size_t>(g_.nb >> 7, 1);
         const size_t hist_need = (size_t)np_ * ng * g_.nb, crel_need = (size_t)np_ * ng * bins;
-        const bool want_tmpf = has_tmpf || msm_rows_wide(std::max<uint64_t>(rows_, (uint64_t)n_ * (uint32_t)g_.W));
+        const bool want_tmpf = has_tmpf || msm_rows_wide(std::max<uint64_t>(rows_, (uint64_t)n_ * (uint32_t)g_.tables()));
         if (need_ent <= cap_ent && (size_t)g_.nb <= cap_nb && np_ <= cap_np && hist_need <= cap_hist && crel_need <= cap_crel && want_tmpf == has_tmpf)
             return MASP_HIP_OK;
         const size_t need_nb = std::max<size_t>(g_.nb, cap_nb), need_np = std::max<size_t>(np_, cap_np);
@@ -490,7 +496,7 @@ int msm_enqueue(hipStream_t s, const MsmBases<O, BYTES>& B, MsmWorkspace<O>& ws,
 // and then the same row layout of their subset rows, whose bad-block bitmaps the loader unites (masp_hip_circuit_load)
 template <class A, class B>
 inline bool msm_same_sort(const A& a, const B& b) {
-    return a.n == b.n && a.g.c == b.g.c;
+    return a.n == b.n && a.g.c == b.g.c && a.g.twin == b.g.twin;
 }
 
 typedef MsmBases<FpOps, 96> BasesG1;

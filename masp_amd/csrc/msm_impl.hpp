@@ -27,11 +27,11 @@ static inline uint32_t log2_ceil_u64(uint64_t n) {
 
 template <class O, int BYTES>
 int MsmBases<O, BYTES>::load_device(const uint8_t* d_raw, uint32_t n_, hipStream_t s, uint32_t n_eff, int force_c, int sub_bits_, uint32_t sub_lo_,
-                                    uint32_t sub_hi_) {
+                                    uint32_t sub_hi_, bool twin_) {
         release();
         n = n_;
         this->n_eff = std::min(n_eff, n_);
-        g = force_c ? msm_geom(force_c) : pick_geom(std::min(n_eff, n_));
+        g = force_c ? msm_geom(force_c) : pick_geom(std::min(n_eff, n_), twin_);
         if (n == 0) return MASP_HIP_OK;
         if (sub_bits_ != 0 && sub_bits_ != 2 && sub_bits_ != 3) {
             last_hip_error() = "MsmBases: subset blocks are 4 or 8 bases wide";
@@ -40,14 +40,21 @@ int MsmBases<O, BYTES>::load_device(const uint8_t* d_raw, uint32_t n_, hipStream
         // the blocks that lie wholly inside the covered range, by absolute index
         sub_lo = std::min(sub_lo_, n);
         sub_hi = std::min(sub_hi_, n);
-        if (sub_bits_) {
-            MsmSubset u;
-            u.bits = (uint32_t)sub_bits_;
-            u.b_first = (uint32_t)(((uint64_t)sub_lo + (1u << sub_bits_) - 1) >> sub_bits_);
-            u.b_end = sub_hi >> sub_bits_;
-            u.row0 = n * (uint32_t)g.W;
-            if (u.b_end > u.b_first) sub = u;
-        }
+        // the geometry (with doubled window rows if asked for) and the subset rows behind its tables
+        auto layout = [&](bool twin) {
+            if (twin) g = msm_geom_twin(g.c);
+            else g = msm_geom(g.c);
+            sub = MsmSubset();
+            if (sub_bits_) {
+                MsmSubset u;
+                u.bits = (uint32_t)sub_bits_;
+                u.b_first = (uint32_t)(((uint64_t)sub_lo + (1u << sub_bits_) - 1) >> sub_bits_);
+                u.b_end = sub_hi >> sub_bits_;
+                u.row0 = n * (uint32_t)g.tables();
+                if (u.b_end > u.b_first) sub = u;
+            }
+        };
+        layout(twin_);
         if (rows() > 0x7ffffffeull) {
             sub = MsmSubset();
             last_hip_error() = "MsmBases: more table rows than an entry's 31 bits can name";
@@ -59,7 +66,24 @@ int MsmBases<O, BYTES>::load_device(const uint8_t* d_raw, uint32_t n_, hipStream
         HIP_TRY(hipMemsetAsync(d_status, 0, sizeof(int), s));
         dim3 grid((n + 63) / 64), block(64);
         MASP_LAUNCH((k_msm_import<O, BYTES>), grid, block, 0, s, d_raw, tab, n, d_status);
-        MASP_LAUNCH((k_msm_precompute<O>), grid, block, 0, s, tab, n, g.c, g.W);
+        if (twin_) {
+            // Doubled rows only for a base set without a point at infinity: such a set keeps the plain geometry, its window rows at
+            // infinity as before, in a table of the plain size (the imported rows move over).  No other row can double to infinity: these
+            // curves have no point of order two, so with this no entry of a twin set ever names a row at infinity.  MsmGeom::twin of the
+            // loaded set says which it became (masp_hip_circuit_window_row_multiples).
+            HIP_TRY(hipMemcpyAsync(&import_status, d_status, sizeof(int), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            if (import_status & PT_INFINITY) {
+                layout(false);
+                TabRow<O>* plain = nullptr;
+                HIP_TRY(dev_malloc(&plain, sizeof(TabRow<O>) * (size_t)rows()));
+                HIP_TRY(hipMemcpyAsync(plain, tab, sizeof(TabRow<O>) * (size_t)n, hipMemcpyDeviceToDevice, s));
+                HIP_TRY(hipStreamSynchronize(s));
+                dev_free(tab);
+                tab = plain;
+            }
+        }
+        MASP_LAUNCH((k_msm_precompute<O>), grid, block, 0, s, tab, n, g.c, g.W, g.twin);
         if (sub.bits) {
             HIP_TRY(dev_malloc(&sub.bad, sizeof(uint32_t) * sub.bad_words()));
             HIP_TRY(hipMemsetAsync(sub.bad, 0, sizeof(uint32_t) * sub.bad_words(), s));
@@ -119,7 +143,7 @@ void MsmWorkspace<O>::reduce_to_one_lanes(hipStream_t s, uint32_t np, const Xyzz
 // per point (OT: O itself, its lane-pair form for G2, FpQuadOps for a lone proof's G1 MSMs).
 template <class O, class OT>
 void msm_tails_enqueue(hipStream_t s, MsmWorkspace<O>& ws, const uint32_t* start, uint32_t nb, uint32_t nchunks, uint32_t np, bool lone, Xyzz<O>* d_out,
-                       size_t out_stride) {
+                       size_t out_stride, int twin_c = 0) {
     constexpr uint32_t LN = OT::LANES;
     if constexpr (OT::LANES <= 2) {
         if (!lone) {  // a batch: single partials copied, one lane per chunk boundary for the buckets that straddle one (k_msm_bucket_gather_split)
@@ -155,6 +179,33 @@ void msm_tails_enqueue(hipStream_t s, MsmWorkspace<O>& ws, const uint32_t* start
     // the 32 768 of h+l: 64 = 2.3 instead of 3.2 additions per bucket) — with other batches in flight total work counts, not
     // the length of the chain; a lone proof takes 4 (shortest dependent chain).
     uint32_t g_log = nb <= WSUM_L ? 0 : WSUM_G_LOG_MIN;  // at most 128 buckets: one per lane, one workgroup, no second level
+    if (twin_c) {
+        // Doubled window rows (twin_c: the window width of the twin geometry; msm_geom_twin, device/msm_geom.h): the buckets are classes of
+        // dense odd weights.  ONE launch of the level kernel over all of them, chunks as a batch takes them (at least nb / 4 buckets, so
+        // that the single lane of k_msm_twin_combine has a handful of chunks — a lone proof over such a set pays the longer chain);
+        // the classes smaller than a chunk, s >= s0, are the last workgroup's.
+        if constexpr (!OT::REPLICATED) {
+            g_log = 3;
+            while (g_log < 6u && (1u << (g_log + 1 + WSUM_L_LOG)) <= nb) ++g_log;
+            const uint32_t cs_log = g_log + WSUM_L_LOG, cs = 1u << cs_log;
+            uint32_t s0 = 0;
+            while (s0 < msm_twin_classes(twin_c) && msm_twin_class(twin_c, s0).size >= cs) ++s0;
+            const uint32_t big = s0 < msm_twin_classes(twin_c) ? msm_twin_class(twin_c, s0).off >> cs_log : msm_twin_buckets(twin_c) >> cs_log;
+            const uint32_t span = s0 < msm_twin_classes(twin_c) ? (1u << (twin_c - 1)) >> (2u * s0) : 0u;  // the last chunk's dense values (<= cs)
+            const size_t st_stride = big + 1;
+            const dim3 grid(big + 1, np), block((1u << wsum_points_log<OT>()) * LN);
+            switch (g_log) {
+#define MASP_WSUM_CASE(GL) \
+    case GL: MASP_LAUNCH((k_msm_wsum_level<OT, GL, true>), grid, block, 0, s, ws.bkt, (size_t)nb, span, 0u, ws.S[0], ws.T, st_stride); break;
+                MASP_WSUM_CASE(3) MASP_WSUM_CASE(4) MASP_WSUM_CASE(5) MASP_WSUM_CASE(6)
+#undef MASP_WSUM_CASE
+            }
+            MASP_LAUNCH((k_msm_twin_combine<O>), dim3(1, np), dim3(64), 0, s, ws.S[0], ws.T, st_stride, twin_c, s0, (int)cs_log, d_out, out_stride);
+        } else {
+            last_hip_error() = "msm_tails_enqueue: doubled window rows have no replicated-lane form";  // (msm_reduce_enqueue never asks for one)
+        }
+        return;
+    }
     if (!lone) {
         const uint32_t hi = 6u;
         g_log = 3;
@@ -197,10 +248,10 @@ void msm_tails_enqueue(hipStream_t s, MsmWorkspace<O>& ws, const uint32_t* start
         MASP_LAUNCH((k_msm_combine<O>), dim3(1, np), dim3(64), 0, s, ws.tsum, level, (int)(g_log + WSUM_L_LOG), d_out, out_stride);
 }
 #ifndef MASP_TAILS_QUAD_UNIT
-extern template void msm_tails_enqueue<FpOps, FpQuadOps>(hipStream_t, MsmWorkspace<FpOps>&, const uint32_t*, uint32_t, uint32_t, uint32_t, bool, Xyzz<FpOps>*, size_t);
+extern template void msm_tails_enqueue<FpOps, FpQuadOps>(hipStream_t, MsmWorkspace<FpOps>&, const uint32_t*, uint32_t, uint32_t, uint32_t, bool, Xyzz<FpOps>*, size_t, int);
 #endif
 #ifndef MASP_TAILS_OCT_UNIT
-extern template void msm_tails_enqueue<Fp2Ops, Fp2OctOps>(hipStream_t, MsmWorkspace<Fp2Ops>&, const uint32_t*, uint32_t, uint32_t, uint32_t, bool, Xyzz<Fp2Ops>*, size_t);
+extern template void msm_tails_enqueue<Fp2Ops, Fp2OctOps>(hipStream_t, MsmWorkspace<Fp2Ops>&, const uint32_t*, uint32_t, uint32_t, uint32_t, bool, Xyzz<Fp2Ops>*, size_t, int);
 #endif
 
 template <class O, int BYTES>
@@ -208,7 +259,7 @@ int msm_reduce_enqueue(hipStream_t s, const MsmBases<O, BYTES>& B, const MsmSort
                        MsmProfile* prof) {
     const MsmGeom& g = B.g;
     const uint32_t n = B.n, np = sb.np;
-    if (sb.n != n || sb.g.c != g.c) {
+    if (sb.n != n || sb.g.c != g.c || sb.g.twin != g.twin) {
         last_hip_error() = "msm_reduce_enqueue: sort does not match the base set";
         return MASP_HIP_E_INVALID_ARG;
     }
@@ -313,17 +364,19 @@ int msm_reduce_enqueue(hipStream_t s, const MsmBases<O, BYTES>& B, const MsmSort
     // first working workgroup (x = 0: bucket 0) would land on the same XCD: keep gridDim.x odd.
     // a lone proof's G1 tails run over quads (device/quad.hpp): their chains of dependent additions are what it waits for.
     // (Those kernels live in a translation unit of their own, k_msm_g1_lone.hip.)
+    // (A set with doubled window rows keeps the one-lane / lane-pair forms for a lone proof too: its class-wise weighted sum exists in those.)
+    const int twin_c = g.twin ? g.c : 0;
     if constexpr (std::is_same<O, FpOps>::value) {
-        if (lone)
+        if (lone && !twin_c)
             msm_tails_enqueue<O, FpQuadOps>(s, ws, start, nb, nchunks, np, lone, d_out, out_stride);
         else
-            msm_tails_enqueue<O, FpOps>(s, ws, start, nb, nchunks, np, lone, d_out, out_stride);
+            msm_tails_enqueue<O, FpOps>(s, ws, start, nb, nchunks, np, lone, d_out, out_stride, twin_c);
     } else {
         // ... and its G2 tails over groups of four lane pairs (device/oct.hpp)
-        if (lone && (MASP_G2_OCT_LONE))
+        if (lone && !twin_c && (MASP_G2_OCT_LONE))
             msm_tails_enqueue<O, Fp2OctOps>(s, ws, start, nb, nchunks, np, lone, d_out, out_stride);
         else
-            msm_tails_enqueue<O, typename TailLaneOps<O>::type>(s, ws, start, nb, nchunks, np, lone, d_out, out_stride);
+            msm_tails_enqueue<O, typename TailLaneOps<O>::type>(s, ws, start, nb, nchunks, np, lone, d_out, out_stride, twin_c);
     }
     return launch_status();  // (a launch the runtime refused: MASP_LAUNCH, util.h)
 }

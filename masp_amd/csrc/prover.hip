@@ -392,10 +392,13 @@ static int enqueue_proofs(Slot& sl, Circuit& C, uint32_t np, const Fr* d_w, size
         // priority streams for A / B1, were measured: every chain then starts within 0.5 ms, they slow each other down and the
         // proof takes the same 6.1 - 6.4 ms: profiles/r03x_same_box_ab_lone_threads.txt.)
         const bool own_b2 = C.b2_lone.n != 0;  // B2 on its own narrow windows: sorts for itself
+        // (where the batch tables of a / b_g1 have doubled window rows, a lone proof has plain ones of its own: Circuit::a_lone)
+        const BasesG1 &Al = C.a_lone.n ? C.a_lone : C.a, &B1l = C.b1_lone.n ? C.b1_lone : C.b1;
+        const bool share_bl = C.nbq && msm_same_sort(B1l, C.b2);
         auto chain_a = [&]() -> int {
             int r;
             if (C.na) launch_gather_scalars(sl.aux[1], d_w, w_stride, C.a_var.p, C.na, sl.sa.p, np);
-            if ((r = msm_enqueue(sl.aux[1], C.a, sl.ws_a, (const uint32_t*)sl.sa.p, (size_t)C.na * 8, sl.res1.p + 2, 4, np))) return r;
+            if ((r = msm_enqueue(sl.aux[1], Al, sl.ws_a, (const uint32_t*)sl.sa.p, (size_t)C.na * 8, sl.res1.p + 2, 4, np))) return r;
             sl.lone_mark(sl.aux[1], 1);
             launch_groth16_var_mul(sl.aux[1], 0, sl.res1.p, d_rs, 16, sl.asm1.p, np, C.g1_endo);
             sl.lone_mark(sl.aux[1], 2);
@@ -405,11 +408,11 @@ static int enqueue_proofs(Slot& sl, Circuit& C, uint32_t np, const Fr* d_w, size
             int r;
             if (C.nbq) launch_gather_scalars(sl.aux[2], d_w, w_stride, C.b_var.p, C.nbq, sl.sb.p, np);
             HIP_TRY(hipEventRecord(sl.ev_sort_b, sl.aux[2]));  // B2 on aux[3] reads sb (and, without tables of its own, B1's sort) behind this
-            if (share_b) {
-                if ((r = msm_sort_enqueue(sl.aux[2], C.b1.n, C.b1.g, sl.ws_b.sort, (const uint32_t*)sl.sb.p, (size_t)C.nbq * 8, np, 0, C.b1.subset()))) return r;
+            if (share_bl) {
+                if ((r = msm_sort_enqueue(sl.aux[2], B1l.n, B1l.g, sl.ws_b.sort, (const uint32_t*)sl.sb.p, (size_t)C.nbq * 8, np, 0, B1l.subset()))) return r;
                 if (!own_b2) HIP_TRY(hipEventRecord(sl.ev_sort_b, sl.aux[2]));
-                if ((r = msm_reduce_enqueue(sl.aux[2], C.b1, sl.ws_b.sort, sl.ws_b, sl.res1.p + 3, 4))) return r;
-            } else if ((r = msm_enqueue(sl.aux[2], C.b1, sl.ws_b, (const uint32_t*)sl.sb.p, (size_t)C.nbq * 8, sl.res1.p + 3, 4, np))) {
+                if ((r = msm_reduce_enqueue(sl.aux[2], B1l, sl.ws_b.sort, sl.ws_b, sl.res1.p + 3, 4))) return r;
+            } else if ((r = msm_enqueue(sl.aux[2], B1l, sl.ws_b, (const uint32_t*)sl.sb.p, (size_t)C.nbq * 8, sl.res1.p + 3, 4, np))) {
                 return r;
             }
             sl.lone_mark(sl.aux[2], 3);
@@ -418,7 +421,7 @@ static int enqueue_proofs(Slot& sl, Circuit& C, uint32_t np, const Fr* d_w, size
             HIP_TRY(hipStreamWaitEvent(sl.aux[3], sl.ev_sort_b, 0));
             if (own_b2) {
                 if ((r = msm_enqueue(sl.aux[3], C.b2_lone, sl.ws2, (const uint32_t*)sl.sb.p, (size_t)C.nbq * 8, sl.res2.p, 1, np))) return r;
-            } else if (share_b) {
+            } else if (share_bl) {
                 if ((r = msm_reduce_enqueue(sl.aux[3], C.b2, sl.ws_b.sort, sl.ws2, sl.res2.p, 1))) return r;
             } else if ((r = msm_enqueue(sl.aux[3], C.b2, sl.ws2, (const uint32_t*)sl.sb.p, (size_t)C.nbq * 8, sl.res2.p, 1, np))) {
                 return r;
@@ -930,6 +933,24 @@ int masp_hip_ctx_get_boolean_block_bits(const masp_hip_ctx* ctx, int32_t* out) {
     return MASP_HIP_OK;
 }
 
+int masp_hip_ctx_set_window_row_multiples(masp_hip_ctx* ctx, int32_t v) {
+    if (!ctx || v < -1 || v > 2) return MASP_HIP_E_INVALID_ARG;
+    const int resolved = v == 0 ? (int)(MASP_TWIN_ROWS) : v < 0 ? 0 : v == 1 ? 3 : 1;
+    auto set = [&](masp_hip_ctx* c) {
+        std::unique_lock<std::shared_mutex> lock(c->mu);
+        c->twin_rows = resolved;
+        c->twin_rows_msm = v == 1;
+    };
+    set(ctx);
+    for (masp_hip_ctx* c : ctx->children) set(c);
+    return MASP_HIP_OK;
+}
+int masp_hip_ctx_get_window_row_multiples(const masp_hip_ctx* ctx, int32_t* out) {
+    if (!ctx || !out) return MASP_HIP_E_INVALID_ARG;
+    *out = (ctx->children.empty() ? ctx : ctx->children[0])->twin_rows;
+    return MASP_HIP_OK;
+}
+
 int masp_hip_ctx_set_quotient_form(masp_hip_ctx* ctx, int32_t form) {
     if (!ctx || (form != MASP_HIP_QUOTIENT_EVALUATION && form != MASP_HIP_QUOTIENT_COEFFICIENT)) return MASP_HIP_E_INVALID_ARG;
     auto set = [&](masp_hip_ctx* c) {
@@ -1216,9 +1237,14 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
     // h + l —: a third of a witness is the scalar 1, and an aligned block of boolean scalars becomes one entry.  The tables that only lone
     // proofs use (h, l, b2_lone) have none.
     const int sub_bits = ctx->boolean_block_bits;
+    // doubled window rows (msm_geom_twin, device/msm_geom.h) behind the tables that batches use: two thirds as many buckets.  b_g1 and b_g2
+    // share a sort only with the same layout; a point at infinity in one of them (the circuit is refused below) leaves that one plain.
+    const bool twin_hl = ctx->twin_rows & 1, twin_ab = ctx->twin_rows & 2;
+    // (with doubled rows a / b take 13-bit windows where the width is the loader's choice: MsmBases::pick_geom)
     if ((rc = C->h.load_host(L.h, (uint32_t)(C->m - 1), s, 0xffffffffu, c_h_lone)) || (rc = C->l.load_host(L.l, L.n_l, s, eff(L.n_l), c_la)) ||
-        (rc = C->a.load_host(L.a, L.n_a, s, eff(L.n_a), c_la, sub_bits)) || (rc = C->b1.load_host(L.b_g1, L.n_b1, s, eff(L.n_b1), c_b, sub_bits)) ||
-        (rc = C->b2.load_host(L.b_g2, L.n_b2, s, eff(L.n_b2), c_b2, sub_bits)))
+        (rc = C->a.load_host(L.a, L.n_a, s, eff(L.n_a), c_la, sub_bits, 0, 0xffffffffu, twin_ab)) ||
+        (rc = C->b1.load_host(L.b_g1, L.n_b1, s, eff(L.n_b1), c_b, sub_bits, 0, 0xffffffffu, twin_ab)) ||
+        (rc = C->b2.load_host(L.b_g2, L.n_b2, s, eff(L.n_b2), c_b2, sub_bits, 0, 0xffffffffu, twin_ab)))
         return fail(ctx, rc);
     if (C->b1.sub.bits && C->b2.sub.bits && msm_same_sort(C->b1, C->b2)) {
         // b_g2 is reduced from b_g1's sorted digit list (enqueue_proofs: share_b): the two tables have the same row layout, and the sort
@@ -1233,6 +1259,9 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
             hipMemcpyAsync(C->b2.sub.bad, w1.data(), 4 * (size_t)words, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
             return fail(ctx, MASP_HIP_E_HIP);
     }
+    // plain tables of a / b_g1 for lone proofs where the batch tables were doubled (Circuit::a_lone)
+    if (C->a.g.twin && (rc = C->a_lone.load_host(L.a, L.n_a, s, eff(L.n_a), c_la, sub_bits))) return fail(ctx, rc);
+    if (C->b1.g.twin && (rc = C->b1_lone.load_host(L.b_g1, L.n_b1, s, eff(L.n_b1), c_b, sub_bits))) return fail(ctx, rc);
     {
         const int c_lone = ctx->opt.window_bits_b2_lone;  // 0 = lone proofs share the batch tables (and B1's sort)
         if (c_lone > 0 && L.n_b2 && (rc = C->b2_lone.load_host(L.b_g2, L.n_b2, s, eff(L.n_b2), c_lone))) return fail(ctx, rc);
@@ -1244,7 +1273,7 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
         memcpy(cat.data(), L.h, 96 * nh);
         memcpy(cat.data() + 96 * nh, L.l, 96 * (size_t)L.n_l);
         // (subset rows over the l part only: the quotient's coefficients are uniform in Fr)
-        if ((rc = C->hl.load_host(cat.data(), (uint32_t)(nh + L.n_l), s, 0xffffffffu, c_hl, sub_bits, (uint32_t)nh))) return fail(ctx, rc);
+        if ((rc = C->hl.load_host(cat.data(), (uint32_t)(nh + L.n_l), s, 0xffffffffu, c_hl, sub_bits, (uint32_t)nh, 0xffffffffu, twin_hl))) return fail(ctx, rc);
     }
     int st = C->h.import_status | C->l.import_status | C->a.import_status | C->b1.import_status | C->b2.import_status;
     if (st) return MASP_HIP_E_PARAMS_FORMAT;  // includes infinity inside a query vector, which bellman rejects
@@ -1273,7 +1302,7 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
         if (E.usable) {
             const masp::EvalLayout& lay = E.lay;
             // (subset rows over the aux part only: the coset evaluations are as uniform in Fr as the coefficients were)
-            if ((rc = C->hl_eval.load_device(E.d_raw.p, (uint32_t)lay.n(), s, 0xffffffffu, c_hl, sub_bits, (uint32_t)lay.aux_off(), (uint32_t)lay.in_off())))
+            if ((rc = C->hl_eval.load_device(E.d_raw.p, (uint32_t)lay.n(), s, 0xffffffffu, c_hl, sub_bits, (uint32_t)lay.aux_off(), (uint32_t)lay.in_off(), twin_hl)))
                 return fail(ctx, rc);
             if ((rc = C->eval_in_var.upload(lay.used_inputs.data(), lay.used_inputs.size(), s))) return fail(ctx, rc);
             if (hipStreamSynchronize(s) != hipSuccess) return fail(ctx, MASP_HIP_E_HIP);
@@ -1328,6 +1357,15 @@ int masp_hip_circuit_quotient_form(const masp_hip_ctx* ctx, uint32_t slot, int32
     std::shared_lock<std::shared_mutex> lock(const_cast<masp_hip_ctx*>(ctx)->mu);
     if (slot >= MASP_HIP_MAX_CIRCUITS || !ctx->circ[slot]) return MASP_HIP_E_NOT_LOADED;
     *form = ctx->circ[slot]->hl_eval.n ? MASP_HIP_QUOTIENT_EVALUATION : MASP_HIP_QUOTIENT_COEFFICIENT;
+    return MASP_HIP_OK;
+}
+int masp_hip_circuit_window_row_multiples(const masp_hip_ctx* ctx, uint32_t slot, int32_t* sets) {
+    if (!ctx || !sets) return MASP_HIP_E_INVALID_ARG;
+    if (!ctx->children.empty()) return masp_hip_circuit_window_row_multiples(ctx->children[0], slot, sets);
+    std::shared_lock<std::shared_mutex> lock(const_cast<masp_hip_ctx*>(ctx)->mu);
+    if (slot >= MASP_HIP_MAX_CIRCUITS || !ctx->circ[slot]) return MASP_HIP_E_NOT_LOADED;
+    const Circuit& C = *ctx->circ[slot];
+    *sets = (C.hl.g.twin ? 1 : 0) | (C.hl_eval.n && C.hl_eval.g.twin ? 2 : 0) | (C.a.g.twin ? 4 : 0) | (C.b1.g.twin ? 8 : 0) | (C.b2.g.twin ? 16 : 0);
     return MASP_HIP_OK;
 }
 int masp_hip_circuit_eval_bases(const masp_hip_ctx* ctx, uint32_t slot, uint8_t* bases, size_t cap_points, size_t* n_points, uint32_t* input_cols,
@@ -1731,7 +1769,10 @@ static int msm_multi(masp_hip_ctx* ctx, const uint8_t* bases, size_t n, const ui
     DevBuf<Xyzz<O>> res;
     DevBuf<uint8_t> d_out;
     int rc;
-    if ((rc = B.load_host(bases, (uint32_t)n, s, 0xffffffffu, window_bits, block_bits, (uint32_t)sub_lo, (uint32_t)sub_hi))) return fail(ctx, rc);
+    // (doubled window rows only where the context was told to use them behind every table, masp_hip_ctx_set_window_row_multiples(ctx, 1):
+    // by default this building block keeps the plain geometry, whose bucket 0 is the digits of magnitude 1 — what bucket0_entries reports)
+    if ((rc = B.load_host(bases, (uint32_t)n, s, 0xffffffffu, window_bits, block_bits, (uint32_t)sub_lo, (uint32_t)sub_hi, ctx->twin_rows_msm)))
+        return fail(ctx, rc);
     if (B.import_status & (PT_BAD_FLAGS | PT_NOT_CANONICAL)) return MASP_HIP_E_PARAMS_FORMAT;
     if ((rc = ctx->tmp_scalars.upload((const Fr*)scalars, n * np, s)) || (rc = res.reserve(np)) || (rc = d_out.reserve(BYTES * np))) return fail(ctx, rc);
     if ((rc = msm_enqueue(s, B, ws, (const uint32_t*)ctx->tmp_scalars.p, n * 8, res.p, 1, (uint32_t)np))) return fail(ctx, rc);

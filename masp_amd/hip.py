@@ -124,10 +124,13 @@ def load_library():
         L.masp_hip_msm_g2_multi_ex.argtypes = [vp, vp, sz, vp, sz, C.c_int, C.c_int, sz, sz, vp, vp]
         L.masp_hip_ctx_set_boolean_block_bits.argtypes = [vp, C.c_int32]
         L.masp_hip_ctx_get_boolean_block_bits.argtypes = [vp, C.POINTER(C.c_int32)]
+        L.masp_hip_ctx_set_window_row_multiples.argtypes = [vp, C.c_int32]
+        L.masp_hip_ctx_get_window_row_multiples.argtypes = [vp, C.POINTER(C.c_int32)]
     if hasattr(L, "masp_hip_ctx_set_quotient_form"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
         L.masp_hip_ctx_set_quotient_form.argtypes = [vp, C.c_int32]
         L.masp_hip_ctx_get_quotient_form.argtypes = [vp, C.POINTER(C.c_int32)]
         L.masp_hip_circuit_quotient_form.argtypes = [vp, u32, C.POINTER(C.c_int32)]
+        L.masp_hip_circuit_window_row_multiples.argtypes = [vp, u32, C.POINTER(C.c_int32)]
         L.masp_hip_circuit_eval_bases.argtypes = [vp, u32, vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz)]
     if hasattr(L, "masp_hip_ctx_set_quotient_schedule"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
         L.masp_hip_ctx_set_quotient_schedule.argtypes = [vp, C.c_int32]
@@ -625,6 +628,18 @@ class Context:
         self._check(self._L.masp_hip_ctx_get_boolean_block_bits(self._h, C.byref(v)))
         return int(v.value)
 
+    def set_window_row_multiples(self, v):
+        """Doubled window rows behind the batch tables of circuits loaded FROM NOW ON (two thirds as many buckets per MSM): 0 = the build's
+        default, -1 = off, 1 = every table that batches use, 2 = the merged h + l tables only."""
+        self._check(self._L.masp_hip_ctx_set_window_row_multiples(self._h, int(v)))
+
+    @property
+    def window_row_multiples(self):
+        """the resolved value as a mask: bit 0 = the merged h + l tables, bit 1 = a, b_g1, b_g2"""
+        v = C.c_int32(0)
+        self._check(self._L.masp_hip_ctx_get_window_row_multiples(self._h, C.byref(v)))
+        return int(v.value)
+
     def set_quotient_form(self, form):
         """How the batches of circuits loaded FROM NOW ON compute their quotient: QUOTIENT_EVALUATION (0, the default: four transforms per
         proof over bases derived when the circuit is loaded) or QUOTIENT_COEFFICIENT (1: six transforms over the h and l queries)."""
@@ -651,6 +666,13 @@ class Context:
         """the form the batches of the circuit in `slot` really use (coefficient form also where a derived base came out at infinity)"""
         v = C.c_int32(0)
         self._check(self._L.masp_hip_circuit_quotient_form(self._h, int(slot), C.byref(v)))
+        return int(v.value)
+
+    def circuit_window_row_multiples(self, slot):
+        """the tables of the circuit in `slot` that really have doubled window rows: bit 0 h + l, bit 1 the evaluation form's merged table,
+        bit 2 a, bit 3 b_g1, bit 4 b_g2 (a table with a point at infinity stays plain)"""
+        v = C.c_int32(0)
+        self._check(self._L.masp_hip_circuit_window_row_multiples(self._h, int(slot), C.byref(v)))
         return int(v.value)
 
     def circuit_eval_bases(self, slot):
