@@ -507,6 +507,35 @@ int masp_hip_merkle_last_timing(masp_hip_ctx* ctx, double ms[3]);
 int masp_hip_merkle_tree_append(masp_hip_ctx* ctx, uint64_t start, const uint8_t frontier[32 * 32], size_t n, const uint8_t* row,
                                 uint8_t* nodes_out, size_t nodes_capacity, size_t* n_nodes, int64_t* bad_index);
 
+/* ---- Nullifiers and note commitments of a wallet's notes on the GPU ----
+ * masp_hip_sapling_note_nullifiers <- Note::cmu and Note::nf(&nk, position) (masp_primitives/src/sapling.rs:828) for n notes:
+ *    g = the asset generator of the identifier (cofactor not cleared), g_d = diversifier.g_d(),
+ *    rcm = the 32 bytes (lead byte 1) | PRF^expand(rseed, [4]) mod r_J (lead byte 2),
+ *    cm = PedersenHash(NoteCommitment, repr(g) | value | repr(g_d) | pk_d) + [rcm] G_ncr, cmu = its affine u,
+ *    rho = cm + [position] G_nf (all 64 bits of position count), nf = BLAKE2s-256(personal "MASP__nf", nk | repr(rho)).
+ * asset_identifiers, pk_ds, rseeds (rcm or rseed), nks: n x 32; diversifiers: n x 11; values, positions: n; lead_bytes: n, each 1
+ * (BeforeZip212) or 2 (AfterZip212).  n <= 2^22 a call; the device works through them in chunks of 2^19, a few hundred MB of state.
+ * Result: status (n bytes), cmus_out (n x 32, may be NULL: not downloaded) and nfs_out (n x 32).  status[i] is 0, or the first check that
+ * fails, in this order: 1 the asset identifier has no generator, 2 the diversifier has no g_d, 3 pk_d is not the canonical encoding of a
+ * curve point, 4 the lead byte is neither 1 nor 2, or lead byte 1 with rcm >= r_J, 5 nk is not the canonical encoding of a curve point.
+ * A note with status != 0 has 32 zero bytes in either output and changes neither the return code nor its neighbours' results.
+ * What is checked of pk_d and nk is what masp_host_note_cmu checks of pk_d: the encoding is canonical and on the curve.  The reference's
+ * types make both of them points of the prime-order subgroup; that is NOT tested here, and the bytes hashed are the bytes given.
+ * n = 0: MASP_HIP_OK, no GPU work, no array is read.  A NULL array (cmus_out apart) with n > 0, or n > 2^22: MASP_HIP_E_INVALID_ARG.
+ * The result is deterministic, and the same for either number of lanes per note.  Re-entrant next to proving and verification calls; on
+ * the context's first verifier stream, under the lock of the note scans and the trees (a context runs one of them at a time: they share
+ * the Pedersen table), no stream or hardware queue of its own; on a multi-device context on the first device.
+ * masp_host_sapling_note_nullifiers (include/masp_host.h) is the same on the host.
+ * masp_hip_note_nullifiers_configure - lanes_per_note: 1 or 8 lanes add a note's table points, 0 (the default) = by the number of notes
+ * (DESIGN.md 13); for measurements and tests, the bytes do not depend on it.  Anything else: MASP_HIP_E_INVALID_ARG.
+ * masp_hip_note_nullifiers_last_timing - of the last such call of this context, summed over its chunks from HIP events on its stream:
+ * ms[0] the host-to-device copies, ms[1] the kernels, ms[2] the device-to-host copies. */
+int masp_hip_sapling_note_nullifiers(masp_hip_ctx* ctx, size_t n, const uint8_t* asset_identifiers, const uint64_t* values,
+                                     const uint8_t* diversifiers, const uint8_t* pk_ds, const uint8_t* lead_bytes, const uint8_t* rseeds,
+                                     const uint8_t* nks, const uint64_t* positions, uint8_t* status, uint8_t* cmus_out, uint8_t* nfs_out);
+int masp_hip_note_nullifiers_configure(masp_hip_ctx* ctx, int lanes_per_note);
+int masp_hip_note_nullifiers_last_timing(masp_hip_ctx* ctx, double ms[3]);
+
 /* ---- measurement hooks (bench.py): device-resident workloads, HIP-event timing on the ctx stream ---- */
 /* Keeps `n` jobs' assignments resident in HBM; returns a handle (>= 0) or a negative error code. */
 int masp_hip_batch_upload(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs);

@@ -116,6 +116,16 @@ int masp_host_asset_generator(const uint8_t id[32], uint8_t out32[32]);
 int masp_host_value_commitment(const uint8_t id[32], uint64_t value, const uint8_t rcv[32], uint8_t out32[32], uint8_t uv64[64]);
 int masp_host_note_cmu(const uint8_t id[32], uint64_t value, const uint8_t diversifier[11], const uint8_t pk_d[32], const uint8_t rcm[32],
                        uint8_t cmu32[32]);
+/* Note::cmu and Note::nf(&nk, position) (masp_primitives/src/sapling.rs) for n <= 2^22 notes on `threads` host threads: the arguments and
+ * results of masp_hip_sapling_note_nullifiers (include/masp_hip.h) without the context.  asset_identifiers, pk_ds, rseeds (rcm for lead
+ * byte 1, rseed for lead byte 2), nks, cmus_out (may be NULL), nfs_out: n x 32; diversifiers: n x 11; lead_bytes, status: n.
+ * status[i]: 0, or the first check that fails: 1 the asset identifier has no generator, 2 the diversifier has no g_d, 3 pk_d does not decode,
+ * 4 the lead byte is neither 1 nor 2 or rcm >= r_J, 5 nk does not decode; the note's outputs are then zeros and nothing else changes.
+ * pk_d and nk are decoded as masp_host_note_cmu decodes pk_d (canonical, on the curve) and hashed as the given bytes; the reference's
+ * types make both points of the prime-order subgroup, which is NOT tested here.  MASP_HOST_E_INVALID: a NULL array with n > 0, n > 2^22. */
+int masp_host_sapling_note_nullifiers(size_t n, const uint8_t* asset_identifiers, const uint64_t* values, const uint8_t* diversifiers,
+                                      const uint8_t* pk_ds, const uint8_t* lead_bytes, const uint8_t* rseeds, const uint8_t* nks,
+                                      const uint64_t* positions, uint8_t* status, uint8_t* cmus_out, uint8_t* nfs_out, int threads);
 int masp_host_merkle_hash(unsigned depth, const uint8_t lhs[32], const uint8_t rhs[32], uint8_t out32[32]);
 /* empty_root(0..32) of the commitment tree, 33 x 32 bytes: the uncommitted leaf 1 and the roots of the empty subtrees above it */
 void masp_host_merkle_empty_roots(uint8_t out[33 * 32]);

@@ -9,7 +9,7 @@ from .r1cs import R1cs  # noqa: F401
 from .verifier import (BatchValidator, Bundle, ConvertDescription, OutputDescription, SaplingVerificationContext,  # noqa: F401
                        SpendDescription)
 from . import note_encryption  # noqa: F401
-from .note_encryption import (CompactShieldedOutput, Note, PaymentAddress, Rseed, ShieldedOutput, sapling_note_encrypt,  # noqa: F401
+from .note_encryption import (CompactShieldedOutput, Note, PaymentAddress, Rseed, ShieldedOutput, note_nf, sapling_note_encrypt,  # noqa: F401
                               try_sapling_compact_note_decryption, try_sapling_note_decryption)
 from . import merkle_tree  # noqa: F401
 from .merkle_tree import CommitmentTree, FrozenCommitmentTree, IncrementalWitness, MerklePath, advance, empty_root  # noqa: F401

@@ -685,6 +685,59 @@ int masp_host_note_cmu(const uint8_t id[32], uint64_t value, const uint8_t diver
     note_commitment(g, value, gd, pk, rcm).to_affine().u.to_bytes(cmu32);
     return 0;
 }
+// Note::cmu and Note::nf(&nk, position) (masp_primitives/src/sapling.rs) for n notes, dealt to `threads` host threads sixteen at a time;
+// what masp_hip_sapling_note_nullifiers computes, and its other side in the tests.  status: the first check that fails (1 asset
+// identifier, 2 diversifier, 3 pk_d, 4 lead byte or rcm, 5 nk), the note's outputs then zeros.  pk_d and nk are decoded as
+// masp_host_note_cmu decodes pk_d: canonical and on the curve, no subgroup test.
+int masp_host_sapling_note_nullifiers(size_t n, const uint8_t* asset_identifiers, const uint64_t* values, const uint8_t* diversifiers,
+                                      const uint8_t* pk_ds, const uint8_t* lead_bytes, const uint8_t* rseeds, const uint8_t* nks,
+                                      const uint64_t* positions, uint8_t* status, uint8_t* cmus_out, uint8_t* nfs_out, int threads) {
+    if (n > ((size_t)1 << 22)) return MASP_HOST_E_INVALID;
+    if (n == 0) return MASP_HOST_OK;
+    if (!asset_identifiers || !values || !diversifiers || !pk_ds || !lead_bytes || !rseeds || !nks || !positions || !status || !nfs_out)
+        return MASP_HOST_E_INVALID;
+    (void)pedersen_windows();   // the lazily built tables, before the threads race for them
+    (void)generators();
+    auto one = [&](size_t i) {
+        uint8_t* nf = nfs_out + 32 * i;
+        memset(nf, 0, 32);
+        if (cmus_out) memset(cmus_out + 32 * i, 0, 32);
+        JPoint g, gd, pk, nk;
+        uint8_t rcm[32];
+        const uint8_t lead = lead_bytes[i], *r = rseeds + 32 * i;
+        if (!asset_generator(g, asset_identifiers + 32 * i)) return 1;
+        if (!group_hash(gd, diversifiers + 11 * i, 11, "MASP__gd")) return 2;
+        if (!JPoint::from_bytes(pk, pk_ds + 32 * i)) return 3;
+        if (lead == 1) {
+            if (!rj_is_canonical(r)) return 4;   // jubjub::Fr::from_repr(rcm)
+            memcpy(rcm, r, 32);
+        } else if (lead == 2) {
+            rseed_scalar(rcm, r, 4);
+        } else {
+            return 4;
+        }
+        if (!JPoint::from_bytes(nk, nks + 32 * i)) return 5;
+        const JPoint cm = note_commitment(g, values[i], gd, pk, rcm);
+        if (cmus_out) cm.to_affine().u.to_bytes(cmus_out + 32 * i);
+        nullifier(nf, cm, positions[i], nk);   // (decoding accepts canonical encodings only: nk's bytes are the ones that came)
+        return 0;
+    };
+    const int nt = std::max(1, std::min<int>(threads, 256));
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (;;) {
+            const size_t i0 = next.fetch_add(16);
+            if (i0 >= n) return;
+            for (size_t i = i0; i < std::min(n, i0 + 16); ++i) status[i] = (uint8_t)one(i);
+        }
+    };
+    std::vector<std::thread> pool;
+    if (n >= 64)   // (a few notes are not worth the threads' start)
+        for (int k = 1; k < nt; ++k) pool.emplace_back(work);
+    work();
+    for (auto& th : pool) th.join();
+    return MASP_HOST_OK;
+}
 int masp_host_merkle_hash(unsigned depth, const uint8_t lhs[32], const uint8_t rhs[32], uint8_t out32[32]) {
     Fr l, r;
     if (!Fr::from_bytes(l, lhs) || !Fr::from_bytes(r, rhs)) return 1;

@@ -468,6 +468,12 @@ struct masp_hip_ctx {
     DevBuf<uint32_t> mt_nodes, mt_bad, mt_paths, mt_empties;
     DevBuf<uint64_t> mt_pos;
     double mt_last_ms[3] = {0, 0, 0};    // masp_hip_merkle_last_timing: upload, kernels, download (under slot_mu)
+    // the note nullifiers (k_nullifier.hip: masp_hip_sapling_note_nullifiers) run under ns_mu too, on the first verifier stream, and read
+    // nsc_table beside a table of their own (nullifier_table.h: the windows of G_ncr and G_nf); a chunk's arrays as they come, the
+    // per-note state, and cmu | nf | status
+    DevBuf<uint8_t> nf_table, nf_in, nf_state, nf_out;
+    std::atomic<int> nf_lanes{0};        // masp_hip_note_nullifiers_configure: lanes per note, 0 = by the number of notes
+    double nf_last_ms[3] = {0, 0, 0};    // masp_hip_note_nullifiers_last_timing: upload, kernels, download (under slot_mu)
 };
 
 namespace masp {

@@ -170,6 +170,10 @@ def load_library():
         L.masp_hip_merkle_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
     if hasattr(L, "masp_hip_merkle_tree_append"):
         L.masp_hip_merkle_tree_append.argtypes = [vp, C.c_uint64, vp, sz, vp, vp, sz, C.POINTER(sz), C.POINTER(C.c_int64)]
+    if hasattr(L, "masp_hip_sapling_note_nullifiers"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
+        L.masp_hip_sapling_note_nullifiers.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.masp_hip_note_nullifiers_configure.argtypes = [vp, C.c_int]
+        L.masp_hip_note_nullifiers_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
     L.masp_hip_batch_upload.argtypes = [vp, sz, vp]
     L.masp_hip_batch_prove_resident.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.masp_hip_batch_prove_resident_steps.argtypes = [vp, C.c_int, sz, vp, vp, C.POINTER(C.c_float)]
@@ -562,6 +566,32 @@ class Context:
         """(upload ms, kernel ms, download ms) of the last tree of this context, from HIP events on its stream"""
         ms = (C.c_double * 3)()
         self._check(self._L.masp_hip_merkle_last_timing(self._h, ms))
+        return ms[0], ms[1], ms[2]
+
+    # ---- nullifiers and note commitments of a wallet's notes on the GPU ----
+    def note_nullifiers(self, asset_identifiers, values, diversifiers, pk_ds, lead_bytes, rseeds, nks, positions, want_cmus=True):
+        """Note::cmu and Note::nf(&nk, position) for n notes on the GPU (masp_hip_sapling_note_nullifiers): arrays in (n x 32 bytes each,
+        diversifiers n x 11, values / positions / lead bytes n) -> (status uint8[n], cmus uint8[n, 32] or None with want_cmus=False: not
+        downloaded, nfs uint8[n, 32]).  status: 0, or 1 asset identifier, 2 diversifier, 3 pk_d, 4 lead byte or rcm, 5 nk; such a note's
+        outputs are zeros.  host.note_nullifiers is the same on the host."""
+        from .host import note_nullifier_args
+        args = note_nullifier_args(asset_identifiers, values, diversifiers, pk_ds, lead_bytes, rseeds, nks, positions)
+        n = args[0].shape[0]
+        status, nfs = np.zeros(n, np.uint8), np.zeros((n, 32), np.uint8)
+        cmus = np.zeros((n, 32), np.uint8) if want_cmus else None
+        p = [_p(a) if n else None for a in args]
+        self._check(self._L.masp_hip_sapling_note_nullifiers(self._h, n, *p, _p(status) if n else None, _p(cmus) if n else None,
+                                                             _p(nfs) if n else None))
+        return status, cmus, nfs
+
+    def note_nullifiers_configure(self, lanes_per_note=0):
+        """how many lanes add a note's table points: 1 or 8; 0 = by the number of notes (the default).  The bytes do not depend on it."""
+        self._check(self._L.masp_hip_note_nullifiers_configure(self._h, int(lanes_per_note)))
+
+    def note_nullifiers_last_timing(self):
+        """(upload ms, kernel ms, download ms) of the last note_nullifiers call of this context, HIP events summed over its chunks"""
+        ms = (C.c_double * 3)()
+        self._check(self._L.masp_hip_note_nullifiers_last_timing(self._h, ms))
         return ms[0], ms[1], ms[2]
 
     # ---- building blocks ----

@@ -58,6 +58,7 @@ def load_library():
         L.masp_host_asset_generator.argtypes = [cp, cp]
         L.masp_host_value_commitment.argtypes = [cp, u64, cp, cp, cp]
         L.masp_host_note_cmu.argtypes = [cp, u64, cp, cp, cp, cp]
+        L.masp_host_sapling_note_nullifiers.argtypes = [C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]
         L.masp_host_merkle_hash.argtypes = [C.c_uint, cp, cp, cp]
         L.masp_host_merkle_empty_roots.argtypes = [vp]
         L.masp_host_merkle_empty_roots.restype = None
@@ -393,6 +394,35 @@ def note_cmu(identifier, value, diversifier, pk_d, rcm):
     if load_library().masp_host_note_cmu(_b(identifier), value, _b(diversifier, 11), _b(pk_d), _b(rcm), out):
         raise ValueError("invalid note")
     return out.raw
+
+
+def note_nullifier_args(asset_identifiers, values, diversifiers, pk_ds, lead_bytes, rseeds, nks, positions):
+    """the arguments of either note_nullifiers as contiguous arrays: uint8[n, 32] (bytes or arrays), uint64[n], uint8[n, 11], uint8[n]"""
+    def u8(a, w):
+        if isinstance(a, (bytes, bytearray, memoryview)):
+            a = np.frombuffer(a, dtype=np.uint8)
+        return np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, w) if w else np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+    out = (u8(asset_identifiers, 32), np.ascontiguousarray(values, dtype=np.uint64).reshape(-1), u8(diversifiers, 11), u8(pk_ds, 32),
+           u8(lead_bytes, 0), u8(rseeds, 32), u8(nks, 32), np.ascontiguousarray(positions, dtype=np.uint64).reshape(-1))
+    n = out[0].shape[0]
+    if any(a.shape[0] != n for a in out):
+        raise ValueError("note_nullifiers: the arrays differ in length: %s" % ([a.shape[0] for a in out],))
+    return out
+
+
+def note_nullifiers(asset_identifiers, values, diversifiers, pk_ds, lead_bytes, rseeds, nks, positions, threads=None, want_cmus=True):
+    """masp_host_sapling_note_nullifiers: Note::cmu and Note::nf(&nk, position) for n notes on host threads (default: effective_cpus()).
+    Arrays in (n x 32 bytes each, diversifiers n x 11, values / positions / lead bytes n) -> (status uint8[n], cmus uint8[n, 32] or None
+    with want_cmus=False, nfs uint8[n, 32]).  status: 0, or 1 asset identifier, 2 diversifier, 3 pk_d, 4 lead byte or rcm, 5 nk; such a note's
+    outputs are zeros."""
+    args = note_nullifier_args(asset_identifiers, values, diversifiers, pk_ds, lead_bytes, rseeds, nks, positions)
+    n = args[0].shape[0]
+    status, nfs = np.zeros(n, np.uint8), np.zeros((n, 32), np.uint8)
+    cmus = np.zeros((n, 32), np.uint8) if want_cmus else None
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    _check(load_library().masp_host_sapling_note_nullifiers(n, *[vp(a) for a in args], vp(status), vp(cmus), vp(nfs),
+                                                           int(threads or effective_cpus())))
+    return status, cmus, nfs
 
 
 def merkle_hash(depth, lhs, rhs):

@@ -13,7 +13,10 @@ note commitment and the esk check for the pairs that pass it), so its hits are f
 The sender's side: `encrypt_outgoing_plaintext` makes an output's out_ciphertext (pk_d | esk under the ock = PRF^ock(ovk, cv, cmu, epk)),
 `try_sapling_output_recovery` and `try_sapling_output_recovery_with_ock` read an `OutputDescription` back on the host, and
 `batch.try_output_recovery` scans outputs x ovks on the GPU (masp_hip_sapling_output_recovery_scan: PRF^ock and out_ciphertext's tag for
-every pair) and finishes the pairs whose tag verifies on the host (masp_host_sapling_try_output_recovery_with_ock: everything else)."""
+every pair) and finishes the pairs whose tag verifies on the host (masp_host_sapling_try_output_recovery_with_ock: everything else).
+
+Once a note is the wallet's: `note_nf` is Note::nf(&nk, position) on the host, and `batch.note_nullifiers` computes the commitments and
+nullifiers of a list of notes on the GPU (masp_hip_sapling_note_nullifiers) or on host threads."""
 import os
 from collections import namedtuple
 
@@ -53,6 +56,29 @@ def note_derive_esk(note):
 
 def note_cmu(note, to):
     return H.note_cmu(note.asset_identifier, note.value, to.diversifier, note.pk_d, note_rcm(note))
+
+
+def _nullifier_arrays(items):
+    """items: (Note, PaymentAddress, nk, position) each -> the eight arrays of either note_nullifiers"""
+    items = list(items)
+    cat = lambda f: np.frombuffer(b"".join(f(it) for it in items), dtype=np.uint8)
+    return (cat(lambda it: H._b(it[0].asset_identifier)), np.array([int(it[0].value) for it in items], dtype=np.uint64),
+            cat(lambda it: H._b(it[1].diversifier, 11)), cat(lambda it: H._b(it[0].pk_d)),
+            np.array([int(it[0].rseed.lead_byte) & 0xff for it in items], dtype=np.uint8), cat(lambda it: H._b(it[0].rseed.bytes)),
+            cat(lambda it: H._b(it[2])), np.array([int(it[3]) for it in items], dtype=np.uint64))
+
+
+NULLIFIER_STATUS = {1: "the asset identifier has no generator", 2: "the diversifier has no g_d", 3: "pk_d does not decode",
+                    4: "the lead byte is neither 1 nor 2, or rcm is not below r_J", 5: "nk does not decode"}
+
+
+def note_nf(note, to, nk, position):
+    """Note::nf(&nk, position) -> the 32-byte nullifier, on the host.  nk: the 32 bytes of the NullifierDerivingKey; position: the note's
+    position in the commitment tree, below 2^64.  ValueError where the note has none (NULLIFIER_STATUS)."""
+    status, _, nfs = H.note_nullifiers(*_nullifier_arrays([(note, to, nk, position)]), threads=1, want_cmus=False)
+    if status[0]:
+        raise ValueError("note_nf: %s" % NULLIFIER_STATUS.get(int(status[0]), int(status[0])))
+    return nfs[0].tobytes()
 
 
 def note_plaintext_bytes(note, to, memo=EMPTY_MEMO):
@@ -162,6 +188,18 @@ class batch:
             if result[o] is None:
                 result[o] = (_parse_compact(pt.tobytes(), pk.tobytes()), k)
         return result
+
+    @staticmethod
+    def note_nullifiers(items, ctx, threads=None):
+        """items: (Note, PaymentAddress, nk, position) each -> one entry per item, in order: (cmu, nf), 32 bytes each, or None where the
+        note has none (note_nf raises there).  ctx: a masp_amd.Context, the notes run on its GPU (masp_hip_sapling_note_nullifiers); None:
+        on `threads` host threads."""
+        items = list(items)
+        if not items:
+            return []
+        arrays = _nullifier_arrays(items)
+        status, cmus, nfs = H.note_nullifiers(*arrays, threads=threads) if ctx is None else ctx.note_nullifiers(*arrays)
+        return [None if s else (c.tobytes(), f.tobytes()) for s, c, f in zip(status.tolist(), cmus, nfs)]
 
     @staticmethod
     def try_output_recovery(ovks, outputs, ctx, lead_byte=2):

@@ -1,0 +1,65 @@
+"""Build of the test-only shim tests/native/nullifier_dev.hip (device/nullifier.hpp on the host, and the product's nullifier kernels for
+either lane width on the GPU), with the product's flags as device_shim.py reads them from the Makefile; rebuilt when it or a source it
+includes is newer than the library."""
+import ctypes as C
+import glob
+import os
+import subprocess
+
+import numpy as np
+
+import device_shim
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SRC = os.path.join(HERE, "native", "nullifier_dev.hip")
+SO = os.path.join(HERE, "native", "_nullifier_dev.so")
+CSRC = os.path.join(os.path.dirname(HERE), "masp_amd", "csrc")
+_lib = None
+
+
+def dependencies():
+    return [SRC, device_shim.MAKEFILE, os.path.join(CSRC, "k_nullifier.hip")] + \
+        [p for pat in ("device/*.hpp", "device/*.h", "host/*.h", "*.h") for p in glob.glob(os.path.join(CSRC, pat))]
+
+
+def load():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in dependencies()):
+            flags = device_shim.makefile_flags()
+            tmp = SO + ".%d.tmp" % os.getpid()
+            subprocess.check_call([device_shim.HIPCC] + flags + ["-shared", SRC, "-o", tmp])
+            os.replace(tmp, SO)
+        _lib = C.CDLL(SO)
+        _lib.nfd_table_mul_host.argtypes = [C.c_int, C.c_char_p, C.c_char_p]
+    return _lib
+
+
+def table_mul(which, k):
+    """[k] G_ncr (which = 0) or [k] G_nf (which = 1) from the device's fixed-base table, on the host -> 32 bytes"""
+    out = C.create_string_buffer(32)
+    assert load().nfd_table_mul_host(which, int(k).to_bytes(32, "little"), out) == 0
+    return out.raw
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def steps_host(arrays, lanes=1, trace=False):
+    """device/nullifier.hpp's steps on the CPU -> (status, cmus, nfs[, trace uint8[n, 208]: msg 104 | rcm 32 | cm 32 | rho 32 | bad 8])"""
+    n = arrays[0].shape[0]
+    status, cmus, nfs = np.zeros(n, np.uint8), np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8)
+    tr = np.zeros((n, 208), np.uint8) if trace else None
+    rc = load().nfd_steps_host(n, *[_p(a) for a in arrays], int(lanes), _p(status), _p(cmus), _p(nfs), _p(tr))
+    assert rc == 0, rc
+    return (status, cmus, nfs, tr) if trace else (status, cmus, nfs)
+
+
+def run_gpu(arrays, lanes):
+    """the product's four kernels with `lanes` (1 or 8) lanes per note -> (status, cmus, nfs)"""
+    n = arrays[0].shape[0]
+    status, cmus, nfs = np.zeros(n, np.uint8), np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8)
+    rc = load().nfd_run_gpu(n, *[_p(a) for a in arrays], int(lanes), _p(status), _p(cmus), _p(nfs))
+    assert rc == 0, rc
+    return status, cmus, nfs
