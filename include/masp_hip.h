@@ -136,7 +136,7 @@ typedef struct {
     int32_t window_bits_h_lone;      /* (round 5, appended: struct_size tells) window width of the h query's OWN table, which only lone
                                         proofs use — a batch runs h and l as one MSM over the merged table on window_bits_h.  Narrower
                                         windows mean more additions in the chip-filling accumulation and far fewer buckets in the
-                                        latency-bound tails a lone proof waits for.  Default: see resolve_options (prover.hip) */
+                                        latency-bound tails a lone proof waits for.  Default: see resolve_options (ctx.hip) */
     int32_t digit_recoding;          /* RESERVED, must be 0.  (Round 5: 1 = width-(c + 1) non-adjacent-form digits over a table of 2^t P for every
                                         bit position t — 8 - 15 % fewer bucket additions for 16.6 GB of tables per Spend circuit, which is beyond
                                         the ~3.5 GiB of randomly gathered table an XCD's L2 TLB reaches: Spend -8 %, Output +2 % proofs/s.  Built,
@@ -145,7 +145,7 @@ typedef struct {
     int32_t window_bits_b2;          /* (round 6, appended) window width of the b_g2 query's batch tables when it should differ from
                                         window_bits_b: a G2 addition costs three G1 additions, so b_g2's optimum is wider than b_g1's —
                                         at the price of a sort of its own (with equal widths b_g2 is reduced from b_g1's sorted digit
-                                        list).  0 = the default (resolve_options, prover.hip); -1 = as window_bits_b */
+                                        list).  0 = the default (resolve_options, ctx.hip); -1 = as window_bits_b */
 } masp_hip_options;
 void masp_hip_options_default(masp_hip_options* opt);
 /* More hardware queues than this make a process SLOWER (round 6, profiles/r06_second_context_root_cause.txt): the runtime creates a

@@ -1,5 +1,6 @@
-// Host-side types shared by the translation units of libmasp_hip (prover.hip: context, CRS loading, pipeline, C ABI;
-// k_setup.hip: parameter generation).  No kernels here.
+// Host-side types shared by the translation units of libmasp_hip (ctx.hip: context; circuit_load.hip: CRS loading; prove.hip: slot
+// pool, launch sequences, masp_hip_prove_batch; hooks.hip: building blocks and measurement hooks; k_setup.hip: parameter generation).
+// No kernels here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -221,7 +222,7 @@ struct Slot {
     uint8_t* h_proof = nullptr;  // pinned, batch_cap x 192
     size_t h_proof_cap = 0;
     int* h_flags = nullptr;      // pinned
-    // Launch graphs of lone proofs (prover.hip: enqueue_proofs_graphed; opt-in).  The ~250 launches of one proof take the
+    // Launch graphs of lone proofs (prove.hip: enqueue_proofs_graphed; opt-in).  The ~250 launches of one proof take the
     // host about as long to enqueue as the GPU takes to run them; captured once per (circuit, buffers, form) they replay as
     // one hipGraphLaunch.  A graph holds raw pointers into workspaces that grow on demand: `graph_epoch` is the value of
     // device_alloc_epoch() it was captured under, and any later allocation or release drops every graph of the slot.
@@ -361,7 +362,7 @@ struct masp_hip_ctx {
     int device = 0;
     // multi-device front (masp_hip_ctx_create_multi): one full context per device; this object only shards and forwards
     std::vector<masp_hip_ctx*> children;
-    masp_hip_options opt{};   // resolved at creation (prover.hip: resolve_options); the library reads no environment
+    masp_hip_options opt{};   // resolved at creation (ctx.hip: resolve_options); the library reads no environment
     // block width (log2) of the subset rows behind the tables of circuits loaded from now on, resolved: 0 = none, 2 or 3
     // (masp_hip_ctx_set_boolean_block_bits; the build's default is MASP_SUBSET_BITS)
     int boolean_block_bits = MASP_SUBSET_BITS;

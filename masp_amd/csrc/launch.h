@@ -1,5 +1,5 @@
 // Launch wrappers of the kernel families that live in their own translation units (k_ntt.hip, k_groth16.hip): what the
-// host-side pipeline (prover.hip, k_setup.hip) calls instead of launching those kernels itself, so that every kernel
+// host-side pipeline (circuit_load.hip, prove.hip, hooks.hip, k_setup.hip) calls instead of launching those kernels itself, so that every kernel
 // family compiles once, side by side with the others.  All of them only enqueue on `s`.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -150,6 +150,12 @@ struct PerDeviceOnce {
         return (ok[dev >> 6] & bit) != 0;
     }
 };
+// an event that is destroyed with its scope, whichever way the function returns (create it with hipEventCreate(&ev.e))
+struct ScopedEvent {
+    hipEvent_t e = nullptr;
+    ~ScopedEvent() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
 }  // namespace masp
 
 #define MASP_LAUNCH(kernel, grid, block, shmem, stream, ...)                                \

@@ -1,4 +1,4 @@
-"""The lone proof's captured launch graph (masp_hip_options::lone_proof_graph, prover.hip: enqueue_proofs_graphed): a caller
+"""The lone proof's captured launch graph (masp_hip_options::lone_proof_graph, prove.hip: enqueue_proofs_graphed): a caller
 that proves one description at a time — what SaplingProvingContext::spend_proof does
 (/root/reference/masp_proofs/src/sapling/prover.rs:45-172) — can get its third and later proofs from one hipGraphLaunch (opt-in: with ROCm 7.2 the replay is slower than the launches,
 profiles/r04_lone_proof_graph_ab.txt).  The

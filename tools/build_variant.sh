@@ -11,7 +11,7 @@ out=$root/tools/_build/ab
 mkdir -p $out/$name
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -Wno-unused-variable -Wno-unused-value -Wno-unused-result"
 objs=""
-for u in prover k_msm_sort k_msm_g1 k_msm_g1_lone k_msm_g1_acc k_msm_g1_tree k_msm_g2 k_msm_g2_lone k_msm_g2_acc k_msm_g2_tree k_ntt k_groth16 k_setup k_verify; do
+for u in $(sed -n 's/^UNITS := //p' $csrc/Makefile); do
   if [[ " $* " == *" $u "* ]]; then
     (cd $csrc && /opt/rocm/bin/hipcc $FLAGS $flags -c $u.hip -o $out/$name/$u.o) &
     objs="$objs $out/$name/$u.o"
