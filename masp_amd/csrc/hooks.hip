@@ -282,9 +282,8 @@ int masp_hip_batch_prove_resident_steps(masp_hip_ctx* ctx, int handle, size_t st
         HIP_TRY(hipMemcpyAsync(d_rs.p, tmp.data(), tmp.size(), hipMemcpyHostToDevice, ms));
         HIP_TRY(hipStreamSynchronize(ms));
     }
-    ScopedEvent ev_start, ev_stop;
-    HIP_TRY(hipEventCreate(&ev_start.e));
-    HIP_TRY(hipEventCreate(&ev_stop.e));
+    Event ev_start, ev_stop;
+    if ((rc = ev_start.create()) || (rc = ev_stop.create())) return rc;
     for (size_t si = 0; si < ns; ++si) HIP_TRY(hipMemsetAsync(ctx->slots[si]->flags.p, 0, sizeof(int), ms));
     HIP_TRY(hipEventRecord(ev_start, ms));
     for (size_t si = 0; si < ns; ++si) HIP_TRY(hipStreamWaitEvent(ctx->slots[si]->stream, ev_start, 0));
@@ -416,9 +415,8 @@ int masp_hip_bench_msm(masp_hip_ctx* ctx, int handle, size_t job, int which, int
     const BasesG1* bases[4] = {&C.h, &C.l, &C.a, &C.b1};
     const uint32_t* scal[4] = {(const uint32_t*)sl.h.p, (const uint32_t*)(B.w.p + B.w_off[job] + C.n_inputs), (const uint32_t*)sl.sa.p,
                                (const uint32_t*)sl.sb.p};
-    ScopedEvent e0, e1;
-    HIP_TRY(hipEventCreate(&e0.e));
-    HIP_TRY(hipEventCreate(&e1.e));
+    Event e0, e1;
+    if ((rc = e0.create()) || (rc = e1.create())) return rc;
     HIP_TRY(hipEventRecord(e0, sl.stream));
     for (int it = 0; it < iters; ++it)
         if ((rc = msm_enqueue(sl.stream, *bases[which], sl.ws1, scal[which], 0, sl.res1.p + which, 4, 1))) return fail(ctx, rc);

@@ -185,15 +185,15 @@ struct Circuit {
 // A slot BORROWS its streams from its context's stream table (masp_hip_ctx::streams) and never creates or destroys one.
 struct Slot {
     hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
+    Event done;
     MsmWorkspace<FpOps> ws1;
     MsmWorkspace<Fp2Ops> ws2;
     // lone-proof mode (a batch too small to fill the chip): the five MSMs run side by side on their own streams, each
     // with its own workspace, next to the quotient pipeline on the main stream
     static constexpr int N_AUX = 4;
     hipStream_t aux[N_AUX] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_sort_b = nullptr, ev_fixed = nullptr, ev_join[N_AUX] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ev_uploaded = nullptr;   // behind the host-to-device copies of this slot's batch (masp_hip_ctx::upload_tail)
+    Event ev_fork, ev_sort_b, ev_fixed, ev_join[N_AUX];
+    Event ev_uploaded;   // behind the host-to-device copies of this slot's batch (masp_hip_ctx::upload_tail)
     MsmWorkspace<FpOps> ws_l, ws_a, ws_b;
     DevBuf<Fr> w, inp, abc, wm, ev[3], x0, x1, h, hl, sa, sb;
     DevBuf<G1Xyzz> res1, asm1;  // asm1: the six G1 pieces of the assembly per proof, asm2: s*delta2
@@ -207,21 +207,19 @@ struct Slot {
     // ~60 launches each): timing events recorded behind the stages of the last lone proof while profiling is on
     // (masp_hip_profile_read_lone).  Created on first use.
     static constexpr int N_LONE_MARKS = 12;
-    hipEvent_t ev_lone[N_LONE_MARKS] = {};
+    Event ev_lone[N_LONE_MARKS];
     bool lone_marked = false;
     void lone_mark(hipStream_t st, int id) {
         if (!profiling) return;
-        if (!ev_lone[id] && hipEventCreate(&ev_lone[id]) != hipSuccess) return;
+        if (ev_lone[id].create() != MASP_HIP_OK) return;
         (void)hipEventRecord(ev_lone[id], st);
         if (id == N_LONE_MARKS - 1) lone_marked = true;
     }
     uint32_t ntt_sub = 8;        // masp_hip_options::ntt_sub_batch of the owning context (0 = whole batch)
     const std::atomic<int>* quotient_schedule = nullptr;  // the owning context's (masp_hip_ctx_set_quotient_schedule)
-    uint8_t* h_stage = nullptr;  // pinned staging for the assignment
-    size_t h_stage_cap = 0;
-    uint8_t* h_proof = nullptr;  // pinned, batch_cap x 192
-    size_t h_proof_cap = 0;
-    int* h_flags = nullptr;      // pinned
+    PinnedBuf<uint8_t> h_stage;  // pinned staging for the assignment
+    PinnedBuf<uint8_t> h_proof;  // batch_cap x 192
+    PinnedBuf<int> h_flags;
     // Launch graphs of lone proofs (prove.hip: enqueue_proofs_graphed; opt-in).  The ~250 launches of one proof take the
     // host about as long to enqueue as the GPU takes to run them; captured once per (circuit, buffers, form) they replay as
     // one hipGraphLaunch.  A graph holds raw pointers into workspaces that grow on demand: `graph_epoch` is the value of
@@ -244,21 +242,7 @@ struct Slot {
             if (g.exec) hipGraphExecDestroy(g.exec);
         graphs.clear();
     }
-    ~Slot() {
-        drop_graphs();
-        if (done) hipEventDestroy(done);
-        for (hipEvent_t e : ev_join)
-            if (e) hipEventDestroy(e);
-        for (hipEvent_t e : ev_lone)
-            if (e) hipEventDestroy(e);
-        if (ev_fork) hipEventDestroy(ev_fork);
-        if (ev_uploaded) hipEventDestroy(ev_uploaded);
-        if (ev_sort_b) hipEventDestroy(ev_sort_b);
-        if (ev_fixed) hipEventDestroy(ev_fixed);
-        if (h_stage) hipHostFree(h_stage);
-        if (h_proof) hipHostFree(h_proof);
-        if (h_flags) hipHostFree(h_flags);
-    }
+    ~Slot() { drop_graphs(); }
     // the options of the owning context that the slot's launch sequences depend on
     void configure(const masp_hip_options& o) {
         ntt_sub = (uint32_t)o.ntt_sub_batch;
@@ -277,35 +261,16 @@ struct Slot {
     int init(const std::array<hipStream_t, 5>& streams) {
         stream = streams[0];
         for (int i = 0; i < N_AUX; ++i) aux[i] = streams[1 + i];
-        HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&ev_uploaded, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&ev_sort_b, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&ev_fixed, hipEventDisableTiming));
-        for (hipEvent_t& e : ev_join) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIP_TRY(hipHostMalloc(&h_flags, sizeof(int)));
         int rc;
-        if ((rc = flags.reserve(1))) return rc;
+        for (Event* e : {&done, &ev_fork, &ev_uploaded, &ev_sort_b, &ev_fixed})
+            if ((rc = e->create(hipEventDisableTiming))) return rc;
+        if ((rc = create_events(ev_join, hipEventDisableTiming)) || (rc = h_flags.reserve(1)) || (rc = flags.reserve(1))) return rc;
         return reserve_batch(1);
     }
     int reserve_batch(size_t np) {
         int rc;
         if ((rc = res1.reserve(4 * np)) || (rc = res2.reserve(np)) || (rc = asm1.reserve(6 * np)) || (rc = asm2.reserve(np)) || (rc = rs.reserve(16 * np)) || (rc = proof.reserve(192 * np))) return rc;
-        if (np > h_proof_cap) {
-            if (h_proof) hipHostFree(h_proof);
-            h_proof = nullptr;
-            HIP_TRY(hipHostMalloc(&h_proof, 192 * np));
-            h_proof_cap = np;
-        }
-        return MASP_HIP_OK;
-    }
-    int stage_reserve(size_t bytes) {
-        if (bytes <= h_stage_cap) return MASP_HIP_OK;
-        if (h_stage) hipHostFree(h_stage);
-        h_stage = nullptr;
-        HIP_TRY(hipHostMalloc(&h_stage, bytes));
-        h_stage_cap = bytes;
-        return MASP_HIP_OK;
+        return h_proof.reserve(192 * np);
     }
 };
 
@@ -337,6 +302,75 @@ struct StreamTable {
     }
     ~StreamTable() {
         for (hipStream_t s : distinct()) (void)hipStreamDestroy(s);
+    }
+};
+
+// A device table that is uploaded once per context by whichever call needs it first.  `fresh`: this call enqueued the upload and nothing has
+// confirmed yet that it arrived; WalletState::settle_tables decides at the end of the call.
+template <class T>
+struct OnceTable : DevBuf<T> {
+    bool fresh = false;
+    int ensure(const T* h, size_t n, hipStream_t s) {
+        if (this->p) return MASP_HIP_OK;
+        fresh = true;
+        return this->upload(h, n, s);
+    }
+};
+
+// What the wallet-side entry points of a device context keep between calls: the note scan (k_note_scan.hip), the compact note scan
+// (k_note_scan_compact.hip), the output recovery scan (k_out_recovery.hip), the commitment trees (k_merkle.hip) and the note nullifiers
+// (k_nullifier.hip).  One of these calls runs at a time per context: `mu` guards every member but the atomics and the timing records, and is
+// taken by WalletCall alone.  The scans alternate their chunks between the two verifier streams (streams.vk), each with a buffer set of its
+// own; the trees and the nullifiers run on streams.vk[0].  Every buffer grows on demand and is kept.
+struct WalletState {
+    std::mutex mu;
+    struct NoteScanSet {
+        DevBuf<uint8_t> epk, raw, ct, pts, status, hit_keys;
+        DevBuf<uint32_t> count, hit_idx;
+    };
+    NoteScanSet ns[2];
+    DevBuf<uint32_t> ns_digits;
+    std::atomic<int> ns_signed_digits{1}, ns_inversion{0};   // masp_hip_note_scan_configure; the defaults are the measured winners (KERNELS.md)
+    LastTiming<2> ns_timing;                                 // masp_hip_note_scan_last_timing: upload, kernels
+    // the compact scan decodes the epks into ns[set].epk / pts / status; what it has beyond that: per set the cmus, the 84-byte rows, the
+    // candidate list of stage 1 and the per-candidate state of stage 2 (sized for the launch's pair count), the survivor lists and the final hits
+    struct NoteScanCompactSet {
+        DevBuf<uint8_t> cmu, enc, cand, state, hit_idx, hit_data;
+        DevBuf<uint32_t> count, list;
+    };
+    NoteScanCompactSet nsc[2];
+    DevBuf<uint8_t> nsc_ivks;         // the ivks as they come: stage 2's per-lane scalars
+    OnceTable<uint8_t> nsc_table;     // the Pedersen Niels table and G_ncr behind it (pedersen_table.h): the compact scan, the trees, the nullifiers
+    LastTiming<3> nsc_timing;         // masp_hip_note_scan_compact_last_timing: upload, stage 1, stage 2
+    // output recovery: per set the rows as they come (cv, cmu, epk 32 bytes each, out_ciphertext 80), their eleven 16-byte columns, and the hits
+    struct OutRecoverySet {
+        DevBuf<uint8_t> cv, cmu, epk, cout, cols, hit_ocks;
+        DevBuf<uint32_t> count, hit_idx;
+    };
+    OutRecoverySet orc[2];
+    DevBuf<uint32_t> orc_ovks;        // the ovks, eight words each: the kernel's wave-uniform message words
+    LastTiming<2> orc_timing;         // masp_hip_out_recovery_last_timing: upload, kernels
+    // the trees: the node vector (eight words a node), the first bad input's index, the positions and their paths, empty_root(0..32)
+    DevBuf<uint32_t> mt_nodes, mt_bad, mt_paths;
+    OnceTable<uint32_t> mt_empties;
+    DevBuf<uint64_t> mt_pos;
+    LastTiming<3> mt_timing;          // masp_hip_merkle_last_timing: upload, kernels, download
+    // the nullifiers: a table of their own beside nsc_table (nullifier_table.h: the windows of G_ncr and G_nf), a chunk's arrays as they
+    // come, the per-note state, and cmu | nf | status
+    OnceTable<uint8_t> nf_table;
+    DevBuf<uint8_t> nf_in, nf_state, nf_out;
+    std::atomic<int> nf_lanes{0};     // masp_hip_note_nullifiers_configure: lanes per note, 0 = by the number of notes
+    LastTiming<3> nf_timing;          // masp_hip_note_nullifiers_last_timing: upload, kernels, download
+    // The end of a call that may have uploaded tables: one that failed with a HIP error cannot tell whether they arrived, so they are released
+    // and the next call uploads them again; any other end confirms them.  A table of an earlier call is not marked and survives either way.
+    void settle_tables(int rc) {
+        auto settle = [rc](auto& t) {
+            if (t.fresh && rc == MASP_HIP_E_HIP) t.release();
+            t.fresh = false;
+        };
+        settle(nsc_table);
+        settle(mt_empties);
+        settle(nf_table);
     }
 };
 
@@ -433,48 +467,7 @@ struct masp_hip_ctx {
     DevBuf<uint8_t> jj_points, jj_scalars, jj_partial;
     DevBuf<int> jj_status;
     DevBuf<uint32_t> jj_out;
-    // the note scan (k_note_scan.hip: masp_hip_sapling_trial_decrypt), one at a time per context (ns_mu): chunks of outputs alternate between
-    // the two verifier streams, each with a buffer set of its own; the buffers grow on demand and are kept
-    struct NoteScanSet {
-        DevBuf<uint8_t> epk, raw, ct, pts, status, hit_keys;
-        DevBuf<uint32_t> count, hit_idx;
-    };
-    std::mutex ns_mu;
-    NoteScanSet ns[2];
-    DevBuf<uint32_t> ns_digits;
-    std::atomic<int> ns_signed_digits{1}, ns_inversion{0};   // masp_hip_note_scan_configure; the defaults are the measured winners (KERNELS.md)
-    double ns_last_ms[2] = {0, 0};                           // masp_hip_note_scan_last_timing (under slot_mu)
-    // the compact note scan (k_note_scan_compact.hip: masp_hip_sapling_compact_trial_decrypt) runs under ns_mu too, on the same two streams,
-    // and decodes the epks into ns[set].epk / pts / status; what it has beyond that: per set the cmus, the 84-byte rows, the candidate list
-    // of stage 1 and the per-candidate state of stage 2 (sized for the launch's pair count), the survivor lists and the final hits
-    struct NoteScanCompactSet {
-        DevBuf<uint8_t> cmu, enc, cand, state, hit_idx, hit_data;
-        DevBuf<uint32_t> count, list;
-    };
-    NoteScanCompactSet nsc[2];
-    DevBuf<uint8_t> nsc_ivks;         // the ivks as they come: stage 2's per-lane scalars
-    DevBuf<uint8_t> nsc_table;        // the Pedersen Niels table and G_ncr behind it, uploaded at the first compact scan or tree (pedersen_table.h)
-    double nsc_last_ms[3] = {0, 0, 0};   // masp_hip_note_scan_compact_last_timing: upload, stage 1, stage 2 (under slot_mu)
-    // the output recovery scan (k_out_recovery.hip: masp_hip_sapling_output_recovery_scan) runs under ns_mu too, on the same two streams;
-    // per set the rows as they come (cv, cmu, epk 32 bytes each, out_ciphertext 80), their eleven 16-byte columns, and the hits
-    struct OutRecoverySet {
-        DevBuf<uint8_t> cv, cmu, epk, cout, cols, hit_ocks;
-        DevBuf<uint32_t> count, hit_idx;
-    };
-    OutRecoverySet orc[2];
-    DevBuf<uint32_t> orc_ovks;           // the ovks, eight words each: the kernel's wave-uniform message words
-    double orc_last_ms[2] = {0, 0};      // masp_hip_out_recovery_last_timing: upload, kernels (under slot_mu)
-    // the commitment tree (k_merkle.hip: masp_hip_merkle_tree_complete) runs under ns_mu too, on the first verifier stream, and reads nsc_table:
-    // the node vector (eight words a node), the first bad input's index, the positions and their paths, empty_root(0..32)
-    DevBuf<uint32_t> mt_nodes, mt_bad, mt_paths, mt_empties;
-    DevBuf<uint64_t> mt_pos;
-    double mt_last_ms[3] = {0, 0, 0};    // masp_hip_merkle_last_timing: upload, kernels, download (under slot_mu)
-    // the note nullifiers (k_nullifier.hip: masp_hip_sapling_note_nullifiers) run under ns_mu too, on the first verifier stream, and read
-    // nsc_table beside a table of their own (nullifier_table.h: the windows of G_ncr and G_nf); a chunk's arrays as they come, the
-    // per-note state, and cmu | nf | status
-    DevBuf<uint8_t> nf_table, nf_in, nf_state, nf_out;
-    std::atomic<int> nf_lanes{0};        // masp_hip_note_nullifiers_configure: lanes per note, 0 = by the number of notes
-    double nf_last_ms[3] = {0, 0, 0};    // masp_hip_note_nullifiers_last_timing: upload, kernels, download (under slot_mu)
+    masp::WalletState wallet;   // the wallet-side calls' state, under a lock of its own
 };
 
 namespace masp {
@@ -489,6 +482,21 @@ static inline int fail(masp_hip_ctx* ctx, int rc) {
 
 // the context a single-device entry point works on: a multi-device front's first device context
 #define FIRST_DEVICE(ctx) ((ctx) && !(ctx)->children.empty() ? (ctx)->children[0] : (ctx))
+
+// The opening of every wallet-side entry point, in this order: the launch scope, the first device's context, its `mu` shared (concurrent
+// with provers and verifiers), the wallet lock, the device.  done(rc) is how such a call returns once it holds the locks.
+struct WalletCall {
+    const ApiLaunchScope scope;
+    masp_hip_ctx* const ctx;
+    std::shared_lock<std::shared_mutex> lock;
+    std::lock_guard<std::mutex> wlock;
+    WalletState& w;
+    explicit WalletCall(masp_hip_ctx* c) : ctx(FIRST_DEVICE(c)), lock(ctx->mu), wlock(ctx->wallet.mu), w(ctx->wallet) { hipSetDevice(ctx->device); }
+    int done(int rc) {
+        w.settle_tables(rc);
+        return rc ? fail(ctx, rc) : MASP_HIP_OK;
+    }
+};
 
 static inline int get_domain(masp_hip_ctx* ctx, uint32_t logm, NttDomain** out) {
     auto it = ctx->domains.find(logm);

@@ -150,39 +150,30 @@ size_t mt_append_count(uint64_t start, uint64_t n) {
     return total;
 }
 
-struct Events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Events() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-
-// everything of one tree on the context's first verifier stream; the caller holds ns_mu
+// everything of one tree on the context's first verifier stream; the caller is a WalletCall
 int run_tree(masp_hip_ctx* ctx, unsigned height0, size_t n, size_t total, const uint8_t* row, uint8_t* nodes_out, uint8_t root32[32],
-             size_t n_paths, const uint64_t* positions, uint8_t* paths_out, int64_t* bad_index, bool& first_upload) {
+             size_t n_paths, const uint64_t* positions, uint8_t* paths_out, int64_t* bad_index) {
+    WalletState& w = ctx->wallet;
     hipStream_t s = ctx->streams.vk[0];
     const uint32_t depth = MT_DEPTH - height0;
     const auto& empty = masp_host::merkle_empty_roots();
     int rc;
-    if ((rc = ctx->mt_nodes.reserve(8 * total)) || (rc = ctx->mt_bad.reserve(1)) || (rc = ctx->mt_pos.reserve(n_paths)) ||
-        (rc = ctx->mt_paths.reserve(8 * n_paths * depth)))
+    if ((rc = w.mt_nodes.reserve(8 * total)) || (rc = w.mt_bad.reserve(1)) || (rc = w.mt_pos.reserve(n_paths)) ||
+        (rc = w.mt_paths.reserve(8 * n_paths * depth)))
         return rc;
-    Events ev;
-    for (hipEvent_t& e : ev.e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(ev.e[0], s));
-    first_upload = !ctx->nsc_table.p || !ctx->mt_empties.p;
-    if ((rc = pedersen_table_ensure(ctx, s))) return rc;
-    if (!ctx->mt_empties.p && (rc = ctx->mt_empties.upload((const uint32_t*)empty[0].data(), 8 * (MT_DEPTH + 1), s))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->mt_nodes.p, row, 32 * n, hipMemcpyHostToDevice, s));
-    if (n_paths) HIP_TRY(hipMemcpyAsync(ctx->mt_pos.p, positions, 8 * n_paths, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(ctx->mt_bad.p, 0xff, sizeof(uint32_t), s));
-    HIP_TRY(hipEventRecord(ev.e[1], s));
-    uint32_t* nodes = ctx->mt_nodes.p;
-    const uint32_t *empties = ctx->mt_empties.p, *bad = ctx->mt_bad.p;
-    const JNiels* table = (const JNiels*)ctx->nsc_table.p;
+    Event ev[4];
+    if ((rc = create_events(ev))) return rc;
+    HIP_TRY(hipEventRecord(ev[0], s));
+    if ((rc = pedersen_table_ensure(w, s)) || (rc = w.mt_empties.ensure((const uint32_t*)empty[0].data(), 8 * (MT_DEPTH + 1), s))) return rc;
+    HIP_TRY(hipMemcpyAsync(w.mt_nodes.p, row, 32 * n, hipMemcpyHostToDevice, s));
+    if (n_paths) HIP_TRY(hipMemcpyAsync(w.mt_pos.p, positions, 8 * n_paths, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(w.mt_bad.p, 0xff, sizeof(uint32_t), s));
+    HIP_TRY(hipEventRecord(ev[1], s));
+    uint32_t* nodes = w.mt_nodes.p;
+    const uint32_t *empties = w.mt_empties.p, *bad = w.mt_bad.p;
+    const JNiels* table = (const JNiels*)w.nsc_table.p;
     MASP_LAUNCH(k_mt_check, dim3((uint32_t)((n + MT_BLOCK - 1) / MT_BLOCK)), dim3(MT_BLOCK), 0, s, (const uint32_t*)nodes, (uint32_t)n,
-                ctx->mt_bad.p);
+                w.mt_bad.p);
     uint64_t start = 0;
     uint32_t width = (uint32_t)n, level = height0;
     for (; level < MT_DEPTH && (width + 1) / 2 > MT_TOP_PARENTS; ++level) {
@@ -194,11 +185,11 @@ int run_tree(masp_hip_ctx* ctx, unsigned height0, size_t n, size_t total, const 
     if (level < MT_DEPTH) MASP_LAUNCH(k_mt_top, dim3(1), dim3(MT_TOP_PARENTS), 0, s, nodes, empties, table, bad, start, width, level);
     if (n_paths && depth)
         MASP_LAUNCH(k_mt_paths, dim3((uint32_t)((n_paths * depth + MT_BLOCK - 1) / MT_BLOCK)), dim3(MT_BLOCK), 0, s, (const uint32_t*)nodes, empties,
-                    bad, (uint32_t)n, height0, (const uint64_t*)ctx->mt_pos.p, (uint32_t)n_paths, ctx->mt_paths.p);
-    HIP_TRY(hipEventRecord(ev.e[2], s));
+                    bad, (uint32_t)n, height0, (const uint64_t*)w.mt_pos.p, (uint32_t)n_paths, w.mt_paths.p);
+    HIP_TRY(hipEventRecord(ev[2], s));
     uint32_t h_bad = MT_NO_BAD;
     uint8_t h_root[32];
-    HIP_TRY(hipMemcpyAsync(&h_bad, ctx->mt_bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&h_bad, w.mt_bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(h_root, nodes + 8 * (total - 1), 32, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (launch_status() != MASP_HIP_OK) return MASP_HIP_E_HIP;   // a refused launch: the buffers mean nothing
@@ -211,42 +202,37 @@ int run_tree(masp_hip_ctx* ctx, unsigned height0, size_t n, size_t total, const 
         return MASP_HIP_E_INVALID_ARG;   // nothing written
     }
     if (nodes_out) HIP_TRY(hipMemcpyAsync(nodes_out, nodes, 32 * total, hipMemcpyDeviceToHost, s));
-    if (n_paths && depth) HIP_TRY(hipMemcpyAsync(paths_out, ctx->mt_paths.p, 32 * n_paths * depth, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipEventRecord(ev.e[3], s));
+    if (n_paths && depth) HIP_TRY(hipMemcpyAsync(paths_out, w.mt_paths.p, 32 * n_paths * depth, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipEventRecord(ev[3], s));
     HIP_TRY(hipStreamSynchronize(s));
     memcpy(root32, h_root, 32);
-    float up = 0, k = 0, down = 0;
-    HIP_TRY(hipEventElapsedTime(&up, ev.e[0], ev.e[1]));
-    HIP_TRY(hipEventElapsedTime(&k, ev.e[1], ev.e[2]));
-    HIP_TRY(hipEventElapsedTime(&down, ev.e[2], ev.e[3]));
-    std::lock_guard<std::mutex> g(ctx->slot_mu);
-    ctx->mt_last_ms[0] = up;
-    ctx->mt_last_ms[1] = k;
-    ctx->mt_last_ms[2] = down;   // (with the wait for the kernels' end when the host was ahead of them: stream time)
+    double ms[3] = {0, 0, 0};   // (the download with the wait for the kernels' end when the host was ahead of them: stream time)
+    if ((rc = add_elapsed(ev, 3, ms))) return rc;
+    w.mt_timing.store(ms);
     return MASP_HIP_OK;
 }
 
-// a block of n >= 1 leaves at `start`, on the same stream and in the same scratch as run_tree; the caller holds ns_mu
+// a block of n >= 1 leaves at `start`, on the same stream and in the same scratch as run_tree; the caller is a WalletCall
 int run_append(masp_hip_ctx* ctx, uint64_t start, const uint8_t* frontier, size_t n, size_t total, const uint8_t* row, uint8_t* nodes_out,
-               int64_t* bad_index, bool& first_upload) {
+               int64_t* bad_index) {
+    WalletState& w = ctx->wallet;
     hipStream_t s = ctx->streams.vk[0];
     const uint64_t end = start + n;
     int rc;
-    if ((rc = ctx->mt_nodes.reserve(8 * (MT_APPEND_ROW + n + total))) || (rc = ctx->mt_bad.reserve(1))) return rc;
-    Events ev;
-    for (hipEvent_t& e : ev.e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipEventRecord(ev.e[0], s));
-    first_upload = !ctx->nsc_table.p;
-    if ((rc = pedersen_table_ensure(ctx, s))) return rc;
-    uint32_t* nodes = ctx->mt_nodes.p;
+    if ((rc = w.mt_nodes.reserve(8 * (MT_APPEND_ROW + n + total))) || (rc = w.mt_bad.reserve(1))) return rc;
+    Event ev[4];
+    if ((rc = create_events(ev))) return rc;
+    HIP_TRY(hipEventRecord(ev[0], s));
+    if ((rc = pedersen_table_ensure(w, s))) return rc;
+    uint32_t* nodes = w.mt_nodes.p;
     HIP_TRY(hipMemcpyAsync(nodes, frontier, 32 * MT_DEPTH, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(nodes + 8 * MT_APPEND_ROW, row, 32 * n, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(ctx->mt_bad.p, 0xff, sizeof(uint32_t), s));
-    HIP_TRY(hipEventRecord(ev.e[1], s));
-    const uint32_t* bad = ctx->mt_bad.p;
-    const JNiels* table = (const JNiels*)ctx->nsc_table.p;
+    HIP_TRY(hipMemsetAsync(w.mt_bad.p, 0xff, sizeof(uint32_t), s));
+    HIP_TRY(hipEventRecord(ev[1], s));
+    const uint32_t* bad = w.mt_bad.p;
+    const JNiels* table = (const JNiels*)w.nsc_table.p;
     MASP_LAUNCH(k_mt_check, dim3((uint32_t)((n + MT_BLOCK - 1) / MT_BLOCK)), dim3(MT_BLOCK), 0, s, (const uint32_t*)(nodes + 8 * MT_APPEND_ROW),
-                (uint32_t)n, ctx->mt_bad.p);
+                (uint32_t)n, w.mt_bad.p);
     uint64_t src = MT_APPEND_ROW;
     uint32_t level = 0;
     for (; level < MT_DEPTH; ++level) {
@@ -259,9 +245,9 @@ int run_append(masp_hip_ctx* ctx, uint64_t start, const uint8_t* frontier, size_
     }
     if (level < MT_DEPTH && (end >> (level + 1)) > (start >> (level + 1)))
         MASP_LAUNCH(k_mt_append_top, dim3(1), dim3(MT_TOP_PARENTS), 0, s, nodes, table, bad, start, end, src, level);
-    HIP_TRY(hipEventRecord(ev.e[2], s));
+    HIP_TRY(hipEventRecord(ev[2], s));
     uint32_t h_bad = MT_NO_BAD;
-    HIP_TRY(hipMemcpyAsync(&h_bad, ctx->mt_bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&h_bad, w.mt_bad.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (launch_status() != MASP_HIP_OK) return MASP_HIP_E_HIP;   // a refused launch: the buffers mean nothing
     if (h_bad != MT_NO_BAD) {
@@ -273,16 +259,11 @@ int run_append(masp_hip_ctx* ctx, uint64_t start, const uint8_t* frontier, size_
         return MASP_HIP_E_INVALID_ARG;   // nothing written
     }
     if (total) HIP_TRY(hipMemcpyAsync(nodes_out, nodes + 8 * (MT_APPEND_ROW + n), 32 * total, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipEventRecord(ev.e[3], s));
+    HIP_TRY(hipEventRecord(ev[3], s));
     HIP_TRY(hipStreamSynchronize(s));
-    float up = 0, k = 0, down = 0;
-    HIP_TRY(hipEventElapsedTime(&up, ev.e[0], ev.e[1]));
-    HIP_TRY(hipEventElapsedTime(&k, ev.e[1], ev.e[2]));
-    HIP_TRY(hipEventElapsedTime(&down, ev.e[2], ev.e[3]));
-    std::lock_guard<std::mutex> g(ctx->slot_mu);
-    ctx->mt_last_ms[0] = up;
-    ctx->mt_last_ms[1] = k;
-    ctx->mt_last_ms[2] = down;
+    double ms[3] = {0, 0, 0};
+    if ((rc = add_elapsed(ev, 3, ms))) return rc;
+    w.mt_timing.store(ms);
     return MASP_HIP_OK;
 }
 
@@ -312,21 +293,10 @@ int masp_hip_merkle_tree_complete(masp_hip_ctx* ctx, unsigned height0, size_t n,
         return MASP_HIP_OK;
     }
     (void)pedersen_table_bytes();   // built outside the locks
-    const ApiLaunchScope api_scope;
-    ctx = FIRST_DEVICE(ctx);
-    std::shared_lock<std::shared_mutex> lock(ctx->mu);   // concurrent with provers and verifiers
-    std::lock_guard<std::mutex> nlock(ctx->ns_mu);       // one scan or one tree at a time: they share the stream and the table
-    hipSetDevice(ctx->device);
-    bool first_upload = false;
-    const int rc = run_tree(ctx, height0, n, total, row, nodes_out, root32, n_paths, positions, paths_out, bad_index, first_upload);
-    if (rc == MASP_HIP_E_HIP) {
-        (void)hipStreamSynchronize(ctx->streams.vk[0]);   // nothing of this call stays in flight
-        if (first_upload) {                               // the table and the empty roots may not have arrived
-            ctx->nsc_table.release();
-            ctx->mt_empties.release();
-        }
-    }
-    return rc ? fail(ctx, rc) : MASP_HIP_OK;
+    WalletCall call(ctx);
+    const int rc = run_tree(call.ctx, height0, n, total, row, nodes_out, root32, n_paths, positions, paths_out, bad_index);
+    if (rc == MASP_HIP_E_HIP) (void)hipStreamSynchronize(call.ctx->streams.vk[0]);   // nothing of this call stays in flight
+    return call.done(rc);
 }
 
 int masp_hip_merkle_tree_append(masp_hip_ctx* ctx, uint64_t start, const uint8_t frontier[32 * 32], size_t n, const uint8_t* row,
@@ -350,25 +320,15 @@ int masp_hip_merkle_tree_append(masp_hip_ctx* ctx, uint64_t start, const uint8_t
         }
     }
     (void)pedersen_table_bytes();   // built outside the locks
-    const ApiLaunchScope api_scope;
-    ctx = FIRST_DEVICE(ctx);
-    std::shared_lock<std::shared_mutex> lock(ctx->mu);   // concurrent with provers and verifiers
-    std::lock_guard<std::mutex> nlock(ctx->ns_mu);       // one scan or one tree at a time: they share the stream and the table
-    hipSetDevice(ctx->device);
-    bool first_upload = false;
-    const int rc = run_append(ctx, start, frontier, n, total, row, nodes_out, bad_index, first_upload);
-    if (rc == MASP_HIP_E_HIP) {
-        (void)hipStreamSynchronize(ctx->streams.vk[0]);   // nothing of this call stays in flight
-        if (first_upload) ctx->nsc_table.release();       // the table may not have arrived
-    }
-    return rc ? fail(ctx, rc) : MASP_HIP_OK;
+    WalletCall call(ctx);
+    const int rc = run_append(call.ctx, start, frontier, n, total, row, nodes_out, bad_index);
+    if (rc == MASP_HIP_E_HIP) (void)hipStreamSynchronize(call.ctx->streams.vk[0]);   // nothing of this call stays in flight
+    return call.done(rc);
 }
 
 int masp_hip_merkle_last_timing(masp_hip_ctx* ctx, double ms[3]) {
     if (!ctx || !ms) return MASP_HIP_E_INVALID_ARG;
-    ctx = FIRST_DEVICE(ctx);
-    std::lock_guard<std::mutex> g(ctx->slot_mu);
-    for (int i = 0; i < 3; ++i) ms[i] = ctx->mt_last_ms[i];
+    FIRST_DEVICE(ctx)->wallet.mt_timing.load(ms);
     return MASP_HIP_OK;
 }
 

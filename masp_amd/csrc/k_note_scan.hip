@@ -132,7 +132,8 @@ void recode(uint32_t out[16], const uint32_t k_in[8], bool signed_digits) {
 // enqueues one chunk of outputs on its stream: upload, decode, repitch, trials, and the count's way back
 int enqueue_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, ScanSetHost<3>& h, size_t n_ivk, const uint8_t* epks, const uint8_t* encs,
                   uint32_t* h_count) {
-    masp_hip_ctx::NoteScanSet& b = ctx->ns[c.set];
+    WalletState& w = ctx->wallet;
+    WalletState::NoteScanSet& b = w.ns[c.set];
     hipStream_t s = ctx->streams.vk[c.set];
     const uint32_t n = (uint32_t)c.n, nb = (n + NS_BLOCK - 1) / NS_BLOCK, n_pad = nb * NS_BLOCK;
     const size_t cap = c.n * n_ivk;
@@ -141,7 +142,7 @@ int enqueue_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, ScanSetHost<3>& h, 
         (rc = b.pts.reserve(sizeof(JNiels) * (size_t)n_pad)) || (rc = b.status.reserve(n_pad)) || (rc = b.count.reserve(1)) ||
         (rc = b.hit_idx.reserve(2 * cap)) || (rc = b.hit_keys.reserve(32 * cap)))
         return rc;
-    if ((rc = h.create_events())) return rc;
+    if ((rc = create_events(h.ev))) return rc;
     HIP_TRY(hipEventRecord(h.ev[0], s));
     HIP_TRY(hipMemcpyAsync(b.epk.p, epks + 32 * c.o0, 32 * c.n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(b.raw.p, encs + NS_ENC * c.o0, NS_ENC * c.n, hipMemcpyHostToDevice, s));
@@ -149,8 +150,8 @@ int enqueue_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, ScanSetHost<3>& h, 
     HIP_TRY(hipEventRecord(h.ev[1], s));
     launch_ns_decode(s, b.epk.p, n, b.status.p, b.pts.p);
     MASP_LAUNCH(k_ns_repitch, dim3(nb, NS_COLS), dim3(NS_BLOCK), 0, s, (const uint32_t*)b.raw.p, n, n_pad, (uint4*)b.ct.p);
-    MASP_LAUNCH(k_ns_trial, dim3(nb, (uint32_t)n_ivk), dim3(NS_BLOCK), 0, s, (const uint32_t*)ctx->ns_digits.p, (const JNiels*)b.pts.p,
-                (const uint8_t*)b.status.p, (const uint4*)b.epk.p, (const uint4*)b.ct.p, n, n_pad, (uint32_t)c.o0, ctx->ns_inversion.load(),
+    MASP_LAUNCH(k_ns_trial, dim3(nb, (uint32_t)n_ivk), dim3(NS_BLOCK), 0, s, (const uint32_t*)w.ns_digits.p, (const JNiels*)b.pts.p,
+                (const uint8_t*)b.status.p, (const uint4*)b.epk.p, (const uint4*)b.ct.p, n, n_pad, (uint32_t)c.o0, w.ns_inversion.load(),
                 b.count.p, (uint32_t)cap, (uint2*)b.hit_idx.p, (uint4*)b.hit_keys.p);
     HIP_TRY(hipEventRecord(h.ev[2], s));
     HIP_TRY(hipMemcpyAsync(h_count, b.count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -188,21 +189,19 @@ int masp_hip_sapling_trial_decrypt(masp_hip_ctx* ctx, size_t n_ivk, const uint8_
         return MASP_HIP_E_INVALID_ARG;
     *n_hits = 0;
     std::vector<uint32_t> digits;
-    if (ns_recode_ivks(digits, n_ivk, ivks, FIRST_DEVICE(ctx)->ns_signed_digits.load() != 0)) return MASP_HIP_E_INVALID_ARG;
+    if (ns_recode_ivks(digits, n_ivk, ivks, FIRST_DEVICE(ctx)->wallet.ns_signed_digits.load() != 0)) return MASP_HIP_E_INVALID_ARG;
     if (n_ivk == 0 || n_out == 0) {
         if (epk_status && n_out) memset(epk_status, 0, n_out);   // (not looked at: no key asked for them)
         return MASP_HIP_OK;
     }
-    const ApiLaunchScope api_scope;
-    ctx = FIRST_DEVICE(ctx);
-    std::shared_lock<std::shared_mutex> lock(ctx->mu);   // concurrent with provers and verifiers
-    std::lock_guard<std::mutex> nlock(ctx->ns_mu);
-    hipSetDevice(ctx->device);
+    WalletCall call(ctx);
+    ctx = call.ctx;
+    WalletState& w = call.w;
     int rc;
-    if ((rc = ctx->ns_digits.upload(digits.data(), digits.size(), ctx->streams.vk[0]))) return fail(ctx, rc);
+    if ((rc = w.ns_digits.upload(digits.data(), digits.size(), ctx->streams.vk[0]))) return call.done(rc);
     if (hipStreamSynchronize(ctx->streams.vk[0]) != hipSuccess) {   // both streams read the digits
         last_hip_error() = std::string("note scan: upload failed: ") + hipGetErrorString(hipGetLastError());
-        return fail(ctx, MASP_HIP_E_HIP);
+        return call.done(MASP_HIP_E_HIP);
     }
     // chunks of outputs, alternately on the two verifier streams with a buffer set each (chunk_pipeline.h)
     ScanSetHost<3> host[2];   // events: before the upload, behind it, behind the kernels
@@ -213,35 +212,28 @@ int masp_hip_sapling_trial_decrypt(masp_hip_ctx* ctx, size_t n_ivk, const uint8_
         n_out, chunk_outputs(n_ivk),
         [&](const ChunkInFlight& c) { return enqueue_chunk(ctx, c, host[c.set], n_ivk, epks, enc_ciphertexts, &h_count[c.set]); },
         [&](const ChunkInFlight& c) {
-            const masp_hip_ctx::NoteScanSet& b = ctx->ns[c.set];
+            const WalletState::NoteScanSet& b = w.ns[c.set];
             return scan_collect(
                 ctx->streams.vk[c.set], c, host[c.set], [&](size_t& nh) { return (nh = h_count[c.set]) <= c.n * n_ivk; },
                 "note scan: hit count beyond the chunk's pairs", epk_status, b.status.p, b.hit_idx.p, b.hit_keys.p, hits, ms);
         },
         [&](int set) { (void)hipStreamSynchronize(ctx->streams.vk[set]); });
-    if (rc) return fail(ctx, rc);
-    {
-        std::lock_guard<std::mutex> g(ctx->slot_mu);
-        ctx->ns_last_ms[0] = ms[0];
-        ctx->ns_last_ms[1] = ms[1];
-    }
-    return scan_finish(hits, hit_capacity, hit_output, hit_ivk, hit_keys, 32, nullptr, n_hits);
+    if (rc) return call.done(rc);
+    w.ns_timing.store(ms);
+    return call.done(scan_finish(hits, hit_capacity, hit_output, hit_ivk, hit_keys, 32, nullptr, n_hits));
 }
 
 int masp_hip_note_scan_configure(masp_hip_ctx* ctx, int signed_digits, int inversion) {
     if (!ctx || signed_digits < 0 || signed_digits > 1 || inversion < 0 || inversion > 1) return MASP_HIP_E_INVALID_ARG;
-    ctx = FIRST_DEVICE(ctx);
-    ctx->ns_signed_digits.store(signed_digits);
-    ctx->ns_inversion.store(inversion);
+    WalletState& w = FIRST_DEVICE(ctx)->wallet;
+    w.ns_signed_digits.store(signed_digits);
+    w.ns_inversion.store(inversion);
     return MASP_HIP_OK;
 }
 
 int masp_hip_note_scan_last_timing(masp_hip_ctx* ctx, double ms[2]) {
     if (!ctx || !ms) return MASP_HIP_E_INVALID_ARG;
-    ctx = FIRST_DEVICE(ctx);
-    std::lock_guard<std::mutex> g(ctx->slot_mu);
-    ms[0] = ctx->ns_last_ms[0];
-    ms[1] = ctx->ns_last_ms[1];
+    FIRST_DEVICE(ctx)->wallet.ns_timing.load(ms);
     return MASP_HIP_OK;
 }
 

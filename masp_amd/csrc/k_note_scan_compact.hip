@@ -131,8 +131,9 @@ __global__ __launch_bounds__(NSC_BLOCK2) void k_nsc_emit(const NscArgs a, int fr
 // enqueues one chunk of outputs on its stream: upload, decode, stage 1, stage 2, and the counts' way back
 int enqueue_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, ScanSetHost<4>& h, size_t n_ivk, const uint8_t* epks, const uint8_t* cmus,
                   const uint8_t* encs, int lead, uint32_t* h_counts) {
-    masp_hip_ctx::NoteScanSet& b = ctx->ns[c.set];
-    masp_hip_ctx::NoteScanCompactSet& x = ctx->nsc[c.set];
+    WalletState& w = ctx->wallet;
+    WalletState::NoteScanSet& b = w.ns[c.set];
+    WalletState::NoteScanCompactSet& x = w.nsc[c.set];
     hipStream_t s = ctx->streams.vk[c.set];
     const uint32_t n = (uint32_t)c.n, nb = (n + NS_BLOCK - 1) / NS_BLOCK, n_pad = nb * NS_BLOCK;
     const size_t cap = c.n * n_ivk;
@@ -142,7 +143,7 @@ int enqueue_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, ScanSetHost<4>& h, 
         (rc = x.cand.reserve(sizeof(NscCand) * cap)) || (rc = x.state.reserve(sizeof(NscState) * cap)) || (rc = x.list.reserve(4 * cap)) ||
         (rc = x.hit_idx.reserve(8 * cap)) || (rc = x.hit_data.reserve(116 * cap)))
         return rc;
-    if ((rc = h.create_events())) return rc;
+    if ((rc = create_events(h.ev))) return rc;
     HIP_TRY(hipEventRecord(h.ev[0], s));
     HIP_TRY(hipMemcpyAsync(b.epk.p, epks + 32 * c.o0, 32 * c.n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(x.cmu.p, cmus + 32 * c.o0, 32 * c.n, hipMemcpyHostToDevice, s));
@@ -150,8 +151,8 @@ int enqueue_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, ScanSetHost<4>& h, 
     HIP_TRY(hipMemsetAsync(x.count.p, 0, 5 * sizeof(uint32_t), s));
     HIP_TRY(hipEventRecord(h.ev[1], s));
     launch_ns_decode(s, b.epk.p, n, b.status.p, b.pts.p);
-    MASP_LAUNCH(k_nsc_trial, dim3(nb, (uint32_t)n_ivk), dim3(NS_BLOCK), 0, s, (const uint32_t*)ctx->ns_digits.p, (const JNiels*)b.pts.p,
-                (const uint8_t*)b.status.p, (const uint4*)b.epk.p, (const uint32_t*)x.enc.p, n, ctx->ns_inversion.load(), (uint32_t)lead,
+    MASP_LAUNCH(k_nsc_trial, dim3(nb, (uint32_t)n_ivk), dim3(NS_BLOCK), 0, s, (const uint32_t*)w.ns_digits.p, (const JNiels*)b.pts.p,
+                (const uint8_t*)b.status.p, (const uint4*)b.epk.p, (const uint32_t*)x.enc.p, n, w.ns_inversion.load(), (uint32_t)lead,
                 x.count.p, (uint32_t)cap, (NscCand*)x.cand.p);
     HIP_TRY(hipEventRecord(h.ev[2], s));
     NscArgs a;
@@ -163,8 +164,8 @@ int enqueue_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, ScanSetHost<4>& h, 
     a.enc = (const uint32_t*)x.enc.p;
     a.epks = (const uint32_t*)b.epk.p;
     a.cmus = (const uint32_t*)x.cmu.p;
-    a.ivks = (const uint32_t*)ctx->nsc_ivks.p;
-    a.table = (const JNiels*)ctx->nsc_table.p;
+    a.ivks = (const uint32_t*)w.nsc_ivks.p;
+    a.table = (const JNiels*)w.nsc_table.p;
     a.lead = lead;
     const dim3 grid2((uint32_t)((cap + NSC_BLOCK2 - 1) / NSC_BLOCK2)), block2(NSC_BLOCK2);
     MASP_LAUNCH(k_nsc_parse, grid2, block2, 0, s, a);
@@ -191,26 +192,23 @@ int masp_hip_sapling_compact_trial_decrypt(masp_hip_ctx* ctx, size_t n_ivk, cons
     *n_hits = 0;
     if (n_candidates) *n_candidates = 0;
     std::vector<uint32_t> digits;
-    if (ns_recode_ivks(digits, n_ivk, ivks, FIRST_DEVICE(ctx)->ns_signed_digits.load() != 0)) return MASP_HIP_E_INVALID_ARG;
+    if (ns_recode_ivks(digits, n_ivk, ivks, FIRST_DEVICE(ctx)->wallet.ns_signed_digits.load() != 0)) return MASP_HIP_E_INVALID_ARG;
     if (n_ivk == 0 || n_out == 0) {
         if (epk_status && n_out) memset(epk_status, 0, n_out);   // (not looked at: no key asked for them)
         return MASP_HIP_OK;
     }
     (void)pedersen_table_bytes();   // built outside the locks
-    const ApiLaunchScope api_scope;
-    ctx = FIRST_DEVICE(ctx);
-    std::shared_lock<std::shared_mutex> lock(ctx->mu);   // concurrent with provers and verifiers
-    std::lock_guard<std::mutex> nlock(ctx->ns_mu);       // one note scan, full or compact, at a time: they share the streams and buffers
-    hipSetDevice(ctx->device);
+    WalletCall call(ctx);
+    ctx = call.ctx;
+    WalletState& w = call.w;
     int rc;
-    if ((rc = ctx->ns_digits.upload(digits.data(), digits.size(), ctx->streams.vk[0])) ||
-        (rc = ctx->nsc_ivks.upload(ivks, 32 * n_ivk, ctx->streams.vk[0])))
-        return fail(ctx, rc);
-    if ((rc = pedersen_table_ensure(ctx, ctx->streams.vk[0]))) return fail(ctx, rc);   // (shared with the commitment tree)
+    if ((rc = w.ns_digits.upload(digits.data(), digits.size(), ctx->streams.vk[0])) ||
+        (rc = w.nsc_ivks.upload(ivks, 32 * n_ivk, ctx->streams.vk[0])) ||
+        (rc = pedersen_table_ensure(w, ctx->streams.vk[0])))   // (shared with the trees and the nullifiers)
+        return call.done(rc);
     if (hipStreamSynchronize(ctx->streams.vk[0]) != hipSuccess) {   // both streams read the digits, the ivks and the table
         last_hip_error() = std::string("compact note scan: upload failed: ") + hipGetErrorString(hipGetLastError());
-        ctx->nsc_table.release();
-        return fail(ctx, MASP_HIP_E_HIP);
+        return call.done(MASP_HIP_E_HIP);
     }
     // chunks of outputs, alternately on the two verifier streams with a buffer set each (chunk_pipeline.h): a chunk's upload and stage 1
     // run beside the thin stage 2 of the chunk before
@@ -223,7 +221,7 @@ int masp_hip_sapling_compact_trial_decrypt(masp_hip_ctx* ctx, size_t n_ivk, cons
         n_out, chunk_outputs(n_ivk),
         [&](const ChunkInFlight& c) { return enqueue_chunk(ctx, c, host[c.set], n_ivk, epks, cmus, enc_compact, lead_byte, h_counts[c.set]); },
         [&](const ChunkInFlight& c) {
-            const masp_hip_ctx::NoteScanCompactSet& x = ctx->nsc[c.set];
+            const WalletState::NoteScanCompactSet& x = w.nsc[c.set];
             auto count = [&](size_t& nh) {   // the candidates of stage 1, of them the survivors of stage 2
                 const size_t nc = h_counts[c.set][0];
                 nh = h_counts[c.set][lead_byte == 2 ? 4 : 3];
@@ -232,23 +230,18 @@ int masp_hip_sapling_compact_trial_decrypt(masp_hip_ctx* ctx, size_t n_ivk, cons
                 return true;
             };
             return scan_collect(ctx->streams.vk[c.set], c, host[c.set], count, "compact note scan: a count beyond the chunk's pairs", epk_status,
-                                ctx->ns[c.set].status.p, x.hit_idx.p, x.hit_data.p, hits, ms);
+                                w.ns[c.set].status.p, x.hit_idx.p, x.hit_data.p, hits, ms);
         },
         [&](int set) { (void)hipStreamSynchronize(ctx->streams.vk[set]); });
-    if (rc) return fail(ctx, rc);
-    {
-        std::lock_guard<std::mutex> g(ctx->slot_mu);
-        for (int i = 0; i < 3; ++i) ctx->nsc_last_ms[i] = ms[i];
-    }
+    if (rc) return call.done(rc);
+    w.nsc_timing.store(ms);
     if (n_candidates) *n_candidates = candidates;
-    return scan_finish(hits, hit_capacity, hit_output, hit_ivk, hit_plaintexts, 84, hit_pk_d, n_hits);
+    return call.done(scan_finish(hits, hit_capacity, hit_output, hit_ivk, hit_plaintexts, 84, hit_pk_d, n_hits));
 }
 
 int masp_hip_note_scan_compact_last_timing(masp_hip_ctx* ctx, double ms[3]) {
     if (!ctx || !ms) return MASP_HIP_E_INVALID_ARG;
-    ctx = FIRST_DEVICE(ctx);
-    std::lock_guard<std::mutex> g(ctx->slot_mu);
-    for (int i = 0; i < 3; ++i) ms[i] = ctx->nsc_last_ms[i];
+    FIRST_DEVICE(ctx)->wallet.nsc_timing.load(ms);
     return MASP_HIP_OK;
 }
 

@@ -128,51 +128,42 @@ namespace {
 constexpr size_t NF_MAX_NOTES = (size_t)1 << 22;
 constexpr size_t NF_CHUNK = (size_t)1 << 19;   // notes per launch sequence: 272 bytes of state, 156 in and 65 out a note, 250 MB in all
 
-struct Events {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Events() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-};
-
 struct NfHost {
     const uint8_t *ids, *divs, *pk_ds, *leads, *rseeds, *nks;
     const uint64_t *values, *positions;
     uint8_t *status, *cmus, *nfs;
 };
 
-// everything of one call on the context's first verifier stream, chunk after chunk; the caller holds ns_mu
-int run_nullifiers(masp_hip_ctx* ctx, size_t n, const NfHost& h, bool first_upload[2]) {
+// everything of one call on the context's first verifier stream, chunk after chunk; the caller is a WalletCall
+int run_nullifiers(masp_hip_ctx* ctx, size_t n, const NfHost& h) {
+    WalletState& w = ctx->wallet;
     hipStream_t s = ctx->streams.vk[0];
     const size_t cap = std::min(NF_CHUNK, (n + 63) / 64 * 64);   // every array of the input buffer starts on a multiple of 8 bytes
     int rc;
-    if ((rc = ctx->nf_in.reserve(156 * cap)) || (rc = ctx->nf_state.reserve(sizeof(NfState) * cap)) || (rc = ctx->nf_out.reserve(65 * cap)))
+    if ((rc = w.nf_in.reserve(156 * cap)) || (rc = w.nf_state.reserve(sizeof(NfState) * cap)) || (rc = w.nf_out.reserve(65 * cap)))
         return rc;
-    first_upload[0] = !ctx->nsc_table.p;
-    first_upload[1] = !ctx->nf_table.p;
-    if ((rc = pedersen_table_ensure(ctx, s)) || (rc = nullifier_table_ensure(ctx, s))) return rc;
-    uint8_t* in = ctx->nf_in.p;
+    if ((rc = pedersen_table_ensure(w, s)) || (rc = nullifier_table_ensure(w, s))) return rc;
+    uint8_t* in = w.nf_in.p;
     uint8_t *d_ids = in, *d_pk = in + 32 * cap, *d_rs = in + 64 * cap, *d_nk = in + 96 * cap, *d_val = in + 128 * cap, *d_pos = in + 136 * cap,
             *d_div = in + 144 * cap, *d_lead = in + 155 * cap;
-    uint8_t *d_cmu = ctx->nf_out.p, *d_nf = d_cmu + 32 * cap, *d_status = d_cmu + 64 * cap;
+    uint8_t *d_cmu = w.nf_out.p, *d_nf = d_cmu + 32 * cap, *d_status = d_cmu + 64 * cap;
     NfArgs a;
     a.in = {(const uint32_t*)d_ids, (const uint64_t*)d_val, d_div, (const uint32_t*)d_pk, d_lead, (const uint32_t*)d_rs, (const uint32_t*)d_nk,
             (const uint64_t*)d_pos};
-    a.state = (NfState*)ctx->nf_state.p;
-    a.ped = (const JNiels*)ctx->nsc_table.p;
-    a.tab = (const JNiels*)ctx->nf_table.p;
+    a.state = (NfState*)w.nf_state.p;
+    a.ped = (const JNiels*)w.nsc_table.p;
+    a.tab = (const JNiels*)w.nf_table.p;
     a.status = d_status;
     a.cmus = (uint32_t*)d_cmu;
     a.nfs = (uint32_t*)d_nf;
-    const int forced = ctx->nf_lanes.load();
+    const int forced = w.nf_lanes.load();
     const int lanes = forced ? forced : n < NF_WIDE_BELOW ? 8 : 1;
-    Events ev;
-    for (hipEvent_t& e : ev.e) HIP_TRY(hipEventCreate(&e));
+    Event ev[4];
+    if ((rc = create_events(ev))) return rc;
     double ms[3] = {0, 0, 0};
     for (size_t o = 0; o < n; o += cap) {
         const size_t c = std::min(cap, n - o);
-        HIP_TRY(hipEventRecord(ev.e[0], s));
+        HIP_TRY(hipEventRecord(ev[0], s));
         HIP_TRY(hipMemcpyAsync(d_ids, h.ids + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(d_pk, h.pk_ds + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(d_rs, h.rseeds + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
@@ -182,24 +173,19 @@ int run_nullifiers(masp_hip_ctx* ctx, size_t n, const NfHost& h, bool first_uplo
         HIP_TRY(hipMemcpyAsync(d_div, h.divs + 11 * o, 11 * c, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(d_lead, h.leads + o, c, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemsetAsync(d_cmu, 0, 64 * cap, s));   // a refused note's outputs are zeros
-        HIP_TRY(hipEventRecord(ev.e[1], s));
+        HIP_TRY(hipEventRecord(ev[1], s));
         a.n = (uint32_t)c;
         nf_enqueue(s, a, lanes);
-        HIP_TRY(hipEventRecord(ev.e[2], s));
+        HIP_TRY(hipEventRecord(ev[2], s));
         HIP_TRY(hipMemcpyAsync(h.status + o, d_status, c, hipMemcpyDeviceToHost, s));
         if (h.cmus) HIP_TRY(hipMemcpyAsync(h.cmus + 32 * o, d_cmu, 32 * c, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(h.nfs + 32 * o, d_nf, 32 * c, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipEventRecord(ev.e[3], s));
+        HIP_TRY(hipEventRecord(ev[3], s));
         HIP_TRY(hipStreamSynchronize(s));   // the next chunk overwrites the buffers
         if (launch_status() != MASP_HIP_OK) return MASP_HIP_E_HIP;   // a refused launch: the buffers mean nothing
-        for (int k = 0; k < 3; ++k) {
-            float t = 0;
-            HIP_TRY(hipEventElapsedTime(&t, ev.e[k], ev.e[k + 1]));
-            ms[k] += t;
-        }
+        if ((rc = add_elapsed(ev, 3, ms))) return rc;
     }
-    std::lock_guard<std::mutex> g(ctx->slot_mu);
-    for (int k = 0; k < 3; ++k) ctx->nf_last_ms[k] = ms[k];
+    w.nf_timing.store(ms);
     return MASP_HIP_OK;
 }
 
@@ -216,33 +202,22 @@ int masp_hip_sapling_note_nullifiers(masp_hip_ctx* ctx, size_t n, const uint8_t*
         return MASP_HIP_E_INVALID_ARG;
     (void)pedersen_table_bytes();   // built outside the locks
     (void)nullifier_table();
-    const ApiLaunchScope api_scope;
-    ctx = FIRST_DEVICE(ctx);
-    std::shared_lock<std::shared_mutex> lock(ctx->mu);   // concurrent with provers and verifiers
-    std::lock_guard<std::mutex> nlock(ctx->ns_mu);       // one scan, one tree or one of these at a time: they share the stream and the table
-    hipSetDevice(ctx->device);
+    WalletCall call(ctx);
     const NfHost h = {asset_identifiers, diversifiers, pk_ds, lead_bytes, rseeds, nks, values, positions, status, cmus_out, nfs_out};
-    bool first_upload[2] = {false, false};
-    const int rc = run_nullifiers(ctx, n, h, first_upload);
-    if (rc == MASP_HIP_E_HIP) {
-        (void)hipStreamSynchronize(ctx->streams.vk[0]);     // nothing of this call stays in flight
-        if (first_upload[0]) ctx->nsc_table.release();      // a table this call uploaded may not have arrived
-        if (first_upload[1]) ctx->nf_table.release();
-    }
-    return rc ? fail(ctx, rc) : MASP_HIP_OK;
+    const int rc = run_nullifiers(call.ctx, n, h);
+    if (rc == MASP_HIP_E_HIP) (void)hipStreamSynchronize(call.ctx->streams.vk[0]);   // nothing of this call stays in flight
+    return call.done(rc);
 }
 
 int masp_hip_note_nullifiers_configure(masp_hip_ctx* ctx, int lanes_per_note) {
     if (!ctx || (lanes_per_note != 0 && lanes_per_note != 1 && lanes_per_note != 8)) return MASP_HIP_E_INVALID_ARG;
-    FIRST_DEVICE(ctx)->nf_lanes.store(lanes_per_note);
+    FIRST_DEVICE(ctx)->wallet.nf_lanes.store(lanes_per_note);
     return MASP_HIP_OK;
 }
 
 int masp_hip_note_nullifiers_last_timing(masp_hip_ctx* ctx, double ms[3]) {
     if (!ctx || !ms) return MASP_HIP_E_INVALID_ARG;
-    ctx = FIRST_DEVICE(ctx);
-    std::lock_guard<std::mutex> g(ctx->slot_mu);
-    for (int i = 0; i < 3; ++i) ms[i] = ctx->nf_last_ms[i];
+    FIRST_DEVICE(ctx)->wallet.nf_timing.load(ms);
     return MASP_HIP_OK;
 }
 

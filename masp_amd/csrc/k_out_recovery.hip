@@ -62,7 +62,8 @@ struct Rows {
 
 // enqueues one chunk of outputs on its stream: upload, repitch, trials, and the count's way back
 int enqueue_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, ScanSetHost<3>& h, size_t n_ovk, const Rows& r, uint32_t* h_count) {
-    masp_hip_ctx::OutRecoverySet& b = ctx->orc[c.set];
+    WalletState& w = ctx->wallet;
+    WalletState::OutRecoverySet& b = w.orc[c.set];
     hipStream_t s = ctx->streams.vk[c.set];
     const uint32_t n = (uint32_t)c.n, nb = (n + NS_BLOCK - 1) / NS_BLOCK, n_pad = nb * NS_BLOCK;
     const size_t cap = c.n * n_ovk;
@@ -71,7 +72,7 @@ int enqueue_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, ScanSetHost<3>& h, 
         (rc = b.cout.reserve(OR_OUT * (size_t)n_pad)) || (rc = b.cols.reserve(16 * (size_t)OR_COLS * n_pad)) || (rc = b.count.reserve(1)) ||
         (rc = b.hit_idx.reserve(2 * cap)) || (rc = b.hit_ocks.reserve(32 * cap)))
         return rc;
-    if ((rc = h.create_events())) return rc;
+    if ((rc = create_events(h.ev))) return rc;
     HIP_TRY(hipEventRecord(h.ev[0], s));
     HIP_TRY(hipMemcpyAsync(b.cv.p, r.cvs + 32 * c.o0, 32 * c.n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(b.cmu.p, r.cmus + 32 * c.o0, 32 * c.n, hipMemcpyHostToDevice, s));
@@ -81,7 +82,7 @@ int enqueue_chunk(masp_hip_ctx* ctx, const ChunkInFlight& c, ScanSetHost<3>& h, 
     HIP_TRY(hipEventRecord(h.ev[1], s));
     MASP_LAUNCH(k_or_repitch, dim3(nb, OR_COLS), dim3(NS_BLOCK), 0, s, (const uint4*)b.cv.p, (const uint4*)b.cmu.p, (const uint4*)b.epk.p,
                 (const uint4*)b.cout.p, n, n_pad, (uint4*)b.cols.p);
-    MASP_LAUNCH(k_or_trial, dim3(nb, (uint32_t)n_ovk), dim3(NS_BLOCK), 0, s, (const uint32_t*)ctx->orc_ovks.p, (const uint4*)b.cols.p, n, n_pad,
+    MASP_LAUNCH(k_or_trial, dim3(nb, (uint32_t)n_ovk), dim3(NS_BLOCK), 0, s, (const uint32_t*)w.orc_ovks.p, (const uint4*)b.cols.p, n, n_pad,
                 (uint32_t)c.o0, b.count.p, (uint32_t)cap, (uint2*)b.hit_idx.p, (uint4*)b.hit_ocks.p);
     HIP_TRY(hipEventRecord(h.ev[2], s));
     HIP_TRY(hipMemcpyAsync(h_count, b.count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -102,16 +103,14 @@ int masp_hip_sapling_output_recovery_scan(masp_hip_ctx* ctx, size_t n_ovk, const
     if (n_ovk == 0 || n_out == 0) return MASP_HIP_OK;   // (an ovk is any 32 bytes: nothing to refuse)
     std::vector<uint32_t> words(8 * n_ovk);
     memcpy(words.data(), ovks, 32 * n_ovk);   // (little-endian host)
-    const ApiLaunchScope api_scope;
-    ctx = FIRST_DEVICE(ctx);
-    std::shared_lock<std::shared_mutex> lock(ctx->mu);   // concurrent with provers and verifiers
-    std::lock_guard<std::mutex> nlock(ctx->ns_mu);       // one scan of any kind at a time: they share the streams
-    hipSetDevice(ctx->device);
+    WalletCall call(ctx);
+    ctx = call.ctx;
+    WalletState& w = call.w;
     int rc;
-    if ((rc = ctx->orc_ovks.upload(words.data(), words.size(), ctx->streams.vk[0]))) return fail(ctx, rc);
+    if ((rc = w.orc_ovks.upload(words.data(), words.size(), ctx->streams.vk[0]))) return call.done(rc);
     if (hipStreamSynchronize(ctx->streams.vk[0]) != hipSuccess) {   // both streams read the ovks
         last_hip_error() = std::string("output recovery scan: upload failed: ") + hipGetErrorString(hipGetLastError());
-        return fail(ctx, MASP_HIP_E_HIP);
+        return call.done(MASP_HIP_E_HIP);
     }
     // chunks of outputs, alternately on the two verifier streams with a buffer set each (chunk_pipeline.h)
     const Rows rows = {cvs, epks, cmus, out_ciphertexts};
@@ -123,27 +122,20 @@ int masp_hip_sapling_output_recovery_scan(masp_hip_ctx* ctx, size_t n_ovk, const
         n_out, chunk_outputs(n_ovk),
         [&](const ChunkInFlight& c) { return enqueue_chunk(ctx, c, host[c.set], n_ovk, rows, &h_count[c.set]); },
         [&](const ChunkInFlight& c) {
-            const masp_hip_ctx::OutRecoverySet& b = ctx->orc[c.set];
+            const WalletState::OutRecoverySet& b = w.orc[c.set];
             return scan_collect(
                 ctx->streams.vk[c.set], c, host[c.set], [&](size_t& nh) { return (nh = h_count[c.set]) <= c.n * n_ovk; },
                 "output recovery scan: hit count beyond the chunk's pairs", nullptr, nullptr, b.hit_idx.p, b.hit_ocks.p, hits, ms);
         },
         [&](int set) { (void)hipStreamSynchronize(ctx->streams.vk[set]); });
-    if (rc) return fail(ctx, rc);
-    {
-        std::lock_guard<std::mutex> g(ctx->slot_mu);
-        ctx->orc_last_ms[0] = ms[0];
-        ctx->orc_last_ms[1] = ms[1];
-    }
-    return scan_finish(hits, hit_capacity, hit_output, hit_ovk, hit_ocks, 32, nullptr, n_hits);
+    if (rc) return call.done(rc);
+    w.orc_timing.store(ms);
+    return call.done(scan_finish(hits, hit_capacity, hit_output, hit_ovk, hit_ocks, 32, nullptr, n_hits));
 }
 
 int masp_hip_out_recovery_last_timing(masp_hip_ctx* ctx, double ms[2]) {
     if (!ctx || !ms) return MASP_HIP_E_INVALID_ARG;
-    ctx = FIRST_DEVICE(ctx);
-    std::lock_guard<std::mutex> g(ctx->slot_mu);
-    ms[0] = ctx->orc_last_ms[0];
-    ms[1] = ctx->orc_last_ms[1];
+    FIRST_DEVICE(ctx)->wallet.orc_timing.load(ms);
     return MASP_HIP_OK;
 }
 

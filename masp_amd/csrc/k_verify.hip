@@ -39,7 +39,7 @@ struct masp_hip_vk {
     DevBuf<uint8_t> d_inputs, d_pre, d_verdict;
     DevBuf<G1Affine> d_pp;
     DevBuf<G2Affine> d_qp;
-    hipEvent_t each_ev[6] = {};    // around the stages of a chunk (masp_hip_verify_each_last_timing); created with the tables, destroyed with the key
+    Event each_ev[6];              // around the stages of a chunk (masp_hip_verify_each_last_timing); created with the tables
     double each_ms[5] = {0, 0, 0, 0, 0};
     hipStream_t stream = nullptr;  // verification runs next to the provers' batches, on one of the context's two verifier streams (not owned:
                                    // masp_hip_ctx::streams — created and kept off the batch streams' hardware queues with the context)
@@ -71,8 +71,7 @@ int prepare_each(masp_hip_ctx* ctx, masp_hip_vk* vk) {
     if ((rc = vk->fe_prog.upload(progs, 6, s))) return rc;
     HIP_TRY(hipStreamSynchronize(s));  // the host arrays above go out of scope
     vk->fe = {vk->fe_prog.p, vk->fe_sched.p, (uint32_t)ft.sched.size(), ft.n_slots, vk->fe_consts.p};
-    for (hipEvent_t& e : vk->each_ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
+    if ((rc = create_events(vk->each_ev))) return rc;
     vk->each_lds_ok = hipFuncSetAttribute((const void*)k_final_exp, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;
     vk->each_ready = true;
     return MASP_HIP_OK;
@@ -122,8 +121,6 @@ int masp_hip_vk_prepare(masp_hip_ctx* ctx, const uint8_t* params, size_t params_
 void masp_hip_vk_free(masp_hip_vk* vk) {
     if (!vk) return;
     hipSetDevice(vk->device);
-    for (hipEvent_t e : vk->each_ev)
-        if (e) (void)hipEventDestroy(e);
     delete vk;
 }
 
@@ -212,7 +209,7 @@ int masp_hip_verify_each(masp_hip_ctx* ctx, masp_hip_vk* vk, size_t n, const uin
     for (size_t lo = 0; lo < n; lo += EACH_CHUNK) {
         const size_t m = std::min(EACH_CHUNK, n - lo);
         const uint32_t mm = (uint32_t)m;
-        hipEvent_t* ev = vk->each_ev;
+        const Event* ev = vk->each_ev;
         HIP_TRY(hipEventRecord(ev[0], s));
         if ((rc = vk->d_proofs.upload(proofs + 192 * lo, 192 * m, s)) ||
             (rc = vk->d_inputs.upload(n_public ? public_inputs + 32 * (size_t)n_public * lo : nullptr, 32 * (size_t)n_public * m, s)) ||
@@ -235,10 +232,7 @@ int masp_hip_verify_each(masp_hip_ctx* ctx, masp_hip_vk* vk, size_t n, const uin
             return fail(ctx, MASP_HIP_E_HIP);
         }
         if (launch_status() != MASP_HIP_OK) return fail(ctx, MASP_HIP_E_HIP);  // a refused launch: the bytes read back mean nothing
-        for (int k = 0; k < 5; ++k) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) vk->each_ms[k] += ms;
-        }
+        (void)add_elapsed(ev, 5, vk->each_ms);
     }
     return MASP_HIP_OK;
 }

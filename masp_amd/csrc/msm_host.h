@@ -259,12 +259,12 @@ struct MsmWorkspace {
     // ... and those with more entries than the tree's views were cut for: counted on the device (k_tree_plan), mirrored into page-locked
     // memory behind every MSM — read it once the stream has been synchronised
     uint32_t* d_tree_over = nullptr;
-    uint32_t* h_tree_over = nullptr;
-    uint64_t tree_over() const { return h_tree_over ? *(volatile const uint32_t*)h_tree_over : 0; }
+    PinnedBuf<uint32_t> h_tree_over;
+    uint64_t tree_over() const { return h_tree_over.p ? *(volatile const uint32_t*)h_tree_over.p : 0; }
     int reserve_tree_over(hipStream_t s) {
         if (d_tree_over) return MASP_HIP_OK;
-        HIP_TRY(hipHostMalloc((void**)&h_tree_over, sizeof(uint32_t), hipHostMallocDefault));
-        *h_tree_over = 0;
+        if (int rc = h_tree_over.reserve(1)) return rc;
+        *h_tree_over.p = 0;
         HIP_TRY(dev_malloc(&d_tree_over, sizeof(uint32_t)));
         HIP_TRY(hipMemsetAsync(d_tree_over, 0, sizeof(uint32_t), s));
         return MASP_HIP_OK;
@@ -279,7 +279,6 @@ struct MsmWorkspace {
     ~MsmWorkspace() {
         release();
         if (d_tree_over) dev_free(d_tree_over);
-        if (h_tree_over) (void)hipHostFree(h_tree_over);
     }
     void release() {
         void* ptrs[] = {heavy, n_heavy, part, bkt, S[0], S[1], T, R[0], R[1], tsum, startT, hparts};

@@ -344,7 +344,7 @@ int msm_reduce_enqueue(hipStream_t s, const MsmBases<O, BYTES>& B, const MsmSort
             if (prof) prof->mark(s, MsmProfile::PH_ACC);
             p0 += q;
         }
-        if (bounded) HIP_TRY(hipMemcpyAsync(ws.h_tree_over, ws.d_tree_over, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        if (bounded) HIP_TRY(hipMemcpyAsync(ws.h_tree_over.p, ws.d_tree_over, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         ws.tree.prof = nullptr;
         start = ws.startT;
     } else {

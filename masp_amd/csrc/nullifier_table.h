@@ -1,6 +1,6 @@
 // The fixed-base tables of the note nullifiers (k_nullifier.hip, device/nullifier.hpp): the Niels points k 16^w G for k = 1..15 of
 // G_ncr (63 windows) and, behind them, of G_nf (16 windows), in the device's Montgomery limbs: 1 185 points, 111 KiB.  Built once per
-// process on the host from masp_host::generators(), uploaded once per context into a buffer of its own (under ns_mu): the Pedersen table
+// process on the host from masp_host::generators(), uploaded once per context into a buffer of its own (under WalletState::mu): the Pedersen table
 // of pedersen_table.h, which the compact scan and the trees read, stays what it is.
 #pragma once
 #include "device/nullifier.hpp"
@@ -29,12 +29,10 @@ inline const std::vector<JNiels>& nullifier_table() {
     return t;
 }
 
-// enqueues the table's upload on `s` if the context does not hold it yet (under ns_mu); the caller synchronises `s` before it relies on
-// the table, and releases ctx->nf_table if that fails
-inline int nullifier_table_ensure(masp_hip_ctx* ctx, hipStream_t s) {
-    if (ctx->nf_table.p) return MASP_HIP_OK;
+// enqueues the table's upload on `s` if the context does not hold it yet, as pedersen_table_ensure does
+inline int nullifier_table_ensure(WalletState& w, hipStream_t s) {
     const std::vector<JNiels>& t = nullifier_table();
-    return ctx->nf_table.upload((const uint8_t*)t.data(), sizeof(JNiels) * t.size(), s);
+    return w.nf_table.ensure((const uint8_t*)t.data(), sizeof(JNiels) * t.size(), s);
 }
 
 }  // namespace masp

@@ -1,6 +1,6 @@
 // The Pedersen Niels table of a device context, shared by the compact note scan (k_note_scan_compact.hip: the NoteCommitment hash over all five
 // segments) and the commitment tree (k_merkle.hip: the Merkle hash over the head of the first three): built once per process on the host from
-// masp_host::pedersen_windows(), uploaded once per context by whichever of the two runs first (both hold ns_mu).
+// masp_host::pedersen_windows(), uploaded once per context by whichever of them runs first (under WalletState::mu).
 #pragma once
 #include "device/pedersen.hpp"
 #include "host/jubjub.h"
@@ -40,12 +40,11 @@ inline const std::vector<uint8_t>& pedersen_table_bytes() {
     return t;
 }
 
-// enqueues the table's upload on `s` if the context does not hold it yet (under ns_mu); the caller synchronises `s` before anything reads the
-// table, and releases ctx->nsc_table if that fails
-inline int pedersen_table_ensure(masp_hip_ctx* ctx, hipStream_t s) {
-    if (ctx->nsc_table.p) return MASP_HIP_OK;
+// enqueues the table's upload on `s` if the context does not hold it yet; the caller synchronises `s` before anything reads the table, and
+// WalletCall::done releases it if the call fails before that is known
+inline int pedersen_table_ensure(WalletState& w, hipStream_t s) {
     const std::vector<uint8_t>& t = pedersen_table_bytes();
-    return ctx->nsc_table.upload(t.data(), t.size(), s);
+    return w.nsc_table.ensure(t.data(), t.size(), s);
 }
 
 }  // namespace masp

@@ -450,10 +450,10 @@ static int stage_group(GroupRun& G) {
     const Circuit& C = G.C;
     const size_t np = G.np, nv = G.nv, in_row = 32 * (size_t)C.n_inputs, abc_row = 32 * (size_t)C.nrows;
     int rc;
-    if ((rc = sl.stage_reserve(G.stage_bytes)) || (rc = sl.w.reserve(nv * np)) || (rc = sl.inp.reserve((size_t)C.n_inputs * np)) ||
+    if ((rc = sl.h_stage.reserve(G.stage_bytes)) || (rc = sl.w.reserve(nv * np)) || (rc = sl.inp.reserve((size_t)C.n_inputs * np)) ||
         (rc = sl.abc.reserve(G.has_abc ? 3 * (size_t)C.nrows * np : 1)) || (rc = sl.reserve_batch(np)))
         return rc;
-    uint8_t* hs = sl.h_stage;
+    uint8_t* hs = sl.h_stage.p;
     G.direct.assign(np, 0);
     for (size_t p = 0; p < np; ++p) {
         const masp_hip_job& J = G.jobs[G.idx[p]];
@@ -479,7 +479,7 @@ static int upload_group(GroupRun& G) {
     Slot& sl = G.sl;
     const Circuit& C = G.C;
     const size_t np = G.np, nv = G.nv, in_row = 32 * (size_t)C.n_inputs;
-    const uint8_t* hs = sl.h_stage;
+    const uint8_t* hs = sl.h_stage.p;
     hipStream_t s = sl.stream;
     bool ok = true;
     // (see masp_hip_ctx::upload_tail; the lock covers wait + enqueue + record so that the chain has one order.)  Not with
@@ -531,8 +531,8 @@ static int enqueue_group(GroupRun& G) {
 static int download_group(GroupRun& G) {
     Slot& sl = G.sl;
     hipStream_t s = sl.stream;
-    if (hipMemcpyAsync(sl.h_proof, sl.proof.p, 192 * G.np, hipMemcpyDeviceToHost, s) == hipSuccess &&
-        hipMemcpyAsync(sl.h_flags, sl.flags.p, sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess && hipEventRecord(sl.done, s) == hipSuccess)
+    if (hipMemcpyAsync(sl.h_proof.p, sl.proof.p, 192 * G.np, hipMemcpyDeviceToHost, s) == hipSuccess &&
+        hipMemcpyAsync(sl.h_flags.p, sl.flags.p, sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess && hipEventRecord(sl.done, s) == hipSuccess)
         return MASP_HIP_OK;
     last_hip_error() = "D2H copy failed";
     return MASP_HIP_E_HIP;
@@ -682,10 +682,10 @@ int masp_hip_prove_batch(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs, 
         if (hipEventSynchronize(sl.done) != hipSuccess) {
             last_hip_error() = "event sync failed";
             result = fail(ctx, MASP_HIP_E_HIP);
-        } else if (*sl.h_flags) {
+        } else if (*sl.h_flags.p) {
             result = MASP_HIP_E_SCALAR_RANGE;
         } else if (result == MASP_HIP_OK) {
-            for (size_t p = 0; p < idx.size(); ++p) memcpy(proofs_out + 192 * idx[p], sl.h_proof + 192 * p, 192);
+            for (size_t p = 0; p < idx.size(); ++p) memcpy(proofs_out + 192 * idx[p], sl.h_proof.p + 192 * p, 192);
         }
         return o.si;
     };

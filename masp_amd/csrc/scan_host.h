@@ -18,18 +18,9 @@ struct ScanHit {
 // a copy that is still queued when scan_collect fails has somewhere to land until the pipeline drains the stream.
 template <int N_EV>
 struct ScanSetHost {
-    hipEvent_t ev[N_EV] = {};
+    Event ev[N_EV];
     std::vector<uint32_t> idx;
     std::vector<uint8_t> data;
-    int create_events() {
-        for (hipEvent_t& e : ev)
-            if (!e) HIP_TRY(hipEventCreate(&e));
-        return MASP_HIP_OK;
-    }
-    ~ScanSetHost() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
 };
 
 // Waits for chunk c on its stream s and takes its statuses and hits.  count(nh), called once the chunk's counters are on the host,
@@ -61,12 +52,7 @@ int scan_collect(hipStream_t s, const ChunkInFlight& c, ScanSetHost<N_EV>& h, Co
         memcpy(hit.data, &h.data[P * i], P);
         hits.push_back(hit);
     }
-    for (int i = 0; i + 1 < N_EV; ++i) {
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, h.ev[i], h.ev[i + 1]));
-        ms[i] += t;
-    }
-    return MASP_HIP_OK;
+    return add_elapsed(h.ev, N_EV - 1, ms);
 }
 
 // A call's hits to the caller: sorted by (output, key), the order lanes reached the counter in being no order; *n_hits set; then

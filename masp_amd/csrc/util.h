@@ -150,12 +150,6 @@ struct PerDeviceOnce {
         return (ok[dev >> 6] & bit) != 0;
     }
 };
-// an event that is destroyed with its scope, whichever way the function returns (create it with hipEventCreate(&ev.e))
-struct ScopedEvent {
-    hipEvent_t e = nullptr;
-    ~ScopedEvent() { if (e) (void)hipEventDestroy(e); }
-    operator hipEvent_t() const { return e; }
-};
 }  // namespace masp
 
 #define MASP_LAUNCH(kernel, grid, block, shmem, stream, ...)                                \
@@ -175,3 +169,71 @@ struct ScopedEvent {
             return MASP_HIP_E_HIP;                                                                        \
         }                                                                                                 \
     } while (0)
+
+namespace masp {
+// A HIP event that is destroyed with its owner, whichever way that goes.  create() makes it on first use and leaves one that exists alone.
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+    Event& operator=(Event&& o) noexcept {
+        std::swap(e, o.e);
+        return *this;
+    }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    int create(unsigned flags = hipEventDefault) {
+        if (!e) HIP_TRY(hipEventCreateWithFlags(&e, flags));
+        return MASP_HIP_OK;
+    }
+    operator hipEvent_t() const { return e; }
+};
+template <size_t N>
+inline int create_events(Event (&ev)[N], unsigned flags = hipEventDefault) {
+    int rc = MASP_HIP_OK;
+    for (size_t i = 0; i < N && !rc; ++i) rc = ev[i].create(flags);
+    return rc;
+}
+// ms[k] += the time between events k and k + 1, for n_stages stages (the stream behind the last event has been synchronised)
+inline int add_elapsed(const Event* ev, int n_stages, double* ms) {
+    for (int k = 0; k < n_stages; ++k) {
+        float t = 0;
+        HIP_TRY(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
+        ms[k] += t;
+    }
+    return MASP_HIP_OK;
+}
+// page-locked host memory with the shape of DevBuf (internal.h): reserve() releases before it allocates and release() zeroes cap, so a
+// failed allocation leaves an empty buffer that the next reserve() fills, never a capacity with nothing behind it
+template <class T>
+struct PinnedBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    ~PinnedBuf() { release(); }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    int reserve(size_t n, unsigned flags = hipHostMallocDefault) {
+        if (n <= cap) return MASP_HIP_OK;
+        release();
+        HIP_TRY(hipHostMalloc((void**)&p, sizeof(T) * n, flags));
+        cap = n;
+        return MASP_HIP_OK;
+    }
+};
+// the stage times of a call kind's last call, under a lock of its own: a reader never waits for a running call
+template <int N>
+struct LastTiming {
+    std::mutex mu;
+    double ms[N] = {};
+    void store(const double* v) {
+        std::lock_guard<std::mutex> g(mu);
+        std::copy(v, v + N, ms);
+    }
+    void load(double* out) {
+        std::lock_guard<std::mutex> g(mu);
+        std::copy(ms, ms + N, out);
+    }
+};
+}  // namespace masp

@@ -296,6 +296,12 @@ class Context:
         if rc:
             raise MaspHipError(rc, self._L.masp_hip_last_error(self._h).decode(errors="replace"))
 
+    def _timing(self, fn, n, handle=None):
+        """the n stage times in ms that fn(handle, ms) reports (handle: this context's unless given)"""
+        ms = (C.c_double * n)()
+        self._check(fn(self._h if handle is None else handle, ms))
+        return tuple(ms)
+
     # ---- page-locked host buffers (assignments written here reach the device without a staging copy) ----
     def host_alloc(self, rows, cols=32):
         """-> np.uint8 array [rows, cols] over memory from masp_hip_host_alloc; release with host_free(array)."""
@@ -468,9 +474,7 @@ class Context:
 
     def note_scan_last_timing(self):
         """(upload ms, kernel ms) of the last scan, HIP events summed over its chunks"""
-        ms = (C.c_double * 2)()
-        self._check(self._L.masp_hip_note_scan_last_timing(self._h, ms))
-        return ms[0], ms[1]
+        return self._timing(self._L.masp_hip_note_scan_last_timing, 2)
 
     def sapling_compact_trial_decrypt(self, ivks, epks, cmus, enc_compact, lead_byte=2, hit_capacity=None, count_candidates=True):
         """batch::try_compact_note_decryption on the GPU, all of it (masp_hip_sapling_compact_trial_decrypt): ivks n_ivk x 32, epks and cmus
@@ -489,9 +493,7 @@ class Context:
 
     def note_scan_compact_last_timing(self):
         """(upload ms, stage 1 ms, stage 2 ms) of the last compact scan, HIP events summed over its chunks"""
-        ms = (C.c_double * 3)()
-        self._check(self._L.masp_hip_note_scan_compact_last_timing(self._h, ms))
-        return ms[0], ms[1], ms[2]
+        return self._timing(self._L.masp_hip_note_scan_compact_last_timing, 3)
 
     # ---- batch output recovery with outgoing viewing keys on the GPU ----
     def sapling_output_recovery_scan(self, ovks, cvs, epks, cmus, c_outs, hit_capacity=None):
@@ -507,9 +509,7 @@ class Context:
 
     def out_recovery_last_timing(self):
         """(upload ms, kernel ms) of the last output recovery scan, HIP events summed over its chunks"""
-        ms = (C.c_double * 2)()
-        self._check(self._L.masp_hip_out_recovery_last_timing(self._h, ms))
-        return ms[0], ms[1]
+        return self._timing(self._L.masp_hip_out_recovery_last_timing, 2)
 
     # ---- frozen commitment trees on the GPU ----
     def merkle_tree_complete(self, row, height0=0, positions=(), want_nodes=True, nodes_capacity=None):
@@ -564,9 +564,7 @@ class Context:
 
     def merkle_last_timing(self):
         """(upload ms, kernel ms, download ms) of the last tree of this context, from HIP events on its stream"""
-        ms = (C.c_double * 3)()
-        self._check(self._L.masp_hip_merkle_last_timing(self._h, ms))
-        return ms[0], ms[1], ms[2]
+        return self._timing(self._L.masp_hip_merkle_last_timing, 3)
 
     # ---- nullifiers and note commitments of a wallet's notes on the GPU ----
     def note_nullifiers(self, asset_identifiers, values, diversifiers, pk_ds, lead_bytes, rseeds, nks, positions, want_cmus=True):
@@ -590,9 +588,7 @@ class Context:
 
     def note_nullifiers_last_timing(self):
         """(upload ms, kernel ms, download ms) of the last note_nullifiers call of this context, HIP events summed over its chunks"""
-        ms = (C.c_double * 3)()
-        self._check(self._L.masp_hip_note_nullifiers_last_timing(self._h, ms))
-        return ms[0], ms[1], ms[2]
+        return self._timing(self._L.masp_hip_note_nullifiers_last_timing, 3)
 
     # ---- building blocks ----
     def msm_g1(self, bases, scalars):
@@ -915,8 +911,7 @@ class GpuVerifyingKey:
 
     def verify_each_last_timing(self):
         """HIP-event milliseconds of the last verify_each: decode (with the copies in), acc, miller, final_exp, copy out"""
-        ms = (C.c_double * 5)()
-        self._ctx._check(self._ctx._L.masp_hip_verify_each_last_timing(self._h, ms))
+        ms = self._ctx._timing(self._ctx._L.masp_hip_verify_each_last_timing, 5, self._h)
         return dict(zip(("decode", "acc", "miller", "final_exp", "copy_out"), ms))
 
     def close(self):

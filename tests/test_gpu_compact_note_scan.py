@@ -209,7 +209,7 @@ def test_arguments(ctx):
 
 
 def test_the_full_scan_is_unchanged(ctx):
-    """the two scans share the streams, ns_mu and the decode buffers: a full scan gives the same bytes before and after a compact one"""
+    """the two scans share the streams, WalletState::mu and the decode buffers: a full scan gives the same bytes before and after a compact one"""
     rng = random.Random(45)
     ivks_int = [rng.randrange(1, RJ) for _ in range(3)]
     ivks = b"".join(k.to_bytes(32, "little") for k in ivks_int)
