@@ -163,7 +163,6 @@ int masp_hip_circuit_tree_entry_bounds(const masp_hip_ctx* ctx, uint32_t slot, u
 }
 
 int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* params, size_t params_len, const masp_hip_r1cs* cs) {
-    const ApiLaunchScope api_scope;
     if (!ctx || !params || !cs || slot >= MASP_HIP_MAX_CIRCUITS || cs->n_inputs == 0) return MASP_HIP_E_INVALID_ARG;
     if (!ctx->children.empty()) {  // the CRS is replicated: every device builds its own window tables, side by side
         std::vector<int> rcs(ctx->children.size(), MASP_HIP_OK);
@@ -175,11 +174,10 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
             if (rc) return rc;
         return MASP_HIP_OK;
     }
-    std::unique_lock<std::shared_mutex> lock(ctx->mu);
-    hipSetDevice(ctx->device);
+    ApiCall call(ctx, CtxLock::EXCLUSIVE);
     hipStream_t s = ctx->streams.main;
     ParamsLayout L;
-    if (!parse_params(params, params_len, L)) return MASP_HIP_E_PARAMS_FORMAT;
+    if (!parse_params(params, params_len, L)) return call.done(MASP_HIP_E_PARAMS_FORMAT);
     std::unique_ptr<Circuit> C(new Circuit);
     C->n_inputs = cs->n_inputs;
     C->n_aux = cs->n_aux;
@@ -196,7 +194,7 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
     for (int mi = 0; mi < 3; ++mi) {
         uint32_t nnz = rp[mi][cs->n_constraints];
         for (uint32_t t = 0; t < nnz; ++t) {
-            if (cl[mi][t] >= nv) return MASP_HIP_E_INVALID_ARG;
+            if (cl[mi][t] >= nv) return call.done(MASP_HIP_E_INVALID_ARG);
             if (mi == 0) a_dense[cl[mi][t]] = 1;
             if (mi == 1) b_dense[cl[mi][t]] = 1;
         }
@@ -211,12 +209,12 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
     C->nbq = b_var.size();
     // length invariants
     if (L.n_ic != cs->n_inputs || L.n_h < C->m - 1 || L.n_l != cs->n_aux || L.n_a != C->na || L.n_b1 != C->nbq || L.n_b2 != C->nbq)
-        return MASP_HIP_E_PARAMS_SHAPE;
+        return call.done(MASP_HIP_E_PARAMS_SHAPE);
     int rc;
-    if ((rc = C->a_var.upload(a_var.data(), a_var.size(), s)) || (rc = C->b_var.upload(b_var.data(), b_var.size(), s))) return fail(ctx, rc);
+    if ((rc = C->a_var.upload(a_var.data(), a_var.size(), s)) || (rc = C->b_var.upload(b_var.data(), b_var.size(), s))) return call.done(rc);
     // static R1CS -> device (coefficients to Montgomery form)
     DevBuf<int> d_flag;
-    if ((rc = d_flag.reserve(1))) return fail(ctx, rc);
+    if ((rc = d_flag.reserve(1))) return call.done(rc);
     hipMemsetAsync(d_flag.p, 0, sizeof(int), s);
     for (int mi = 0; mi < 3; ++mi) {
         uint32_t nnz = rp[mi][cs->n_constraints];
@@ -225,7 +223,7 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
         for (uint32_t r = 0; r < cs->n_constraints; ++r) order[r] = r;
         std::stable_sort(order.begin(), order.end(),
                          [&](uint32_t x, uint32_t y) { return rp[mi][x + 1] - rp[mi][x] > rp[mi][y + 1] - rp[mi][y]; });
-        if ((rc = C->row_order[mi].upload(order.data(), order.size(), s))) return fail(ctx, rc);
+        if ((rc = C->row_order[mi].upload(order.data(), order.size(), s))) return call.done(rc);
         C->n_long_rows[mi] = 0;
         for (uint32_t r : order) {
             if (rp[mi][r + 1] - rp[mi][r] < R1CS_LONG_ROW) break;
@@ -233,17 +231,17 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
         }
         if ((rc = C->rowptr[mi].upload(rp[mi], cs->n_constraints + 1, s)) || (rc = C->col[mi].upload(cl[mi], nnz, s)) ||
             (rc = raw.upload((const Fr*)cf[mi], nnz, s)) || (rc = C->coef[mi].reserve(nnz)))
-            return fail(ctx, rc);
+            return call.done(rc);
         if (nnz) launch_fr_to_mont(s, raw.p, (size_t)0, C->coef[mi].p, nnz, 1, d_flag.p);
-        if (hipStreamSynchronize(s) != hipSuccess) return fail(ctx, MASP_HIP_E_HIP);
+        if (hipStreamSynchronize(s) != hipSuccess) return call.done(MASP_HIP_E_HIP);
     }
     // verifying-key points used by the prover
-    if ((rc = C->vk.reserve(1))) return fail(ctx, rc);
+    if ((rc = C->vk.reserve(1))) return call.done(rc);
     {
         DevBuf<uint8_t> raw;
-        if ((rc = raw.upload(params, 864, s))) return fail(ctx, rc);
+        if ((rc = raw.upload(params, 864, s))) return call.done(rc);
         DevBuf<int> st;
-        if ((rc = st.reserve(1))) return fail(ctx, rc);
+        if ((rc = st.reserve(1))) return call.done(rc);
         hipMemsetAsync(st.p, 0, sizeof(int), s);
         VkDevice* v = C->vk.p;
         launch_g1_import_one(s, raw.p + 0, &v->alpha_g1, st.p);
@@ -255,14 +253,14 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
         if (hipMemcpyAsync(&hst, st.p, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipMemcpyAsync(&hflag, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
             last_hip_error() = "vk import failed";
-            return fail(ctx, MASP_HIP_E_HIP);
+            return call.done(MASP_HIP_E_HIP);
         }
-        if (hflag) return MASP_HIP_E_SCALAR_RANGE;
-        if (hst & (PT_BAD_FLAGS | PT_NOT_CANONICAL)) return MASP_HIP_E_PARAMS_FORMAT;
+        if (hflag) return call.done(MASP_HIP_E_SCALAR_RANGE);
+        if (hst & (PT_BAD_FLAGS | PT_NOT_CANONICAL)) return call.done(MASP_HIP_E_PARAMS_FORMAT);
         // fixed-base tables for the points every proof multiplies by r, s, rs
         DevBuf<G1Affine> p1;
         DevBuf<G2Affine> p2;
-        if ((rc = p1.reserve(3)) || (rc = p2.reserve(1)) || (rc = C->fb1.reserve(3 * 32 * 255)) || (rc = C->fb2.reserve(32 * 255))) return fail(ctx, rc);
+        if ((rc = p1.reserve(3)) || (rc = p2.reserve(1)) || (rc = C->fb1.reserve(3 * 32 * 255)) || (rc = C->fb2.reserve(32 * 255))) return call.done(rc);
         hipMemcpyAsync(p1.p + 0, &v->delta_g1, sizeof(G1Affine), hipMemcpyDeviceToDevice, s);
         hipMemcpyAsync(p1.p + 1, &v->alpha_g1, sizeof(G1Affine), hipMemcpyDeviceToDevice, s);
         hipMemcpyAsync(p1.p + 2, &v->beta_g1, sizeof(G1Affine), hipMemcpyDeviceToDevice, s);
@@ -271,10 +269,10 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
         launch_fixed_table_g2(s, p2.p, C->fb2.p, 1);
         if (hipStreamSynchronize(s) != hipSuccess) {
             last_hip_error() = std::string("fixed-base tables failed: ") + hipGetErrorString(hipGetLastError());
-            return fail(ctx, MASP_HIP_E_HIP);
+            return call.done(MASP_HIP_E_HIP);
         }
         // delta at infinity -> bellperson's UnexpectedIdentity; alpha/beta at infinity are merely degenerate
-        if ((params[576] & 0x40) || (params[672] & 0x40)) return MASP_HIP_E_UNEXPECTED_IDENTITY;
+        if ((params[576] & 0x40) || (params[672] & 0x40)) return call.done(MASP_HIP_E_UNEXPECTED_IDENTITY);
     }
     // query vectors + window tables
     // h scalars are uniform in Fr; the witness queries are mostly 0 / 1 (70 % of a Spend witness is
@@ -302,7 +300,7 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
         (rc = C->a.load_host(L.a, L.n_a, s, eff(L.n_a), c_la, sub_bits, 0, 0xffffffffu, twin_ab)) ||
         (rc = C->b1.load_host(L.b_g1, L.n_b1, s, eff(L.n_b1), c_b, sub_bits, 0, 0xffffffffu, twin_ab)) ||
         (rc = C->b2.load_host(L.b_g2, L.n_b2, s, eff(L.n_b2), c_b2, sub_bits, 0, 0xffffffffu, twin_ab)))
-        return fail(ctx, rc);
+        return call.done(rc);
     if (C->b1.sub.bits && C->b2.sub.bits && msm_same_sort(C->b1, C->b2)) {
         // b_g2 is reduced from b_g1's sorted digit list (enqueue_proofs: share_b): the two tables have the same row layout, and the sort
         // must leave alone every block that is bad in either — both bitmaps become their union
@@ -310,18 +308,18 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
         std::vector<uint32_t> w1(words), w2(words);
         if (hipMemcpyAsync(w1.data(), C->b1.sub.bad, 4 * (size_t)words, hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipMemcpyAsync(w2.data(), C->b2.sub.bad, 4 * (size_t)words, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-            return fail(ctx, MASP_HIP_E_HIP);
+            return call.done(MASP_HIP_E_HIP);
         for (uint32_t i = 0; i < words; ++i) w1[i] |= w2[i];
         if (hipMemcpyAsync(C->b1.sub.bad, w1.data(), 4 * (size_t)words, hipMemcpyHostToDevice, s) != hipSuccess ||
             hipMemcpyAsync(C->b2.sub.bad, w1.data(), 4 * (size_t)words, hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-            return fail(ctx, MASP_HIP_E_HIP);
+            return call.done(MASP_HIP_E_HIP);
     }
     // plain tables of a / b_g1 for lone proofs where the batch tables were doubled (Circuit::a_lone)
-    if (C->a.g.twin && (rc = C->a_lone.load_host(L.a, L.n_a, s, eff(L.n_a), c_la, sub_bits))) return fail(ctx, rc);
-    if (C->b1.g.twin && (rc = C->b1_lone.load_host(L.b_g1, L.n_b1, s, eff(L.n_b1), c_b, sub_bits))) return fail(ctx, rc);
+    if (C->a.g.twin && (rc = C->a_lone.load_host(L.a, L.n_a, s, eff(L.n_a), c_la, sub_bits))) return call.done(rc);
+    if (C->b1.g.twin && (rc = C->b1_lone.load_host(L.b_g1, L.n_b1, s, eff(L.n_b1), c_b, sub_bits))) return call.done(rc);
     {
         const int c_lone = ctx->opt.window_bits_b2_lone;  // 0 = lone proofs share the batch tables (and B1's sort)
-        if (c_lone > 0 && L.n_b2 && (rc = C->b2_lone.load_host(L.b_g2, L.n_b2, s, eff(L.n_b2), c_lone))) return fail(ctx, rc);
+        if (c_lone > 0 && L.n_b2 && (rc = C->b2_lone.load_host(L.b_g2, L.n_b2, s, eff(L.n_b2), c_lone))) return call.done(rc);
     }
     const int c_hl = c_h ? c_h : ctx->opt.window_bits_h_lone ? 0 : C->h.g.c;
     {
@@ -330,14 +328,14 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
         memcpy(cat.data(), L.h, 96 * nh);
         memcpy(cat.data() + 96 * nh, L.l, 96 * (size_t)L.n_l);
         // (subset rows over the l part only: the quotient's coefficients are uniform in Fr)
-        if ((rc = C->hl.load_host(cat.data(), (uint32_t)(nh + L.n_l), s, 0xffffffffu, c_hl, sub_bits, (uint32_t)nh, 0xffffffffu, twin_hl))) return fail(ctx, rc);
+        if ((rc = C->hl.load_host(cat.data(), (uint32_t)(nh + L.n_l), s, 0xffffffffu, c_hl, sub_bits, (uint32_t)nh, 0xffffffffu, twin_hl))) return call.done(rc);
     }
     int st = C->h.import_status | C->l.import_status | C->a.import_status | C->b1.import_status | C->b2.import_status;
-    if (st) return MASP_HIP_E_PARAMS_FORMAT;  // includes infinity inside a query vector, which bellman rejects
+    if (st) return call.done(MASP_HIP_E_PARAMS_FORMAT);  // includes infinity inside a query vector, which bellman rejects
     {
         // may s*A and r*B1 use the endomorphism?  Only if everything A and B1 are sums of is in the subgroup (Circuit::g1_endo)
         DevBuf<int> out;
-        if ((rc = out.reserve(1))) return fail(ctx, rc);
+        if ((rc = out.reserve(1))) return call.done(rc);
         hipMemsetAsync(out.p, 0, sizeof(int), s);
         launch_g1_subgroup_flag(s, C->a.tab, sizeof(*C->a.tab), C->a.n, out.p);
         launch_g1_subgroup_flag(s, C->b1.tab, sizeof(*C->b1.tab), C->b1.n, out.p);
@@ -347,22 +345,22 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
         int outside = 1;
         if (hipMemcpyAsync(&outside, out.p, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess ||
             launch_status() != MASP_HIP_OK)
-            return fail(ctx, MASP_HIP_E_HIP);
+            return call.done(MASP_HIP_E_HIP);
         C->g1_endo = outside == 0;
     }
-    if ((rc = get_domain(ctx, C->logm, &C->dom))) return fail(ctx, rc);
+    if ((rc = get_domain(ctx, C->logm, &C->dom))) return call.done(rc);
     if (ctx->quotient_form == 0) {
         // the quotient in evaluation form: the derived base set next to `hl` (which jobs with their own a / b / c keep using).  A derived
         // point at infinity — a toy CRS — is no error: the circuit silently keeps the coefficient form.
         masp::EvalBases E;
-        if ((rc = build_eval_bases(ctx, *C->dom, L.h, L.l, cs, E))) return fail(ctx, rc);
+        if ((rc = build_eval_bases(ctx, *C->dom, L.h, L.l, cs, E))) return call.done(rc);
         if (E.usable) {
             const masp::EvalLayout& lay = E.lay;
             // (subset rows over the aux part only: the coset evaluations are as uniform in Fr as the coefficients were)
             if ((rc = C->hl_eval.load_device(E.d_raw.p, (uint32_t)lay.n(), s, 0xffffffffu, c_hl, sub_bits, (uint32_t)lay.aux_off(), (uint32_t)lay.in_off(), twin_hl)))
-                return fail(ctx, rc);
-            if ((rc = C->eval_in_var.upload(lay.used_inputs.data(), lay.used_inputs.size(), s))) return fail(ctx, rc);
-            if (hipStreamSynchronize(s) != hipSuccess) return fail(ctx, MASP_HIP_E_HIP);
+                return call.done(rc);
+            if ((rc = C->eval_in_var.upload(lay.used_inputs.data(), lay.used_inputs.size(), s))) return call.done(rc);
+            if (hipStreamSynchronize(s) != hipSuccess) return call.done(MASP_HIP_E_HIP);
             C->eval_inputs = lay.used_inputs;
             C->n_eval_in = (uint32_t)lay.used_inputs.size();
             if (C->hl_eval.import_status) {   // (cannot happen for points this library wrote; never prove on a table that failed its import)
@@ -395,8 +393,8 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
         bound(C->b1, (uint32_t)b_var.size(), count(b_var.data(), b_var.size()));
         bound(C->b2, (uint32_t)b_var.size(), count(b_var.data(), b_var.size()));
     }
-    ctx->circ[slot] = std::move(C);
-    return MASP_HIP_OK;
+    if ((rc = call.done(MASP_HIP_OK)) == MASP_HIP_OK) ctx->circ[slot] = std::move(C);   // (never a circuit behind a launch that was refused)
+    return rc;
 }
 
 int masp_hip_circuit_flags(const masp_hip_ctx* ctx, uint32_t slot, uint32_t* flags) {

@@ -18,6 +18,27 @@ struct JubjubCfg {
     static constexpr int TWO_ADICITY = 32;
 };
 
+// r_J, the order of Jubjub's prime-order subgroup, as a modulus of field.hpp (Fe<RjCfg>: k_redjubjub.hip's host-side scalar arithmetic)
+struct RjCfg {
+    static constexpr int N = 8;
+    static constexpr uint32_t MOD[8] = {0xd6f72cb7u, 0xd0970e5eu, 0xccc81082u, 0xa6682093u, 0x01343b00u, 0x06673b01u, 0x6533afa9u, 0x0e7db4eau};
+    static constexpr uint32_t R2[8] = {0x95e57731u, 0x67719aa4u, 0x9ce3fc26u, 0x51b0cef0u, 0xc026e9a5u, 0x69dab7fau, 0x8d127688u, 0x04f6547bu};   // 2^512 mod r_J
+    static constexpr uint32_t INV = 0xef788ef9u;   // -r_J^-1 mod 2^32
+};
+
+// a < r_J as eight little-endian words (jubjub::Fr::from_repr accepts exactly these)
+MASP_HD bool rj_is_canonical(const uint32_t a[8]) {
+    bool lt = false, decided = false;
+#pragma unroll
+    for (int i = 7; i >= 0; --i) {
+        if (!decided && a[i] != RjCfg::MOD[i]) {
+            lt = a[i] < RjCfg::MOD[i];
+            decided = true;
+        }
+    }
+    return lt;
+}
+
 struct JExt {
     Fr U, V, Z, T;
 };

@@ -37,24 +37,6 @@ MASP_HD JExt pedersen_note_commit_hash(const JNiels* table, const uint32_t* msg)
     return r;
 }
 
-// r_J, the order of Jubjub's prime-order subgroup
-struct RjCfg {
-    static constexpr uint32_t M[8] = {0xd6f72cb7u, 0xd0970e5eu, 0xccc81082u, 0xa6682093u, 0x01343b00u, 0x06673b01u, 0x6533afa9u, 0x0e7db4eau};
-};
-
-// a < r_J as eight little-endian words (jubjub::Fr::from_repr accepts exactly these)
-MASP_HD bool rj_is_canonical(const uint32_t a[8]) {
-    bool lt = false, decided = false;
-#pragma unroll
-    for (int i = 7; i >= 0; --i) {
-        if (!decided && a[i] != RjCfg::M[i]) {
-            lt = a[i] < RjCfg::M[i];
-            decided = true;
-        }
-    }
-    return lt;
-}
-
 // jubjub::Fr::from_bytes_wide: the 512-bit little-endian integer in in[0..15] mod r_J, bit by bit like the host's (it runs once per
 // candidate note): a = 2a + bit (a < r_J < 2^252: no overflow), then one conditional subtraction
 MASP_HD void rj_from_bytes_wide(uint32_t out[8], const uint32_t in[16]) {
@@ -70,7 +52,7 @@ MASP_HD void rj_from_bytes_wide(uint32_t out[8], const uint32_t in[16]) {
             uint32_t d[8], borrow = 0;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const uint64_t t = (uint64_t)a[i] - RjCfg::M[i] - borrow;
+                const uint64_t t = (uint64_t)a[i] - RjCfg::MOD[i] - borrow;
                 d[i] = (uint32_t)t;
                 borrow = (uint32_t)(t >> 32) & 1u;
             }

@@ -317,6 +317,16 @@ struct OnceTable : DevBuf<T> {
     }
 };
 
+// What the Jubjub entry points (k_redjubjub.hip: masp_hip_jubjub_msm, masp_hip_redjubjub_verify_batch, masp_hip_redjubjub_verify_each) keep
+// between calls.  They run next to proving calls on the verifier stream streams.vk[1], one at a time per context: `mu` guards every member
+// and is taken behind the context's.  The work buffers grow on demand and are kept.
+struct JubjubState {
+    std::mutex mu;
+    DevBuf<uint8_t> points, scalars, partial;
+    DevBuf<int> status;
+    DevBuf<uint32_t> out;
+};
+
 // What the wallet-side entry points of a device context keep between calls: the note scan (k_note_scan.hip), the compact note scan
 // (k_note_scan_compact.hip), the output recovery scan (k_out_recovery.hip), the commitment trees (k_merkle.hip) and the note nullifiers
 // (k_nullifier.hip).  One of these calls runs at a time per context: `mu` guards every member but the atomics and the timing records, and is
@@ -461,12 +471,7 @@ struct masp_hip_ctx {
     // fixed-base tables of the standard generators (parameter generation)
     DevBuf<G1Affine> fb_g1;
     DevBuf<G2Affine> fb_g2;
-    // the Jubjub entry points (k_redjubjub.hip: masp_hip_jubjub_msm, masp_hip_redjubjub_verify_batch) run next to proving calls on the
-    // verifier stream streams.vk[1], one at a time per context (jj_mu); their work buffers grow on demand and are kept
-    std::mutex jj_mu;
-    DevBuf<uint8_t> jj_points, jj_scalars, jj_partial;
-    DevBuf<int> jj_status;
-    DevBuf<uint32_t> jj_out;
+    masp::JubjubState jj;       // the Jubjub calls' state, under a lock of its own
     masp::WalletState wallet;   // the wallet-side calls' state, under a lock of its own
 };
 
@@ -483,18 +488,39 @@ static inline int fail(masp_hip_ctx* ctx, int rc) {
 // the context a single-device entry point works on: a multi-device front's first device context
 #define FIRST_DEVICE(ctx) ((ctx) && !(ctx)->children.empty() ? (ctx)->children[0] : (ctx))
 
-// The opening of every wallet-side entry point, in this order: the launch scope, the first device's context, its `mu` shared (concurrent
-// with provers and verifiers), the wallet lock, the device.  done(rc) is how such a call returns once it holds the locks.
-struct WalletCall {
+// The opening of every entry point that launches kernels, in this order: the launch scope, the first device's context, its `mu` — SHARED
+// next to provers, verifiers and wallet calls, EXCLUSIVE for what changes circuits or uses the shared scratch —, the device.  A second mutex
+// (a key's, JubjubState::mu, WalletState::mu) is taken behind it.  Argument checks that need no lock stand in front; once the call is open,
+// done(rc) is its only way out: success is reported only if no launch was refused (util.h: ApiLaunchScope), and this is the one place that
+// calls fail().  Helpers return their rc to the entry point and never call fail() themselves.
+enum class CtxLock { SHARED, EXCLUSIVE };
+struct ApiCall {
     const ApiLaunchScope scope;
     masp_hip_ctx* const ctx;
-    std::shared_lock<std::shared_mutex> lock;
+    std::shared_lock<std::shared_mutex> shared;
+    std::unique_lock<std::shared_mutex> exclusive;
+    ApiCall(masp_hip_ctx* c, CtxLock kind) : ctx(FIRST_DEVICE(c)), shared(ctx->mu, std::defer_lock), exclusive(ctx->mu, std::defer_lock) {
+        if (kind == CtxLock::SHARED)
+            shared.lock();
+        else
+            exclusive.lock();
+        hipSetDevice(ctx->device);
+    }
+    int done(int rc) {
+        if (rc == MASP_HIP_OK) rc = launch_status();
+        return rc ? fail(ctx, rc) : MASP_HIP_OK;
+    }
+};
+
+// a wallet-side entry point: an ApiCall next to provers and verifiers, the wallet lock, and the uploaded-once tables settled on the way out
+struct WalletCall : ApiCall {
     std::lock_guard<std::mutex> wlock;
     WalletState& w;
-    explicit WalletCall(masp_hip_ctx* c) : ctx(FIRST_DEVICE(c)), lock(ctx->mu), wlock(ctx->wallet.mu), w(ctx->wallet) { hipSetDevice(ctx->device); }
+    explicit WalletCall(masp_hip_ctx* c) : ApiCall(c, CtxLock::SHARED), wlock(ctx->wallet.mu), w(ctx->wallet) {}
     int done(int rc) {
+        rc = ApiCall::done(rc);
         w.settle_tables(rc);
-        return rc ? fail(ctx, rc) : MASP_HIP_OK;
+        return rc;
     }
 };
 

@@ -94,15 +94,6 @@ __global__ __launch_bounds__(NS_BLOCK) void k_ns_trial(const uint32_t* __restric
     hit_keys[2 * slot + 1] = make_uint4(key[4], key[5], key[6], key[7]);
 }
 
-// r_J, the order of the prime-order subgroup (a SaplingIvk is a canonical scalar below it)
-constexpr uint32_t RJ[8] = {0xd6f72cb7u, 0xd0970e5eu, 0xccc81082u, 0xa6682093u, 0x01343b00u, 0x06673b01u, 0x6533afa9u, 0x0e7db4eau};
-
-bool below_rj(const uint32_t* k) {
-    for (int i = 7; i >= 0; --i)
-        if (k[i] != RJ[i]) return k[i] < RJ[i];
-    return false;
-}
-
 // the digit masks of k_ns_trial for one ivk.  signed_digits: the non-adjacent form (digits -1, 0, 1, no two neighbours non-zero: a third
 // of the positions instead of half, at most 253 of them for k < 2^252); otherwise the plain binary digits.
 void recode(uint32_t out[16], const uint32_t k_in[8], bool signed_digits) {
@@ -167,7 +158,7 @@ int ns_recode_ivks(std::vector<uint32_t>& digits, size_t n_ivk, const uint8_t* i
     for (size_t k = 0; k < n_ivk; ++k) {
         uint32_t w[8];
         memcpy(w, ivks + 32 * k, 32);   // (little-endian host)
-        if (!below_rj(w)) return MASP_HIP_E_INVALID_ARG;
+        if (!rj_is_canonical(w)) return MASP_HIP_E_INVALID_ARG;   // a SaplingIvk is a canonical scalar below r_J
         recode(&digits[16 * k], w, signed_digits);
     }
     return MASP_HIP_OK;

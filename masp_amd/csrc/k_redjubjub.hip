@@ -67,34 +67,28 @@ __global__ __launch_bounds__(JJ_BLOCK) void k_jj_sum(const JExt* __restrict__ pa
 
 // sum_i [scalars_i] points_i over m >= 1 points (m x 32 bytes each) on the context's verifier stream.  status (m): 0 or why point i
 // does not decode (its product is left out of the sum); out9: the encoding of the sum, or of [8] sum with `cofactor`, and the identity flag.
-// Caller: ctx->mu shared, ctx->jj_mu held.
+// Caller: ctx->mu shared, ctx->jj.mu held.
 int jj_msm_run(masp_hip_ctx* ctx, size_t m, const uint8_t* points, const uint8_t* scalars, int cofactor, std::vector<int>& status, uint32_t out9[9]) {
+    JubjubState& jj = ctx->jj;
     hipStream_t s = ctx->streams.vk[1];
     const uint32_t mm = (uint32_t)m, nb = (mm + JJ_BLOCK - 1) / JJ_BLOCK;
     int rc;
-    if ((rc = ctx->jj_points.upload(points, 32 * m, s)) || (rc = ctx->jj_scalars.upload(scalars, 32 * m, s)) || (rc = ctx->jj_status.reserve(m)) ||
-        (rc = ctx->jj_partial.reserve(sizeof(JExt) * nb)) || (rc = ctx->jj_out.reserve(9)))
-        return fail(ctx, rc);
-    MASP_LAUNCH(k_jj_scale, dim3(nb), dim3(JJ_BLOCK), 0, s, (const uint4*)ctx->jj_points.p, (const uint4*)ctx->jj_scalars.p, mm, ctx->jj_status.p,
-                (JExt*)ctx->jj_partial.p);
-    MASP_LAUNCH(k_jj_sum, dim3(1), dim3(JJ_BLOCK), 0, s, (const JExt*)ctx->jj_partial.p, nb, cofactor, ctx->jj_out.p);
+    if ((rc = jj.points.upload(points, 32 * m, s)) || (rc = jj.scalars.upload(scalars, 32 * m, s)) || (rc = jj.status.reserve(m)) ||
+        (rc = jj.partial.reserve(sizeof(JExt) * nb)) || (rc = jj.out.reserve(9)))
+        return rc;
+    MASP_LAUNCH(k_jj_scale, dim3(nb), dim3(JJ_BLOCK), 0, s, (const uint4*)jj.points.p, (const uint4*)jj.scalars.p, mm, jj.status.p, (JExt*)jj.partial.p);
+    MASP_LAUNCH(k_jj_sum, dim3(1), dim3(JJ_BLOCK), 0, s, (const JExt*)jj.partial.p, nb, cofactor, jj.out.p);
     status.resize(m);
-    if (hipMemcpyAsync(status.data(), ctx->jj_status.p, sizeof(int) * m, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(out9, ctx->jj_out.p, 9 * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+    if (hipMemcpyAsync(status.data(), jj.status.p, sizeof(int) * m, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(out9, jj.out.p, 9 * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
         last_hip_error() = std::string("jubjub multi-scalar sum failed: ") + hipGetErrorString(hipGetLastError());
-        return fail(ctx, MASP_HIP_E_HIP);
+        return MASP_HIP_E_HIP;
     }
-    if (launch_status() != MASP_HIP_OK) return fail(ctx, MASP_HIP_E_HIP);  // a refused launch: the buffers read back mean nothing
-    return MASP_HIP_OK;
+    return launch_status();  // a refused launch: the buffers read back mean nothing
 }
 
-// ---- the Jubjub scalar field (order r_J of the prime-order subgroup), host-side Montgomery arithmetic through field.hpp's host forms ----
-struct RjCfg {
-    static constexpr int N = 8;
-    static constexpr uint32_t MOD[8] = {0xd6f72cb7u, 0xd0970e5eu, 0xccc81082u, 0xa6682093u, 0x01343b00u, 0x06673b01u, 0x6533afa9u, 0x0e7db4eau};
-    static constexpr uint32_t R2[8] = {0x95e57731u, 0x67719aa4u, 0x9ce3fc26u, 0x51b0cef0u, 0xc026e9a5u, 0x69dab7fau, 0x8d127688u, 0x04f6547bu};   // 2^512 mod r_J
-    static constexpr uint32_t INV = 0xef788ef9u;   // -r_J^-1 mod 2^32
-};
+// ---- the Jubjub scalar field (order r_J of the prime-order subgroup: RjCfg, device/jubjub.hpp), host-side Montgomery arithmetic through
+// field.hpp's host forms ----
 typedef Fe<RjCfg> Rj;
 
 // One lane per signature, no sum across lanes: items[i] = Rbar | vk | c | S (4 x 32 bytes; c = H*(Rbar || vk || sighash) reduced mod
@@ -117,6 +111,7 @@ __global__ __launch_bounds__(64) void k_jj_verify_each(const uint4* __restrict__
     ok = (jj_decode(vk, w) == JJ_OK) && ok;
     words(items + 8 * (size_t)i + 4, c);
     words(items + 8 * (size_t)i + 6, sc);
+    // (rj_is_canonical(sc) says the same; written out because the kernel's code is then what it has been, instruction for instruction)
     bool s_ge = true;   // S >= r_J, decided at the first word that differs from the top
     for (int k = 7; k >= 0; --k)
         if (sc[k] != RjCfg::MOD[k]) {
@@ -200,22 +195,19 @@ int masp_hip_jubjub_msm(masp_hip_ctx* ctx, size_t n, const uint8_t* points, cons
         out32[0] = 1;   // the identity (0, 1)
         return MASP_HIP_OK;
     }
-    const ApiLaunchScope api_scope;
-    ctx = FIRST_DEVICE(ctx);
-    std::shared_lock<std::shared_mutex> lock(ctx->mu);   // concurrent with provers and verifiers
-    std::lock_guard<std::mutex> jlock(ctx->jj_mu);
-    hipSetDevice(ctx->device);
+    ApiCall call(ctx, CtxLock::SHARED);   // concurrent with provers and verifiers
+    std::lock_guard<std::mutex> jlock(call.ctx->jj.mu);
     std::vector<int> status;
     uint32_t out9[9];
-    int rc = jj_msm_run(ctx, n, points, scalars, 0, status, out9);
-    if (rc) return rc;
+    int rc = jj_msm_run(call.ctx, n, points, scalars, 0, status, out9);
+    if (rc) return call.done(rc);
     for (size_t i = 0; i < n; ++i)
         if (status[i]) {
             if (bad_index) *bad_index = (int64_t)i;
-            return MASP_HIP_E_POINT_ENCODING;
+            return call.done(MASP_HIP_E_POINT_ENCODING);
         }
     memcpy(out32, out9, 32);
-    return MASP_HIP_OK;
+    return call.done(MASP_HIP_OK);
 }
 
 int masp_hip_redjubjub_verify_batch(masp_hip_ctx* ctx, size_t n, const uint8_t* vks, const uint8_t* sigs, const uint8_t* sighashes,
@@ -249,19 +241,16 @@ int masp_hip_redjubjub_verify_batch(masp_hip_ctx* ctx, size_t n, const uint8_t* 
     memcpy(&pts[32 * 2 * n], basepoints(), 64);
     rj_store(&sc[32 * 2 * n], fe_neg(acc[0]));
     rj_store(&sc[32 * (2 * n + 1)], fe_neg(acc[1]));
-    const ApiLaunchScope api_scope;
-    ctx = FIRST_DEVICE(ctx);
-    std::shared_lock<std::shared_mutex> lock(ctx->mu);
-    std::lock_guard<std::mutex> jlock(ctx->jj_mu);
-    hipSetDevice(ctx->device);
+    ApiCall call(ctx, CtxLock::SHARED);
+    std::lock_guard<std::mutex> jlock(call.ctx->jj.mu);
     std::vector<int> status;
     uint32_t out9[9];
-    int rc = jj_msm_run(ctx, m, pts.data(), sc.data(), 1, status, out9);
-    if (rc) return rc;
+    int rc = jj_msm_run(call.ctx, m, pts.data(), sc.data(), 1, status, out9);
+    if (rc) return call.done(rc);
     for (int st : status)
-        if (st) return MASP_HIP_OK;   // an R or vk that does not decode: not valid
+        if (st) return call.done(MASP_HIP_OK);   // an R or vk that does not decode: not valid
     *all_valid = out9[8] == 1;
-    return MASP_HIP_OK;
+    return call.done(MASP_HIP_OK);
 }
 
 int masp_hip_redjubjub_verify_each(masp_hip_ctx* ctx, size_t n, const uint8_t* vks, const uint8_t* sigs, const uint8_t* sighashes,
@@ -281,24 +270,20 @@ int masp_hip_redjubjub_verify_each(masp_hip_ctx* ctx, size_t n, const uint8_t* v
         memcpy(it + 96, sig + 32, 32);
     }
     memcpy(&items[128 * n], basepoints(), 64);
-    const ApiLaunchScope api_scope;
-    ctx = FIRST_DEVICE(ctx);
-    std::shared_lock<std::shared_mutex> lock(ctx->mu);
-    std::lock_guard<std::mutex> jlock(ctx->jj_mu);
-    hipSetDevice(ctx->device);
-    hipStream_t s = ctx->streams.vk[1];
+    ApiCall call(ctx, CtxLock::SHARED);
+    JubjubState& jj = call.ctx->jj;
+    std::lock_guard<std::mutex> jlock(jj.mu);
+    hipStream_t s = call.ctx->streams.vk[1];
     const uint32_t nn = (uint32_t)n;
     int rc;
-    if ((rc = ctx->jj_points.upload(items.data(), items.size(), s)) || (rc = ctx->jj_scalars.upload(kinds, n, s)) || (rc = ctx->jj_partial.reserve(n)))
-        return fail(ctx, rc);
-    MASP_LAUNCH(k_jj_verify_each, dim3((nn + 63) / 64), dim3(64), 0, s, (const uint4*)ctx->jj_points.p, (const uint8_t*)ctx->jj_scalars.p,
-                (const uint4*)(ctx->jj_points.p + 128 * n), nn, ctx->jj_partial.p);
-    if (hipMemcpyAsync(verdicts, ctx->jj_partial.p, n, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+    if ((rc = jj.points.upload(items.data(), items.size(), s)) || (rc = jj.scalars.upload(kinds, n, s)) || (rc = jj.partial.reserve(n))) return call.done(rc);
+    MASP_LAUNCH(k_jj_verify_each, dim3((nn + 63) / 64), dim3(64), 0, s, (const uint4*)jj.points.p, (const uint8_t*)jj.scalars.p,
+                (const uint4*)(jj.points.p + 128 * n), nn, jj.partial.p);
+    if (hipMemcpyAsync(verdicts, jj.partial.p, n, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
         last_hip_error() = std::string("per-signature verification failed: ") + hipGetErrorString(hipGetLastError());
-        return fail(ctx, MASP_HIP_E_HIP);
+        return call.done(MASP_HIP_E_HIP);
     }
-    if (launch_status() != MASP_HIP_OK) return fail(ctx, MASP_HIP_E_HIP);  // a refused launch: the bytes read back mean nothing
-    return MASP_HIP_OK;
+    return call.done(MASP_HIP_OK);  // (a refused launch: the bytes read back mean nothing — done() asks)
 }
 
 }  // extern "C"

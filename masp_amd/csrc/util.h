@@ -41,7 +41,8 @@ inline int launch_status() {
 }
 // First statement of every extern "C" entry point that launches kernels: whatever an earlier call of this thread left behind —
 // a latched launch failure that no launch_status() picked up, or a HIP error the embedding application (torch, RCCL ...) left on the
-// thread — must not be reported by this call as its own.  Each such entry point asks launch_status() before it reports success.
+// thread — must not be reported by this call as its own.  Each such entry point asks launch_status() before it reports success: inside
+// libmasp_hip it opens an ApiCall (internal.h), which holds this scope, and returns through ApiCall::done(), which asks.
 struct ApiLaunchScope {
     ApiLaunchScope() {
         (void)hipGetLastError();
@@ -159,15 +160,21 @@ struct PerDeviceOnce {
         if (_le != hipSuccess) masp::note_launch_error(_le, #kernel, __FILE__, __LINE__);   \
     } while (0)
 
-#define HIP_TRY(expr)                                                                                     \
-    do {                                                                                                  \
-        hipError_t _e = (expr);                                                                           \
-        if (_e != hipSuccess) {                                                                           \
-            char _b[512];                                                                                 \
-            snprintf(_b, sizeof(_b), "%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-            masp::last_hip_error() = _b;                                                                  \
-            return MASP_HIP_E_HIP;                                                                        \
-        }                                                                                                 \
+namespace masp {
+inline int hip_rc(hipError_t e, const char* expr, const char* file, int line) {
+    if (e == hipSuccess) return MASP_HIP_OK;
+    char b[512];
+    snprintf(b, sizeof(b), "%s:%d: %s -> %s", file, line, expr, hipGetErrorString(e));
+    last_hip_error() = b;
+    return MASP_HIP_E_HIP;
+}
+}  // namespace masp
+// A HIP call's outcome as one of this library's codes, with last_hip_error() set if it failed.  HIP_RC yields the code: for the body of an
+// entry point, which leaves through ApiCall::done() alone.  HIP_TRY returns it: for helpers that hand their rc to an entry point.
+#define HIP_RC(expr) masp::hip_rc((expr), #expr, __FILE__, __LINE__)
+#define HIP_TRY(expr)                                \
+    do {                                             \
+        if (HIP_RC(expr)) return MASP_HIP_E_HIP;     \
     } while (0)
 
 namespace masp {

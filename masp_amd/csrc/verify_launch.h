@@ -5,6 +5,7 @@
 #pragma once
 #include <algorithm>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 #include "device/pairing.hpp"
@@ -13,6 +14,33 @@
 #include "util.h"
 
 namespace masp {
+
+// Interpreter programs (host/pairing_prog.h) as the kernels read them: the ops of all of them in one array, and every program's step_start
+// as absolute indices into it.  dev(i, ...) is program i over the uploaded copies of the two arrays; n_slots is what the largest one needs.
+struct ProgramTable {
+    std::vector<uint32_t> ops, steps;
+    std::vector<size_t> st_off;
+    std::vector<uint32_t> n_steps;
+    uint32_t n_slots = 0;
+    PairingProgramDev dev(int i, const uint32_t* d_ops, const uint32_t* d_steps) const { return {d_ops, d_steps + st_off[i], n_steps[i]}; }
+};
+inline ProgramTable concat_programs(std::initializer_list<const masp_host::prog::Program*> programs) {
+    ProgramTable t;
+    for (const masp_host::prog::Program* p : programs) {
+        const uint32_t op_off = (uint32_t)t.ops.size();
+        t.st_off.push_back(t.steps.size());
+        for (uint32_t s : p->step_start) t.steps.push_back(s + op_off);
+        t.ops.insert(t.ops.end(), p->ops.begin(), p->ops.end());
+        t.n_steps.push_back((uint32_t)p->step_start.size() - 1);
+        t.n_slots = std::max(t.n_slots, p->n_slots);
+    }
+    return t;
+}
+// the batch verifier's three: dbl, add (k_miller_pairs) and mul12 (k_fp12_product)
+inline ProgramTable pairing_program_table() {
+    const masp_host::prog::PairingPrograms& pp = masp_host::prog::pairing_programs();
+    return concat_programs({&pp.dbl, &pp.add, &pp.mul12});
+}
 
 // vals[0] <- the product of the n Fp12 values at vals (12 Fp each, n >= 1; the others are overwritten with partial products):
 // min(n, 64) waves multiply a strided share each, then one wave multiplies their results.  lds: n_slots x 48 bytes of dynamic LDS.
@@ -71,26 +99,16 @@ inline std::vector<G1Affine> ic_table(const masp_host::PreparedVk& vk) {
 }
 // the six programs of the final exponentiation concatenated (mul, sq, frob, frob2, inv1, inv2), its schedule and the 15 Frobenius
 // constants, as k_final_exp reads them
-struct FinalExpTables {
-    std::vector<uint32_t> ops, steps, sched;
-    size_t st_off[6];
-    uint32_t n_steps[6], n_slots;
+struct FinalExpTables : ProgramTable {
+    std::vector<uint32_t> sched;
     Fp consts[15];
-    PairingProgramDev dev(int i, const uint32_t* d_ops, const uint32_t* d_steps) const { return {d_ops, d_steps + st_off[i], n_steps[i]}; }
 };
 inline FinalExpTables final_exp_tables() {
     namespace mp = masp_host::prog;
     const mp::FinalExpPrograms& fp = mp::final_exp_programs();
     FinalExpTables t;
-    for (int i = 0; i < 6; ++i) {
-        const size_t op_off = t.ops.size();
-        t.st_off[i] = t.steps.size();
-        for (uint32_t s : fp.all(i)->step_start) t.steps.push_back(s + (uint32_t)op_off);  // absolute indices into the concatenation
-        t.ops.insert(t.ops.end(), fp.all(i)->ops.begin(), fp.all(i)->ops.end());
-        t.n_steps[i] = (uint32_t)fp.all(i)->step_start.size() - 1;
-    }
+    static_cast<ProgramTable&>(t) = concat_programs({fp.all(0), fp.all(1), fp.all(2), fp.all(3), fp.all(4), fp.all(5)});
     t.sched = mp::final_exp_schedule();
-    t.n_slots = fp.n_slots;
     masp_host::bls::Fp c[15];
     mp::final_exp_constants(c);
     static_assert(sizeof(masp_host::bls::Fp) == sizeof(Fp), "one residue is 48 bytes on both sides");

@@ -49,26 +49,6 @@ bool hfp12_of_be(hb::Fp12& f, const uint8_t* in) {
     return true;
 }
 
-// the three interpreter programs concatenated as masp_hip_vk_prepare uploads them
-struct Programs {
-    std::vector<uint32_t> ops, steps;
-    size_t st_off[3];
-    uint32_t n_steps[3], n_slots;
-    Programs() {
-        const masp_host::prog::PairingPrograms& pp = masp_host::prog::pairing_programs();
-        const masp_host::prog::Program* ps[3] = {&pp.dbl, &pp.add, &pp.mul12};
-        for (int i = 0; i < 3; ++i) {
-            const size_t op_off = ops.size();
-            st_off[i] = steps.size();
-            for (uint32_t s : ps[i]->step_start) steps.push_back(s + (uint32_t)op_off);
-            ops.insert(ops.end(), ps[i]->ops.begin(), ps[i]->ops.end());
-            n_steps[i] = (uint32_t)ps[i]->step_start.size() - 1;
-        }
-        n_slots = pp.n_slots;
-    }
-    PairingProgramDev dev(int i, const uint32_t* d_ops, const uint32_t* d_steps) const { return {d_ops, d_steps + st_off[i], n_steps[i]}; }
-};
-
 // device buffers of one call, released when it returns
 struct Scope {
     std::vector<void*> bufs;
@@ -174,7 +154,7 @@ int vfy_g1_sum_gpu(const uint8_t* points96, uint32_t n, uint8_t* out96) {
 int vfy_miller_gpu(const uint8_t* p96, const uint8_t* q192, uint32_t n, uint8_t* out) {
     if (n == 0) return 0;
     const ApiLaunchScope api_scope;
-    const Programs pr;
+    const ProgramTable pr = pairing_program_table();   // what masp_hip_vk_prepare uploads
     const uint32_t lds = pr.n_slots * 48;
     if (lds > 64 * 1024 || !raise_lds()) return -5;
     std::vector<G1Affine> hp(n);
@@ -203,7 +183,7 @@ int vfy_miller_gpu(const uint8_t* p96, const uint8_t* q192, uint32_t n, uint8_t*
 int vfy_fp12_product_gpu(const uint8_t* vals, uint32_t n, uint8_t* out) {
     if (n == 0) return -1;
     const ApiLaunchScope api_scope;
-    const Programs pr;
+    const ProgramTable pr = pairing_program_table();   // what masp_hip_vk_prepare uploads
     const uint32_t lds = pr.n_slots * 48;
     if (lds > 64 * 1024 || !raise_lds()) return -5;
     std::vector<Fp> hf(12 * (size_t)n);

@@ -182,6 +182,21 @@ def test_near_misses_in_one_batch(ctx):
                 (pt.tobytes(), pk.tobytes())
 
 
+def test_an_ivk_at_or_above_the_group_order_is_refused(ctx):
+    """1 ivk x 1 output.  r_J, r_J + 1, r_J with its top word one higher (every lower word equal) and 2^256 - 1 are no SaplingIvk: the
+    host library refuses each, and so does the call, with MASP_HIP_E_INVALID_ARG.  (r_J - 1 is one: test_near_misses_in_one_batch.)"""
+    tv = VECTORS[0]
+    epk, cmu, enc = (np.frombuffer(tv[f], np.uint8) for f in ("epk", "cmu", "c_enc"))
+    enc = enc[:84].copy()
+    for k in (RJ, RJ + 1, RJ + (1 << 224), (1 << 256) - 1):
+        ivk = k.to_bytes(32, "little")
+        with pytest.raises(H.HostError):
+            H.sapling_try_compact_note_decryption_batch([ivk], [tv["epk"]], [tv["cmu"]], [tv["c_enc"][:84]], lead_byte=1, threads=1)
+        with pytest.raises(masp_amd.MaspHipError) as e:
+            ctx.sapling_compact_trial_decrypt(ivk, epk, cmu, enc, 1)
+        assert e.value.code == 1, k
+
+
 def test_arguments(ctx):
     tv = VECTORS[0]
     epk, cmu, enc = (np.frombuffer(tv[f], np.uint8) for f in ("epk", "cmu", "c_enc"))

@@ -216,6 +216,20 @@ def test_small_order_epk_and_edge_ivks(ctx):
     assert sum(w is not None for w in host_result(ivks, epks, cmus, encs, 2)) == 2       # the two honest notes; the esk check refuses the rest
 
 
+def test_an_ivk_at_or_above_the_group_order_is_refused(ctx):
+    """1 ivk x 1 output.  r_J, r_J + 1, r_J with its top word one higher (every lower word equal) and 2^256 - 1 are no SaplingIvk: the
+    host library refuses each, and so does the call, with MASP_HIP_E_INVALID_ARG.  (r_J - 1 is one: test_small_order_epk_and_edge_ivks.)"""
+    tv = VECTORS[0]
+    epk, enc = np.frombuffer(tv["epk"], np.uint8), np.frombuffer(tv["c_enc"], np.uint8)
+    for k in (RJ, RJ + 1, RJ + (1 << 224), (1 << 256) - 1):
+        ivk = k.to_bytes(32, "little")
+        with pytest.raises(H.HostError):
+            H.sapling_try_note_decryption_batch([ivk], [tv["epk"]], [tv["cmu"]], [tv["c_enc"]], threads=1)
+        with pytest.raises(masp_amd.MaspHipError) as e:
+            ctx.sapling_trial_decrypt(ivk, epk, enc)
+        assert e.value.code == 1, k
+
+
 def test_arguments(ctx):
     tv = VECTORS[0]
     epk, enc = np.frombuffer(tv["epk"], np.uint8), np.frombuffer(tv["c_enc"], np.uint8)

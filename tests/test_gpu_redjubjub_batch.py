@@ -102,6 +102,19 @@ def test_one_bad_item_at_first_middle_last(ctx):
     assert ctx.redjubjub_verify_batch(items) is True
 
 
+def test_s_equal_to_the_group_order_is_no_signature(ctx):
+    """S = r_J exactly, the smallest S that jubjub::Fr::from_repr refuses (the batch call decides it on the host, the per-item call in
+    its kernel), as the middle one of 5 items: the batch call answers all_valid = 0, the per-item call 0 for that item alone."""
+    rng = random.Random(9)
+    items = [_item(rng)[0] for _ in range(5)]
+    vk, sig, sighash, kind = items[2]
+    batch = items[:2] + [(vk, sig[:32] + RJ.to_bytes(32, "little"), sighash, kind)] + items[3:]
+    want = [_single(it) for it in batch]
+    assert want == [True, True, False, True, True]
+    assert ctx.redjubjub_verify_batch(batch) is False
+    assert ctx.redjubjub_verify_each(batch) == want
+
+
 def test_cofactor_cases_are_accepted(ctx):
     rng = random.Random(8)
     items = [_item(rng)[0] for _ in range(10)]
