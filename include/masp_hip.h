@@ -398,6 +398,61 @@ int masp_hip_redjubjub_verify_batch(masp_hip_ctx* ctx, size_t n, const uint8_t* 
 int masp_hip_redjubjub_verify_each(masp_hip_ctx* ctx, size_t n, const uint8_t* vks, const uint8_t* sigs, const uint8_t* sighashes,
                                    const uint8_t* kinds, uint8_t* verdicts);
 
+/* ---- The consensus pre-checks of a block's bundles on the GPU ----
+ * masp_hip_sapling_check_bundles <- what BatchValidator::check_bundle decides before it queues a proof or a signature
+ *    (masp_proofs/src/sapling/verifier/batch.rs:78-193 over SaplingVerificationContextInner, verifier.rs:20-204), for all bundles of a
+ * block at once: per description whether cv / rk / epk decode (ZIP 216) and are not of small order and whether `Proof::read` accepts the
+ * proof, the description's public inputs (verifier.rs:71-95, 120-128, 151-165), and per bundle the binding verification key
+ *    bvk = sum cv(spends) + sum cv(converts) - sum cv(outputs) - sum_entries sign(value) [|value|] [8] asset_generator(identifier)
+ * (verifier.rs:167-204 with masp_compute_value_balance, sapling/mod.rs:14-38).  The caller rebuilds the validator's queues from the
+ * statuses; signatures and proofs are then verified by the calls above.
+ * Arguments: one struct of counts and pointers.  counts: n_bundles x 4, the spends, converts, outputs and value-balance entries of each
+ * bundle; the items of each kind lie bundle after bundle in their arrays.  Spends: cv, anchor, nullifier, rk (32 bytes each) and
+ * zkproof (192); converts: cv, anchor, zkproof; outputs: cv, cmu, epk, zkproof; value balance: asset identifiers (32 bytes) and values as
+ * 16-byte little-endian two's-complement i128.
+ * Limits: each of the four totals <= 2^20, n_bundles <= 2^22.  MASP_HIP_E_INVALID_ARG, with nothing written, when a limit is passed, when
+ * the column sums of counts differ from the four totals, or when an array with a nonzero total (counts, bvk and bundle_status with a
+ * nonzero n_bundles) is NULL.  n_bundles = 0: MASP_HIP_OK, no GPU work, nothing read.
+ * Results, all written on success:
+ *  - one status byte per description, 0 or the first reason that applies in this order (the reference tells none apart: each makes
+ *    check_bundle return false at that description):
+ *       1  cv does not decode (v >= r, u^2 not a square, u = 0 with the sign bit set: JPoint::from_bytes)
+ *       2  rk (spend) or epk (output) does not decode
+ *       3  `Proof::read` refuses the proof: flags, a non-canonical coordinate, off the curve, outside the subgroup, the identity
+ *          (exactly masp_host_proof_read)
+ *       4  cv has small order
+ *       5  rk / epk has small order
+ *  - the public inputs as canonical 32-byte little-endian scalars, ready for masp_hip_verify_batch / masp_hip_verify_each: spends n x 7
+ *    (rk.u, rk.v, cv.u, cv.v, anchor, the nullifier multipacked into two 254-bit chunks), converts n x 3 (cv.u, cv.v, anchor), outputs
+ *    n x 5 (cv.u, cv.v, epk.u, epk.v, cmu).  Anchor and cmu are copied, not range-checked (the verifier's verdict 3 covers them).  The
+ *    rows of a description with a nonzero status are zeros.
+ *  - bvk (32 bytes) and one status byte per bundle:
+ *       0  bvk is valid
+ *       1  a description of the bundle has a nonzero status (bvk zeros)
+ *       2  an entry's value is i128::MIN: no absolute value (bvk zeros)
+ *       3  an entry's identifier has no generator (bvk zeros)
+ *    1 before 2 before 3; among the entries the first failing one decides.  An empty bundle has status 0 and the identity's encoding;
+ *    entries with the same identifier are independent.
+ * The result is deterministic.  Device: one lane per Jubjub encoding, per value-balance entry, per proof point and per bundle (KERNELS.md);
+ * proofs go through 2^16 at a time; the other arrays are resident for the call (about 100 bytes a point, 180 an entry).  Re-entrant next
+ * to proving and verification calls, on the context's second verifier stream under the RedJubjub calls' lock (one at a time per context);
+ * the call creates no stream; on a multi-device context it runs on the first device.
+ * masp_hip_check_bundles_last_timing — of the context's last call, from HIP events on its stream: ms[0] the host-to-device copies,
+ * ms[1] the kernels, ms[2] the device-to-host copies. */
+typedef struct masp_hip_bundle_check {
+    size_t n_bundles, n_spends, n_converts, n_outputs, n_balance;
+    const uint32_t* counts;                                                             /* n_bundles x 4 */
+    const uint8_t *spend_cv, *spend_anchor, *spend_nullifier, *spend_rk, *spend_zkproof;
+    const uint8_t *convert_cv, *convert_anchor, *convert_zkproof;
+    const uint8_t *output_cv, *output_cmu, *output_epk, *output_zkproof;
+    const uint8_t *balance_asset, *balance_value;                                       /* n_balance x 32, n_balance x 16 */
+    uint8_t *spend_status, *convert_status, *output_status;                             /* a byte per description */
+    uint8_t *spend_inputs, *convert_inputs, *output_inputs;                             /* n x 7 x 32, n x 3 x 32, n x 5 x 32 */
+    uint8_t *bvk, *bundle_status;                                                       /* n_bundles x 32, n_bundles */
+} masp_hip_bundle_check;
+int masp_hip_sapling_check_bundles(masp_hip_ctx* ctx, const masp_hip_bundle_check* args);
+int masp_hip_check_bundles_last_timing(masp_hip_ctx* ctx, double ms[3]);
+
 /* ---- Batch trial decryption of Sapling notes on the GPU ----
  * masp_hip_sapling_trial_decrypt <- the device half of masp_note_encryption::batch::try_note_decryption over SaplingDomain
  *    (masp_note_encryption/src/batch.rs:43-86): for each of the n_out x n_ivk (output, ivk) pairs the key agreement [8 ivk] epk, the KDF
@@ -600,5 +655,12 @@ MASP_HIP_STATIC_ASSERT(sizeof(masp_hip_r1cs) == 88 && offsetof(masp_hip_r1cs, a_
 MASP_HIP_STATIC_ASSERT(sizeof(masp_hip_options) == 76 && offsetof(masp_hip_options, window_bits_b2) == 72,
                        "masp_hip_options: struct_size + 18 int32 fields (appended-only: struct_size versions it)");
 MASP_HIP_STATIC_ASSERT(offsetof(masp_hip_options, hw_queues) == 60 && offsetof(masp_hip_options, digit_recoding) == 68, "masp_hip_options tail");
+MASP_HIP_STATIC_ASSERT(sizeof(masp_hip_bundle_check) == 224 && offsetof(masp_hip_bundle_check, counts) == 40, "masp_hip_bundle_check: five counts + 23 pointers");
+MASP_HIP_STATIC_ASSERT(offsetof(masp_hip_bundle_check, convert_cv) == 88 && offsetof(masp_hip_bundle_check, output_cv) == 112 &&
+                           offsetof(masp_hip_bundle_check, balance_asset) == 144,
+                       "masp_hip_bundle_check inputs");
+MASP_HIP_STATIC_ASSERT(offsetof(masp_hip_bundle_check, spend_status) == 160 && offsetof(masp_hip_bundle_check, spend_inputs) == 184 &&
+                           offsetof(masp_hip_bundle_check, bvk) == 208,
+                       "masp_hip_bundle_check results");
 #endif
 #endif

@@ -317,14 +317,18 @@ struct OnceTable : DevBuf<T> {
     }
 };
 
-// What the Jubjub entry points (k_redjubjub.hip: masp_hip_jubjub_msm, masp_hip_redjubjub_verify_batch, masp_hip_redjubjub_verify_each) keep
-// between calls.  They run next to proving calls on the verifier stream streams.vk[1], one at a time per context: `mu` guards every member
-// and is taken behind the context's.  The work buffers grow on demand and are kept.
+// What the Jubjub entry points (k_redjubjub.hip: masp_hip_jubjub_msm, masp_hip_redjubjub_verify_batch, masp_hip_redjubjub_verify_each;
+// k_bundle_check.hip: masp_hip_sapling_check_bundles) keep between calls.  They run next to proving calls on the verifier stream
+// streams.vk[1], one at a time per context: `mu` guards every member but the timing record and is taken behind the context's.  The work
+// buffers grow on demand and are kept.
 struct JubjubState {
     std::mutex mu;
     DevBuf<uint8_t> points, scalars, partial;
     DevBuf<int> status;
     DevBuf<uint32_t> out;
+    // the bundle pre-check: a call's arrays as they come, what its kernels hand each other, its results, and one chunk of proof bytes
+    DevBuf<uint8_t> bc_in, bc_work, bc_out, bc_proofs;
+    LastTiming<3> bc_timing;          // masp_hip_check_bundles_last_timing: upload, kernels, download
 };
 
 // What the wallet-side entry points of a device context keep between calls: the note scan (k_note_scan.hip), the compact note scan

@@ -1,4 +1,5 @@
 """ctypes binding of libmasp_hip.so (C ABI: include/masp_hip.h)."""
+import collections
 import ctypes as C
 import os
 
@@ -50,6 +51,43 @@ assert C.sizeof(JobStruct) == 120 and JobStruct.r.offset == 48 and JobStruct.aux
 AUX_CANONICAL, AUX_MONTGOMERY = 0, 1     # masp_hip_job::aux_form
 QUOTIENT_EVALUATION, QUOTIENT_COEFFICIENT = 0, 1     # masp_hip_ctx_set_quotient_form
 QUOTIENT_FUSED, QUOTIENT_SEPARATE = 0, 1             # masp_hip_ctx_set_quotient_schedule
+
+
+class BundleCheckStruct(C.Structure):
+    """masp_hip_bundle_check (include/masp_hip.h): the arrays of one masp_hip_sapling_check_bundles call"""
+    _fields_ = ([(f, C.c_size_t) for f in ("n_bundles", "n_spends", "n_converts", "n_outputs", "n_balance")] +
+                [(f, C.c_void_p) for f in ("counts", "spend_cv", "spend_anchor", "spend_nullifier", "spend_rk", "spend_zkproof",
+                                           "convert_cv", "convert_anchor", "convert_zkproof",
+                                           "output_cv", "output_cmu", "output_epk", "output_zkproof", "balance_asset", "balance_value",
+                                           "spend_status", "convert_status", "output_status", "spend_inputs", "convert_inputs", "output_inputs",
+                                           "bvk", "bundle_status")])
+
+
+assert C.sizeof(BundleCheckStruct) == 224 and BundleCheckStruct.counts.offset == 40 and BundleCheckStruct.bvk.offset == 208   # include/masp_hip.h asserts the same
+BundleCheckResult = collections.namedtuple("BundleCheckResult", "spend_status convert_status output_status spend_inputs convert_inputs output_inputs "
+                                                                "bvk bundle_status")
+
+
+def bundle_check_args(counts, spends, converts, outputs, balance):
+    """The struct of one check_bundles call over the caller's arrays -> (BundleCheckStruct, BundleCheckResult of zeroed numpy arrays the
+    struct points into, the input arrays to keep alive).  Arguments as Context.check_bundles takes them."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1, 4)
+    widths = ((32, 32, 32, 32, 192), (32, 32, 192), (32, 32, 32, 192), (32, 16))
+    groups = [[_u8(a, w) for a, w in zip(g, ws)] for g, ws in zip((spends, converts, outputs, balance), widths)]
+    assert all(len(g) == len(ws) for g, ws in zip(groups, widths))
+    n = [g[0].shape[0] for g in groups]
+    assert all(a.shape[0] == k for g, k in zip(groups, n) for a in g), "arrays of one kind differ in length"
+    nb = counts.shape[0]
+    res = BundleCheckResult(np.zeros(n[0], np.uint8), np.zeros(n[1], np.uint8), np.zeros(n[2], np.uint8), np.zeros((n[0], 7, 32), np.uint8),
+                            np.zeros((n[1], 3, 32), np.uint8), np.zeros((n[2], 5, 32), np.uint8), np.zeros((nb, 32), np.uint8), np.zeros(nb, np.uint8))
+    s = BundleCheckStruct()
+    s.n_bundles, s.n_spends, s.n_converts, s.n_outputs, s.n_balance = nb, n[0], n[1], n[2], n[3]
+    ptr = lambda a: a.ctypes.data if a.size else None       # noqa: E731  (an empty array goes as NULL: nothing of it is read)
+    s.counts = ptr(counts)
+    names = [f for f, _ in BundleCheckStruct._fields_[6:]]
+    for name, a in zip(names, [a for g in groups for a in g] + list(res)):
+        setattr(s, name, ptr(a))
+    return s, res, (counts, groups)
 
 
 def library_path():
@@ -174,6 +212,9 @@ def load_library():
         L.masp_hip_sapling_note_nullifiers.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.masp_hip_note_nullifiers_configure.argtypes = [vp, C.c_int]
         L.masp_hip_note_nullifiers_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
+    if hasattr(L, "masp_hip_sapling_check_bundles"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
+        L.masp_hip_sapling_check_bundles.argtypes = [vp, C.POINTER(BundleCheckStruct)]
+        L.masp_hip_check_bundles_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
     L.masp_hip_batch_upload.argtypes = [vp, sz, vp]
     L.masp_hip_batch_prove_resident.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_float)]
     L.masp_hip_batch_prove_resident_steps.argtypes = [vp, C.c_int, sz, vp, vp, C.POINTER(C.c_float)]
@@ -434,6 +475,28 @@ class Context:
             raise e
         self._check(rc)
         return out.tobytes()
+
+    # ---- the consensus pre-checks of a block's bundles on the GPU ----
+    def check_bundles(self, counts, spends, converts, outputs, balance):
+        """What BatchValidator.check_bundle decides per description, with the public inputs and binding verification keys, for all bundles
+        of a block in one call (masp_hip_sapling_check_bundles).  counts: uint32[n_bundles, 4], the spends, converts, outputs and
+        value-balance entries of each bundle; the items of a kind lie bundle after bundle in their arrays: spends = (cv, anchor, nullifier,
+        rk, zkproof), converts = (cv, anchor, zkproof), outputs = (cv, cmu, epk, zkproof), balance = (asset identifiers, values as 16-byte
+        little-endian two's-complement i128); 32 bytes an item but zkproof (192) and the values.  -> BundleCheckResult of numpy arrays:
+          spend_status, convert_status, output_status   uint8[n]: 0, or the first that applies of 1 cv does not decode, 2 rk / epk does not
+                                                        decode, 3 `Proof::read` refuses the proof, 4 cv has small order, 5 rk / epk has;
+          spend_inputs [n, 7, 32], convert_inputs [n, 3, 32], output_inputs [n, 5, 32]   the public inputs as canonical little-endian
+                                                        scalars (zeros where the status is not 0);
+          bvk [n_bundles, 32], bundle_status [n_bundles]   0 bvk is valid, 1 a description has a status, 2 a value is i128::MIN, 3 an
+                                                        identifier has no generator (bvk zeros for 1 - 3).
+        Counts that do not add up to the arrays' lengths raise MaspHipError (invalid argument)."""
+        s, res, keep = bundle_check_args(counts, spends, converts, outputs, balance)
+        self._check(self._L.masp_hip_sapling_check_bundles(self._h, C.byref(s)))
+        return res
+
+    def check_bundles_last_timing(self):
+        """(upload ms, kernel ms, download ms) of the last check_bundles call of this context, from HIP events on its stream"""
+        return self._timing(self._L.masp_hip_check_bundles_last_timing, 3)
 
     # ---- batch trial decryption of Sapling notes on the GPU ----
     def _scan_with_room(self, fn, args, widths, n_out, hit_capacity, tail=()):

@@ -95,6 +95,34 @@ def output_public_inputs(cv, cmu, epk):
     return list(H.point_uv(bytes(cv))) + list(H.point_uv(bytes(epk))) + [_int(cmu)]
 
 
+def _le32(x):
+    return x.to_bytes(32, "little") if isinstance(x, int) else bytes(x)
+
+
+def _device_shaped(bundle):
+    """Every field of the bundle has the length its wire encoding has (a scalar given as an int is below 2^256): BatchValidator.check_bundles
+    sends such a bundle to the device; any other goes through check_bundle."""
+    def raw(x, n=32):        # a point, a nullifier, a proof
+        return not isinstance(x, int) and len(bytes(x)) == n
+
+    def scalar(x):
+        return 0 <= x < 1 << 256 if isinstance(x, int) else len(bytes(x)) == 32
+    try:
+        return (all(raw(d.cv) and scalar(d.anchor) and raw(d.nullifier) and raw(d.rk) and raw(d.zkproof, 192) for d in bundle.spends) and
+                all(raw(d.cv) and scalar(d.anchor) and raw(d.zkproof, 192) for d in bundle.converts) and
+                all(raw(d.cv) and scalar(d.cmu) and raw(d.ephemeral_key) and raw(d.zkproof, 192) for d in bundle.outputs) and
+                all(raw(a) and int(v) == v for a, v in bundle.value_balance))
+    except (TypeError, ValueError):
+        return False
+
+
+def _rows_as_ints(a):
+    """uint8[n, k, 32] of little-endian scalars -> n lists of k ints"""
+    n, k = a.shape[0], a.shape[1]
+    data = a.tobytes()
+    return [[int.from_bytes(data[32 * (i * k + j):32 * (i * k + j) + 32], "little") for j in range(k)] for i in range(n)]
+
+
 class _Inner:
     """SaplingVerificationContextInner (verifier.rs:20-204): cv_sum and the consensus checks; the signature and proof checks are the
     caller's callbacks, as in the reference."""
@@ -178,10 +206,14 @@ class SaplingVerificationContext:
         return self._inner.final_check(value_balance, sighash, binding_sig, lambda vk, msg, sig: RJS.verify(vk, msg, bytes(sig), g))
 
 
+_EMPTY_BUNDLE = Bundle([], [], [], [], b"")     # what check_bundles sends in the place of a bundle that check_bundle decides
+
+
 class BatchValidator:
     """= BatchValidator (verifier/batch.rs:40-239) over one `hip.Context`: check_bundle runs the consensus checks on the host and queues
     proofs (per circuit) and signatures; validate verifies everything queued in one RedJubjub batch and one Groth16 batch per circuit on
-    the GPU.  Several validators may share a context and run in different threads."""
+    the GPU.  Several validators may share a context and run in different threads.  check_bundles is check_bundle over a block's bundles
+    with the per-description work in one device call; the two may be mixed."""
 
     def __init__(self, context):
         self._ctx = context
@@ -233,6 +265,57 @@ class BatchValidator:
                 return False
         return ctx.final_check(bundle.value_balance, sighash, bundle.binding_sig,
                                lambda vk, msg, sig: self._queue_sig(vk, sig, sighash, BINDING))
+
+    def check_bundles(self, bundles, sighashes):
+        """check_bundle over a whole block: one bool per bundle, and the validator's queues and marks exactly as check_bundle leaves them
+        bundle after bundle, with the per-description work (decoding cv / rk / epk, the small-order tests, `Proof::read`, the public
+        inputs, bvk) done for all bundles in ONE device call (Context.check_bundles).  The queues are then rebuilt from the statuses in
+        the reference's order.  A bundle with a field of the wrong length goes through check_bundle itself, in its place; a value outside
+        i128 is sent as i128::MIN, which is refused where check_bundle refuses it."""
+        bundles, sighashes = list(bundles), [bytes(s) for s in sighashes]
+        assert len(bundles) == len(sighashes)
+        if not bundles:
+            return []
+        on_device = [_device_shaped(b) for b in bundles]
+        sent = [b if dev else _EMPTY_BUNDLE for b, dev in zip(bundles, on_device)]
+        spends, converts, outputs = ([d for b in sent for d in getattr(b, k)] for k in ("spends", "converts", "outputs"))
+        entries = [(a, int(v)) for b in sent for a, v in b.value_balance]
+        join = lambda items, field: b"".join(_le32(getattr(d, field)) for d in items)      # noqa: E731
+        res = self._ctx.check_bundles(
+            [(len(b.spends), len(b.converts), len(b.outputs), len(b.value_balance)) for b in sent],
+            [join(spends, f) for f in ("cv", "anchor", "nullifier", "rk", "zkproof")],
+            [join(converts, f) for f in ("cv", "anchor", "zkproof")],
+            [join(outputs, f) for f in ("cv", "cmu", "ephemeral_key", "zkproof")],
+            [b"".join(bytes(a) for a, _ in entries),
+             b"".join((v if I128_MIN <= v <= I128_MAX else I128_MIN).to_bytes(16, "little", signed=True) for _, v in entries)])
+        inputs = [_rows_as_ints(a) for a in (res.spend_inputs, res.convert_inputs, res.output_inputs)]
+        status = [a.tolist() for a in (res.spend_status, res.convert_status, res.output_status)]
+        bundle_status, bvks = res.bundle_status.tolist(), res.bvk.tobytes()
+        at, verdicts = [0, 0, 0], []
+        for k, (bundle, sighash, dev) in enumerate(zip(bundles, sighashes, on_device)):
+            if not dev:
+                verdicts.append(self.check_bundle(bundle, sighash))
+                continue
+            self._bundles_added = True
+            start = self._queue_marks()
+            ok = True
+            for q, (kind, items) in enumerate((("spend", bundle.spends), ("convert", bundle.converts), ("output", bundle.outputs))):
+                first = at[q]
+                at[q] += len(items)
+                for i, d in enumerate(items, first):
+                    if not ok or status[q][i]:
+                        ok = False             # refused at this description: what came before stays queued, nothing after it is
+                        break
+                    if q == 0:
+                        self._queue_sig(d.rk, d.spend_auth_sig, sighash, SPEND_AUTH)
+                    self._queue_proof(kind, d.zkproof, inputs[q][i])
+            if ok and bundle_status[k] == 0:
+                self._queue_sig(bvks[32 * k:32 * k + 32], bundle.binding_sig, sighash, BINDING)
+            else:
+                ok = False
+            self._bundles.append((ok, start))
+            verdicts.append(ok)
+        return verdicts
 
     def validate(self, spend_vk, convert_vk, output_vk, rng=None):
         """batch.rs:201-239.  The vks are hip.GpuVerifyingKey objects; rng(k) -> k random bytes (default: secrets.token_bytes).  True when
