@@ -591,6 +591,40 @@ int masp_hip_sapling_note_nullifiers(masp_hip_ctx* ctx, size_t n, const uint8_t*
 int masp_hip_note_nullifiers_configure(masp_hip_ctx* ctx, int lanes_per_note);
 int masp_hip_note_nullifiers_last_timing(masp_hip_ctx* ctx, double ms[3]);
 
+/* ---- A conversion tree's leaves on the GPU: allowed conversions in batches ----
+ * masp_hip_sapling_allowed_conversions <- AllowedConversion::from(I128Sum) and AllowedConversion::cmu (masp_primitives/src/convert.rs:39-64,
+ * 86-118) for n_conv conversions.  The terms are in CSR form: conversion c owns the terms term_offsets[c] .. term_offsets[c + 1] - 1, a term
+ * an identifier (32 bytes) and a value (16 bytes, little-endian two's-complement i128).  For every conversion
+ *    generator = sum_j sign(v_j) [|v_j| as u64] G_j, G_j the asset generator of identifier j (cofactor not cleared), |v_j| as u64 the LOW
+ *                64 bits of the absolute value, as the reference's cast keeps them,
+ *    cmu       = the affine u of PedersenHash(NoteCommitment, the 256 bits of repr(generator)): the conversion tree's leaf.
+ * The terms are summed as given: equal identifiers are not merged, zeros are not dropped (the caller merges, as the reference's I128Sum
+ * does; with the truncation, merging before and after summing differ).  A conversion without terms has the identity as its generator.
+ * Result: status (n_conv bytes), generators_out (n_conv x 32, may be NULL: not downloaded) and cmus_out (n_conv x 32).  status[c] is 0, or
+ * 1: one of its terms' identifiers has no generator, or 2: no such term, but one of its terms' values is i128::MIN (which has no absolute
+ * value); it does not depend on the terms' order.  A conversion with status != 0 has 32 zero bytes in either output and changes neither the
+ * return code nor its neighbours' results.
+ * Requirements: term_offsets[0] = 0, non-decreasing, term_offsets[n_conv] = n_terms, n_conv <= 2^22, n_terms <= 2^24; they are checked on
+ * the host before any GPU work, and anything else, or a NULL array (generators_out apart; identifiers and values may be NULL with
+ * n_terms = 0), is MASP_HIP_E_INVALID_ARG with nothing written.  n_conv = 0: MASP_HIP_OK, no GPU work, no array is read.
+ * The device works through chunks cut at conversion boundaries, of at most 2^19 conversions and at most 2^20 terms (about 180 MB of term
+ * points and inputs); ONE conversion with more terms than a chunk holds is MASP_HIP_E_INVALID_ARG before any work.  A conversion's terms are
+ * added by the lanes of its group one after the other: there is no reduction across lane groups, a very long conversion is a serial loop.
+ * The result is deterministic, and the same for either number of lanes and any chunk size.  Re-entrant next to proving and verification
+ * calls; on the context's first verifier stream, under the lock of the note scans, the trees and the nullifiers (a context runs one of
+ * them at a time: they share the Pedersen table), no stream or hardware queue of its own; on a multi-device context on the first device.
+ * masp_host_allowed_conversions (include/masp_host.h) is the same on the host.
+ * masp_hip_allowed_conversions_configure - for measurements and tests, the bytes depend on none of it.  lanes_per_conversion: 1 or 8
+ * lanes add a conversion's points, 0 (the default) = by the number of conversions; chunk_conversions, chunk_terms: a
+ * chunk's limits, 0 = the defaults.  Other lane counts, or limits above the defaults: MASP_HIP_E_INVALID_ARG.
+ * masp_hip_allowed_conversions_last_timing - of the last such call of this context, summed over its chunks from HIP events on its stream:
+ * ms[0] the host-to-device copies, ms[1] the kernels, ms[2] the device-to-host copies. */
+int masp_hip_sapling_allowed_conversions(masp_hip_ctx* ctx, size_t n_conv, const uint64_t* term_offsets, size_t n_terms,
+                                         const uint8_t* identifiers, const uint8_t* values, uint8_t* status, uint8_t* generators_out,
+                                         uint8_t* cmus_out);
+int masp_hip_allowed_conversions_configure(masp_hip_ctx* ctx, int lanes_per_conversion, size_t chunk_conversions, size_t chunk_terms);
+int masp_hip_allowed_conversions_last_timing(masp_hip_ctx* ctx, double ms[3]);
+
 /* ---- measurement hooks (bench.py): device-resident workloads, HIP-event timing on the ctx stream ---- */
 /* Keeps `n` jobs' assignments resident in HBM; returns a handle (>= 0) or a negative error code. */
 int masp_hip_batch_upload(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs);

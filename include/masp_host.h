@@ -152,6 +152,14 @@ int masp_host_spend_leaf(const uint8_t ak[32], const uint8_t nsk[32], const uint
 int masp_host_allowed_conversion(size_t n, const uint8_t* identifiers, const uint8_t* values, uint8_t generator_out[32]);
 /* leaf of the convert tree (convert.rs:39-64) */
 int masp_host_convert_cmu(const uint8_t generator[32], uint8_t out32[32]);
+/* The two calls above for n_conv <= 2^22 conversions on `threads` host threads: the arguments and results of
+ * masp_hip_sapling_allowed_conversions (include/masp_hip.h) without the context.  Conversion c owns the terms term_offsets[c] ..
+ * term_offsets[c + 1] - 1 (term_offsets[0] = 0, non-decreasing, term_offsets[n_conv] = n_terms <= 2^24) of identifiers (n_terms x 32) and
+ * values (n_terms x 16, LE two's-complement i128), summed as given: nothing merged, no zero dropped.  status[c]: 0, or 1 a term's identifier
+ * has no generator, else 2 a term's value is i128::MIN; generators_out (n_conv x 32, may be NULL) and cmus_out (n_conv x 32) are then zeros
+ * and nothing else changes.  MASP_HOST_E_INVALID: offsets that break the rules, a NULL array that is read or written, a count too large. */
+int masp_host_allowed_conversions(size_t n_conv, const uint64_t* term_offsets, size_t n_terms, const uint8_t* identifiers,
+                                  const uint8_t* values, uint8_t* status, uint8_t* generators_out, uint8_t* cmus_out, int threads);
 
 /* ---- Sapling note encryption and trial decryption (masp_note_encryption, masp_primitives/src/sapling/note_encryption.rs).
  * A note plaintext is 596 bytes: lead byte (1: rcm follows, 2: a ZIP 212 rseed follows) | diversifier 11 | value u64 LE | asset identifier 32 |

@@ -13,3 +13,5 @@ from .note_encryption import (CompactShieldedOutput, Note, PaymentAddress, Rseed
                               try_sapling_compact_note_decryption, try_sapling_note_decryption)
 from . import merkle_tree  # noqa: F401
 from .merkle_tree import CommitmentTree, FrozenCommitmentTree, IncrementalWitness, MerklePath, advance, empty_root  # noqa: F401
+from . import convert  # noqa: F401
+from .convert import AllowedConversion  # noqa: F401

@@ -971,6 +971,73 @@ int masp_host_convert_cmu(const uint8_t generator[32], uint8_t out32[32]) {
     pedersen_hash({true, 0}, bytes_to_bits_le(b, 32)).to_affine().u.to_bytes(out32);
     return 0;
 }
+// The two calls above for n_conv conversions whose terms lie in CSR form, dealt to `threads` host threads sixteen at a time; what
+// masp_hip_sapling_allowed_conversions computes, and its other side in the tests.  The terms are summed as given (nothing merged, no zero
+// dropped).  status: 1 a term's identifier has no generator, else 2 a term's value is i128::MIN; the conversion's outputs then zeros.
+int masp_host_allowed_conversions(size_t n_conv, const uint64_t* term_offsets, size_t n_terms, const uint8_t* identifiers,
+                                  const uint8_t* values, uint8_t* status, uint8_t* generators_out, uint8_t* cmus_out, int threads) {
+    if (n_conv > ((size_t)1 << 22) || n_terms > ((size_t)1 << 24)) return MASP_HOST_E_INVALID;
+    if (n_conv == 0) return MASP_HOST_OK;
+    if (!term_offsets || !status || !cmus_out || (n_terms && (!identifiers || !values))) return MASP_HOST_E_INVALID;
+    if (term_offsets[0] != 0 || term_offsets[n_conv] != n_terms) return MASP_HOST_E_INVALID;
+    for (size_t c = 0; c < n_conv; ++c)
+        if (term_offsets[c] > term_offsets[c + 1]) return MASP_HOST_E_INVALID;
+    (void)pedersen_windows();   // the lazily built table, before the threads race for it
+    auto one = [&](size_t c) {
+        uint8_t* cmu = cmus_out + 32 * c;
+        memset(cmu, 0, 32);
+        if (generators_out) memset(generators_out + 32 * c, 0, 32);
+        JPoint acc = JPoint::identity();
+        int st = 0;
+        for (uint64_t i = term_offsets[c]; i < term_offsets[c + 1]; ++i) {
+            JPoint g;
+            if (!asset_generator(g, identifiers + 32 * i)) {
+                st = 1;
+                continue;
+            }
+            const uint8_t* v = values + 16 * i;
+            uint64_t lo = 0, hi = 0;
+            for (int b = 0; b < 8; ++b) {
+                lo |= (uint64_t)v[b] << (8 * b);
+                hi |= (uint64_t)v[8 + b] << (8 * b);
+            }
+            const bool negative = (hi >> 63) != 0;
+            if (negative) {
+                if (hi == (1ull << 63) && lo == 0) {   // i128::MIN
+                    if (!st) st = 2;
+                    continue;
+                }
+                lo = ~lo + 1;   // low 64 bits of -value
+            }
+            if (st) continue;   // (the other terms only decide between 1 and 2)
+            uint8_t k[32] = {0};
+            for (int b = 0; b < 8; ++b) k[b] = (uint8_t)(lo >> (8 * b));
+            const JPoint t = g.mul(k);
+            acc = acc.add(negative ? t.neg() : t);
+        }
+        if (st) return st;
+        uint8_t gb[32];
+        acc.to_bytes(gb);
+        if (generators_out) memcpy(generators_out + 32 * c, gb, 32);
+        pedersen_hash({true, 0}, bytes_to_bits_le(gb, 32)).to_affine().u.to_bytes(cmu);
+        return 0;
+    };
+    const int nt = std::max(1, std::min<int>(threads, 256));
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (;;) {
+            const size_t c0 = next.fetch_add(16);
+            if (c0 >= n_conv) return;
+            for (size_t c = c0; c < std::min(n_conv, c0 + 16); ++c) status[c] = (uint8_t)one(c);
+        }
+    };
+    std::vector<std::thread> pool;
+    if (n_conv >= 64)   // (a few conversions are not worth the threads' start)
+        for (int k = 1; k < nt; ++k) pool.emplace_back(work);
+    work();
+    for (auto& th : pool) th.join();
+    return MASP_HOST_OK;
+}
 // ---- Sapling note encryption and trial decryption (note_encryption.h) --------------------------------
 int masp_host_sapling_ka_agree(const uint8_t sk[32], const uint8_t p32[32], uint8_t out32[32]) {
     JPoint p;

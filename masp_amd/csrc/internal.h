@@ -332,10 +332,10 @@ struct JubjubState {
 };
 
 // What the wallet-side entry points of a device context keep between calls: the note scan (k_note_scan.hip), the compact note scan
-// (k_note_scan_compact.hip), the output recovery scan (k_out_recovery.hip), the commitment trees (k_merkle.hip) and the note nullifiers
-// (k_nullifier.hip).  One of these calls runs at a time per context: `mu` guards every member but the atomics and the timing records, and is
+// (k_note_scan_compact.hip), the output recovery scan (k_out_recovery.hip), the commitment trees (k_merkle.hip), the note nullifiers
+// (k_nullifier.hip) and the allowed conversions (k_conversion.hip).  One of these calls runs at a time per context: `mu` guards every member but the atomics and the timing records, and is
 // taken by WalletCall alone.  The scans alternate their chunks between the two verifier streams (streams.vk), each with a buffer set of its
-// own; the trees and the nullifiers run on streams.vk[0].  Every buffer grows on demand and is kept.
+// own; the trees, the nullifiers and the conversions run on streams.vk[0].  Every buffer grows on demand and is kept.
 struct WalletState {
     std::mutex mu;
     struct NoteScanSet {
@@ -354,7 +354,7 @@ struct WalletState {
     };
     NoteScanCompactSet nsc[2];
     DevBuf<uint8_t> nsc_ivks;         // the ivks as they come: stage 2's per-lane scalars
-    OnceTable<uint8_t> nsc_table;     // the Pedersen Niels table and G_ncr behind it (pedersen_table.h): the compact scan, the trees, the nullifiers
+    OnceTable<uint8_t> nsc_table;     // the Pedersen Niels table and G_ncr behind it (pedersen_table.h): the compact scan, the trees, the nullifiers, the conversions
     LastTiming<3> nsc_timing;         // masp_hip_note_scan_compact_last_timing: upload, stage 1, stage 2
     // output recovery: per set the rows as they come (cv, cmu, epk 32 bytes each, out_ciphertext 80), their eleven 16-byte columns, and the hits
     struct OutRecoverySet {
@@ -375,6 +375,12 @@ struct WalletState {
     DevBuf<uint8_t> nf_in, nf_state, nf_out;
     std::atomic<int> nf_lanes{0};     // masp_hip_note_nullifiers_configure: lanes per note, 0 = by the number of notes
     LastTiming<3> nf_timing;          // masp_hip_note_nullifiers_last_timing: upload, kernels, download
+    // the allowed conversions (k_conversion.hip), on nsc_table's Pedersen points: a chunk's offsets, identifiers and values as they come, the
+    // terms' points with their status bytes behind them, and generator | cmu | status
+    DevBuf<uint8_t> cv_in, cv_terms, cv_out;
+    std::atomic<int> cv_lanes{0};     // masp_hip_allowed_conversions_configure: lanes per conversion, 0 = by the number of conversions
+    std::atomic<size_t> cv_chunk_conv{0}, cv_chunk_terms{0};   // ... and a chunk's limits, 0 = the defaults
+    LastTiming<3> cv_timing;          // masp_hip_allowed_conversions_last_timing: upload, kernels, download
     // The end of a call that may have uploaded tables: one that failed with a HIP error cannot tell whether they arrived, so they are released
     // and the next call uploads them again; any other end confirms them.  A table of an earlier call is not marked and survives either way.
     void settle_tables(int rc) {

@@ -212,6 +212,10 @@ def load_library():
         L.masp_hip_sapling_note_nullifiers.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.masp_hip_note_nullifiers_configure.argtypes = [vp, C.c_int]
         L.masp_hip_note_nullifiers_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
+    if hasattr(L, "masp_hip_sapling_allowed_conversions"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
+        L.masp_hip_sapling_allowed_conversions.argtypes = [vp, sz, vp, sz, vp, vp, vp, vp, vp]
+        L.masp_hip_allowed_conversions_configure.argtypes = [vp, C.c_int, sz, sz]
+        L.masp_hip_allowed_conversions_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
     if hasattr(L, "masp_hip_sapling_check_bundles"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
         L.masp_hip_sapling_check_bundles.argtypes = [vp, C.POINTER(BundleCheckStruct)]
         L.masp_hip_check_bundles_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
@@ -652,6 +656,31 @@ class Context:
     def note_nullifiers_last_timing(self):
         """(upload ms, kernel ms, download ms) of the last note_nullifiers call of this context, HIP events summed over its chunks"""
         return self._timing(self._L.masp_hip_note_nullifiers_last_timing, 3)
+
+    # ---- a conversion tree's leaves on the GPU ----
+    def allowed_conversions(self, term_offsets, identifiers, values, want_generators=True):
+        """AllowedConversion::from and ::cmu for n_conv conversions on the GPU (masp_hip_sapling_allowed_conversions): conversion c owns the
+        terms term_offsets[c] .. term_offsets[c + 1] - 1 of identifiers (n_terms x 32) and values (n_terms x 16 bytes, little-endian i128, or
+        Python integers), summed as given -> (status uint8[n_conv], generators uint8[n_conv, 32] or None with want_generators=False: not
+        downloaded, cmus uint8[n_conv, 32]).  status: 0, or 1 an identifier without a generator, else 2 a value that is i128::MIN; such a
+        conversion's outputs are zeros.  host.allowed_conversions is the same on the host."""
+        from .host import allowed_conversion_args
+        off, ids, vals = allowed_conversion_args(term_offsets, identifiers, values)
+        n = max(off.shape[0] - 1, 0)
+        status, cmus = np.zeros(n, np.uint8), np.zeros((n, 32), np.uint8)
+        gens = np.zeros((n, 32), np.uint8) if want_generators else None
+        p = lambda a: _p(a) if a is not None and a.size else None
+        self._check(self._L.masp_hip_sapling_allowed_conversions(self._h, n, p(off), ids.shape[0], p(ids), p(vals), p(status), p(gens), p(cmus)))
+        return status, gens, cmus
+
+    def allowed_conversions_configure(self, lanes_per_conversion=0, chunk_conversions=0, chunk_terms=0):
+        """how many lanes add a conversion's points (1 or 8; 0 = by the number of conversions) and a chunk's limits (0 = the defaults,
+        nothing above them).  For measurements and tests: the bytes do not depend on it."""
+        self._check(self._L.masp_hip_allowed_conversions_configure(self._h, int(lanes_per_conversion), int(chunk_conversions), int(chunk_terms)))
+
+    def allowed_conversions_last_timing(self):
+        """(upload ms, kernel ms, download ms) of the last allowed_conversions call of this context, HIP events summed over its chunks"""
+        return self._timing(self._L.masp_hip_allowed_conversions_last_timing, 3)
 
     # ---- building blocks ----
     def msm_g1(self, bases, scalars):

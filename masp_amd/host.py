@@ -79,6 +79,8 @@ def load_library():
         L.masp_host_jubjub_sum.argtypes = [cp, cp, C.c_size_t, cp, cp]
         L.masp_host_spend_leaf.argtypes = [cp, cp, cp, cp, cp, u64, cp, cp]
         L.masp_host_allowed_conversion.argtypes = [C.c_size_t, cp, cp, cp]
+        if hasattr(L, "masp_host_allowed_conversions"):      # (an older build passed as MASP_HOST_LIBRARY lacks it)
+            L.masp_host_allowed_conversions.argtypes = [C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, vp, C.c_int]
         L.masp_host_sapling_ka_agree.argtypes = [cp, cp, cp]
         L.masp_host_diversifier_base.argtypes = [cp, cp]
         L.masp_host_kdf_sapling.argtypes = [cp, cp, cp]
@@ -571,6 +573,64 @@ def convert_cmu(generator):
     return out.raw
 
 
+def compact_size(n):
+    """zcash_encoding's CompactSize::write"""
+    if n < 253:
+        return bytes([n])
+    for lead, width in ((253, 2), (254, 4), (255, 8)):
+        if n < 1 << (8 * width):
+            return bytes([lead]) + n.to_bytes(width, "little")
+    raise ValueError("no CompactSize holds %d" % n)
+
+
+def read_compact_size(data, at=0):
+    """CompactSize::read at data[at:] -> (value, the offset behind it); ValueError for a short or non-canonical encoding"""
+    if len(data) <= at:
+        raise ValueError("CompactSize: no bytes left")
+    lead = data[at]
+    if lead < 253:
+        return lead, at + 1
+    width = {253: 2, 254: 4, 255: 8}[lead]
+    if len(data) < at + 1 + width:
+        raise ValueError("CompactSize: no bytes left")
+    n = int.from_bytes(data[at + 1:at + 1 + width], "little")
+    if n < (253, 1 << 16, 1 << 32)[lead - 253]:
+        raise ValueError("non-canonical CompactSize")
+    return n, at + 1 + width
+
+
+def allowed_conversion_args(term_offsets, identifiers, values):
+    """the arguments of either allowed_conversions as contiguous arrays: uint64[n_conv + 1], uint8[n_terms, 32], uint8[n_terms, 16].
+    values: n_terms x 16 bytes (bytes or a uint8 array), or a sequence of Python integers, written as little-endian i128."""
+    off = np.ascontiguousarray(term_offsets, dtype=np.uint64).reshape(-1)
+    if isinstance(identifiers, (bytes, bytearray, memoryview)):
+        identifiers = np.frombuffer(identifiers, dtype=np.uint8)
+    ids = np.ascontiguousarray(identifiers, dtype=np.uint8).reshape(-1, 32)
+    if isinstance(values, (bytes, bytearray, memoryview)):
+        values = np.frombuffer(values, dtype=np.uint8)
+    elif not isinstance(values, np.ndarray):
+        values = np.frombuffer(b"".join(int(v).to_bytes(16, "little", signed=True) for v in values), dtype=np.uint8)
+    vals = np.ascontiguousarray(values, dtype=np.uint8).reshape(-1, 16)
+    if ids.shape[0] != vals.shape[0]:
+        raise ValueError("allowed_conversions: %d identifiers, %d values" % (ids.shape[0], vals.shape[0]))
+    return off, ids, vals
+
+
+def allowed_conversions(term_offsets, identifiers, values, threads=None, want_generators=True):
+    """masp_host_allowed_conversions: generator and tree leaf of n_conv conversions on host threads (default: effective_cpus()).
+    Conversion c owns the terms term_offsets[c] .. term_offsets[c + 1] - 1, summed as given -> (status uint8[n_conv], generators
+    uint8[n_conv, 32] or None with want_generators=False, cmus uint8[n_conv, 32]).  status: 0, or 1 an identifier without a generator,
+    else 2 a value that is i128::MIN; such a conversion's outputs are zeros."""
+    off, ids, vals = allowed_conversion_args(term_offsets, identifiers, values)
+    n = max(off.shape[0] - 1, 0)
+    status, cmus = np.zeros(n, np.uint8), np.zeros((n, 32), np.uint8)
+    gens = np.zeros((n, 32), np.uint8) if want_generators else None
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    _check(load_library().masp_host_allowed_conversions(n, vp(off), ids.shape[0], vp(ids), vp(vals), vp(status), vp(gens), vp(cmus),
+                                                        int(threads or effective_cpus())))
+    return status, gens, cmus
+
+
 class AllowedConversion:
     """= masp_primitives::convert::AllowedConversion (/root/reference/masp_primitives/src/convert.rs:22-84,86-118).
 
@@ -594,9 +654,64 @@ class AllowedConversion:
             raise ValueError("invalid conversion")
         self.generator = out.raw
 
+    _cmu = None
+
+    @classmethod
+    def from_parts(cls, assets, generator, cmu=None):
+        """The conversion of an already merged value sum (a dict or pairs of identifier and value) whose generator, and leaf if given, are
+        already known — from allowed_conversions, which computes many in one call — without any native call."""
+        self = cls.__new__(cls)
+        self.assets = {_b(k): int(v) for k, v in sorted(dict(assets).items()) if int(v) != 0}
+        self.generator = _b(generator)
+        self._cmu = _b(cmu) if cmu is not None else None
+        return self
+
     def cmu(self):
         """u-coordinate of PedersenHash(NoteCommitment, repr(generator)) (convert.rs:39-64), 32 bytes LE."""
-        return convert_cmu(self.generator)
+        return self._cmu if self._cmu is not None else convert_cmu(self.generator)
+
+    def write(self):
+        """BorshSerialize (convert.rs:138-144): I128Sum::write (amount.rs:361-368: a CompactSize count, then identifier 32 | value i128 LE 16
+        per component in identifier order) and the generator's 32 bytes."""
+        return compact_size(len(self.assets)) + b"".join(k + v.to_bytes(16, "little", signed=True) for k, v in self.assets.items()) + \
+            self.generator
+
+    @staticmethod
+    def parse(data, check_identifiers=True):
+        """-> (merged assets, generator bytes) of a serialised conversion, as UncheckedAllowedConversion reads it (convert.rs:219-232): the
+        pairs summed as I128Sum::read sums them (amount.rs:345-357), the generator decoded.  ValueError: the bytes end early or go on, the
+        count is not a canonical CompactSize, a sum leaves the i128, the generator does not decode — and, with check_identifiers, an
+        identifier has no generator (a batch leaves that to its one call)."""
+        data = bytes(data)
+        n, at = read_compact_size(data)
+        if len(data) != at + 48 * n + 32:
+            raise ValueError("allowed conversion: %d bytes for %d components" % (len(data), n))
+        merged = {}
+        for i in range(n):
+            ident = data[at + 48 * i:at + 48 * i + 32]
+            if check_identifiers:
+                asset_generator(ident)
+            total = merged.get(ident, 0) + int.from_bytes(data[at + 48 * i + 32:at + 48 * i + 48], "little", signed=True)
+            if not -(1 << 127) <= total < (1 << 127):
+                raise ValueError("allowed conversion: the sum does not fit an i128")
+            merged[ident] = total
+        generator = data[at + 48 * n:]
+        point_uv(generator)
+        return {k: v for k, v in sorted(merged.items()) if v != 0}, generator
+
+    @classmethod
+    def read_unchecked(cls, data):
+        """UncheckedAllowedConversion's read (convert.rs:219-232): the generator is decoded and otherwise believed."""
+        return cls.from_parts(*cls.parse(data))
+
+    @classmethod
+    def read(cls, data):
+        """BorshDeserialize (convert.rs:146-160): the generator is recomputed from the value sum; ValueError if it is another."""
+        assets, generator = cls.parse(data)
+        conv = cls(assets)
+        if conv.generator != generator:
+            raise ValueError("allowed conversion: the generator is not the value sum's")
+        return conv
 
     commitment = cmu      # Node::from_scalar(self.cmu()) (convert.rs:80-84): the leaf of the conversion tree
 
