@@ -24,25 +24,55 @@ namespace masp {
 // scalars: n x 8 canonical little-endian limbs.  sorted entry = table row (j*n + i) | sign << 31, j = the window of the digit.
 // (Round 5 also had width-w NAF digits over a table per bit position here, as a template parameter of the iterator and its three kernels;
 // removed in round 6 — the tables it needs are beyond an XCD's TLB reach: EXPERIMENTS.md, profiles/r05_naf_digits_*.txt.)
+#ifndef MASP_HD
+#define MASP_HD __host__ __device__ __forceinline__  // (as device/field.hpp, which this header does not need otherwise)
+#endif
+// The eight words of one scalar in registers: ONE load of two uint4 serves the classification and the digit iterator.
+struct MsmScalar {
+    uint32_t w[8];
+};
+// scalar i of `scalars` where `valid`, else zero (class 0: no entry)
+__device__ __forceinline__ MsmScalar msm_load_scalar(const uint32_t* __restrict__ scalars, uint32_t i, bool valid) {
+    MsmScalar s;
+    uint4 lo = make_uint4(0u, 0u, 0u, 0u), hi = lo;
+    if (valid) {
+        const uint4* sp = reinterpret_cast<const uint4*>(scalars + (size_t)i * 8);
+        lo = sp[0];
+        hi = sp[1];
+    }
+    s.w[0] = lo.x, s.w[1] = lo.y, s.w[2] = lo.z, s.w[3] = lo.w;
+    s.w[4] = hi.x, s.w[5] = hi.y, s.w[6] = hi.z, s.w[7] = hi.w;
+    return s;
+}
+// the low word of (hi:lo) >> s, 0 <= s < 32
+MASP_HD uint32_t msm_funnel_shr(uint32_t hi, uint32_t lo, uint32_t s) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbit(hi, lo, s);
+#else
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> s);
+#endif
+}
+// The signed c-bit window digits of a scalar, lowest window first, from the scalar's words in registers: the digit is the low c bits, then
+// the 256-bit value moves right by c — seven funnel shifts (v_alignbit_b32) and one plain shift, every index a constant; zeros enter from
+// the top, which also gives the last window that starts below bit 256.  No memory is read.  (Before: the iterator fetched two words of the
+// scalar from memory per digit, a 16-window scalar 32 dependent loads with lanes 32 bytes apart.)  MASP_HD: the tests run it on the CPU.
 struct MsmDigitIter {
-    const uint32_t* sw;
-    uint32_t carry, mask, half, pos, j, twin_w;  // twin_w: 0, or W where the base set has doubled window rows (MsmGeom::twin)
-    int c;
-    __device__ __forceinline__ MsmDigitIter(const uint32_t* sw_, const MsmGeom& g)
-        : sw(sw_), carry(0), mask((1u << g.c) - 1u), half(1u << (g.c - 1)), pos(0), j(0), twin_w(g.twin ? (uint32_t)g.W : 0u), c(g.c) {}
-    // 32 bits of the scalar from bit `bit` on, zeros beyond bit 255 (re-read from L1/L2 instead of indexing a register array dynamically;
-    // the last window starts below bit 256)
-    __device__ __forceinline__ uint32_t bits(uint32_t bit) const {
-        const uint32_t w = bit >> 5, off = bit & 31u;
-        const uint64_t two = ((uint64_t)(w + 1 < 8 ? sw[w + 1] : 0u) << 32) | sw[w];
-        return (uint32_t)(two >> off);
+    uint32_t w[8];
+    uint32_t carry, mask, half, j, twin_w;  // twin_w: 0, or W where the base set has doubled window rows (MsmGeom::twin)
+    int c;                                  // 2 .. 16 (msm_sort_enqueue): a funnel shift by c never needs c = 0 or 32
+    MASP_HD MsmDigitIter(const MsmScalar& s, const MsmGeom& g)
+        : carry(0), mask((1u << g.c) - 1u), half(1u << (g.c - 1)), j(0), twin_w(g.twin ? (uint32_t)g.W : 0u), c(g.c) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) w[k] = s.w[k];
     }
     // The next digit: call W times, window after window; false = this window's digit is zero.  table: the window — or, with doubled
     // rows, W + the window for a magnitude of odd valuation, whose bucket is that of half the magnitude (msm_twin_bucket, msm_geom.h).
-    __device__ __forceinline__ bool next(uint32_t& table, uint32_t& bucket, uint32_t& neg) {
-        uint32_t v = (bits(pos) & mask) + carry;
+    MASP_HD bool next(uint32_t& table, uint32_t& bucket, uint32_t& neg) {
+        uint32_t v = (w[0] & mask) + carry;
+#pragma unroll
+        for (int k = 0; k < 7; ++k) w[k] = msm_funnel_shr(w[k + 1], w[k], (uint32_t)c);
+        w[7] >>= c;
         table = j++;
-        pos += (uint32_t)c;
         neg = 0;
         carry = 0;
         if (v > half) {
@@ -60,11 +90,9 @@ struct MsmDigitIter {
     }
 };
 // 0: zero, 1: one, 2: anything else
-__device__ __forceinline__ int msm_scalar_class(const uint32_t* sw) {
-    const uint4* sp = reinterpret_cast<const uint4*>(sw);
-    uint4 lo = sp[0], hi = sp[1];
-    uint32_t rest = lo.y | lo.z | lo.w | hi.x | hi.y | hi.z | hi.w;
-    if (rest == 0 && lo.x <= 1) return (int)lo.x;
+MASP_HD int msm_scalar_class(const MsmScalar& s) {
+    const uint32_t rest = s.w[1] | s.w[2] | s.w[3] | s.w[4] | s.w[5] | s.w[6] | s.w[7];
+    if (rest == 0 && s.w[0] <= 1) return (int)s.w[0];
     return 2;
 }
 // The entries of bucket 0 that the unit scalars of a wave become — the ONE classification k_msm_hist, k_msm_partition and k_msm_scatter
@@ -104,14 +132,14 @@ k_msm_hist(const uint32_t* __restrict__ scalars, size_t scalar_stride, uint32_t 
     const uint32_t per = msm_range_len(n, ng), lo = wg * per, hi = lo < n && lo + per < n ? lo + per : n;
     for (uint32_t base = lo; base < hi; base += MSM_SORT_THREADS) {
         const uint32_t i = base + tid;
-        const uint32_t* sw = scalars + (size_t)i * 8;
-        const int cls = i < hi ? msm_scalar_class(sw) : 0;
+        const MsmScalar sc = msm_load_scalar(scalars, i, i < hi);
+        const int cls = msm_scalar_class(sc);
         uint32_t unit_entry;
         const uint64_t units = msm_unit_lanes(cls, i, sub, unit_entry);
         if (cls != 2) {
             if (units && (uint32_t)__ffsll((unsigned long long)units) - 1u == (tid & 63u)) atomicAdd(&msm_lds[0], (uint32_t)__popcll(units));
         } else {
-            MsmDigitIter it(sw, g);
+            MsmDigitIter it(sc, g);
             for (int j = 0; j < g.W; ++j) {
                 uint32_t table, bucket, neg;
                 if (it.next(table, bucket, neg)) atomicAdd(&msm_lds[bucket], 1u);
@@ -246,8 +274,8 @@ k_msm_scatter(const uint32_t* __restrict__ scalars, size_t scalar_stride, uint32
     const uint32_t per = msm_range_len(n, ng), lo = wg * per, hi = lo < n && lo + per < n ? lo + per : n;
     for (uint32_t base = lo; base < hi; base += MSM_SORT_THREADS) {
         const uint32_t i = base + tid;
-        const uint32_t* sw = scalars + (size_t)i * 8;
-        const int cls = i < hi ? msm_scalar_class(sw) : 0;
+        const MsmScalar sc = msm_load_scalar(scalars, i, i < hi);
+        const int cls = msm_scalar_class(sc);
         uint32_t unit_entry;
         const uint64_t units = msm_unit_lanes(cls, i, sub, unit_entry);
         if (units) {
@@ -259,7 +287,7 @@ k_msm_scatter(const uint32_t* __restrict__ scalars, size_t scalar_stride, uint32
             if ((units >> (tid & 63u)) & 1ull) sorted[first + (uint32_t)__popcll(units & ((1ull << (tid & 63u)) - 1ull))] = unit_entry;
         }
         if (cls == 2) {
-            MsmDigitIter it(sw, g);
+            MsmDigitIter it(sc, g);
             for (int j = 0; j < g.W; ++j) {
                 uint32_t table, bucket, neg;
                 if (it.next(table, bucket, neg)) sorted[atomicAdd(&msm_lds[bucket], 1u)] = (table * n + i) | (neg << 31);
@@ -273,7 +301,7 @@ k_msm_scatter(const uint32_t* __restrict__ scalars, size_t scalar_stride, uint32
 // k_msm_scatter writes every entry on its own: a wave's 64 entries go to 64 unrelated buckets, i.e. 64 four-byte writes
 // into 64 different lines — the kernel is bound by DRAM read-modify-write of partial lines (10.4 ms per 128-proof batch for
 // 1.76 GB of payload).  Here the same entries reach their places in two steps that only ever write runs:
-//   k_msm_partition  (one workgroup per scalar range)   entries -> COARSE bins of 128 buckets.  A tile of 1024 scalars is
+//   k_msm_partition  (one workgroup per scalar range)   entries -> COARSE bins of 128 buckets.  A tile of MSM_PART_TILE scalars is
 //                    sorted by bin inside LDS first (count, scan, place), then copied out bin by bin: runs of ~64 entries.
 //   k_msm_bucketize  (one workgroup per proof and bin)  the bin's entries -> their buckets, again through an LDS-sorted
 //                    tile of 4096 entries: runs of ~32 entries.
@@ -281,7 +309,11 @@ k_msm_scatter(const uint32_t* __restrict__ scalars, size_t scalar_stride, uint32
 // 2^24 rows (`wide`: more than a million points on 16 windows), the 7 bits travel in a byte array of their own
 // (`tmpf`, next to `tmp`) and the word keeps 31 bits for the row.
 static constexpr uint32_t MSM_FINE_LOG = 7, MSM_FINE = 1u << MSM_FINE_LOG;
-static constexpr uint32_t MSM_PART_TILE = 1024;   // scalars per tile of k_msm_partition (= threads)
+// scalars per tile of k_msm_partition (= threads).  512, not 1024: about 51 KB of LDS at W = 16, and with the register cap below two workgroups
+// share a CU, so that one's digits overlap the other's barrier phases (measured: MEASUREMENTS.md "Sort: digits from registers").
+static constexpr uint32_t MSM_PART_TILE = 512;
+static_assert(MSM_PART_TILE >= 256 && MSM_PART_TILE % 64 == 0 && MSM_PART_TILE * 32 <= (1u << 16),
+              "k_msm_partition: msm_small_scan and the bins' cursors take 256 lanes, a range is whole waves, an entry's rank inside a tile 16 bits");
 static constexpr uint32_t MSM_BKT_TILE = 4096;    // entries per tile of k_msm_bucketize
 
 // crel[p][wg][B] = entries of bin B that come from earlier scalar ranges = sum over the bin's buckets of rel[p][wg][b].  One WAVE per
@@ -332,7 +364,7 @@ __device__ __forceinline__ void msm_small_scan(const uint32_t* cnt, uint32_t* of
         if (tid == 255) *total = base + x;
     }
 }
-__global__ void __launch_bounds__(1024)
+__global__ void __launch_bounds__(MSM_PART_TILE, 4)  // four waves per SIMD (at most 128 VGPRs): two workgroups of eight waves on a CU
 k_msm_partition(const uint32_t* __restrict__ scalars, size_t scalar_stride, uint32_t n, MsmGeom g, uint32_t ng, MsmSubset sub, const uint32_t* __restrict__ crel,
                 const uint32_t* __restrict__ start /* packed offsets: MsmSortBuf::dense */, uint32_t* __restrict__ tmp, uint8_t* __restrict__ tmpf,
                 uint32_t wide) {
@@ -358,15 +390,15 @@ k_msm_partition(const uint32_t* __restrict__ scalars, size_t scalar_stride, uint
         if (tid < nbins) cnt[tid] = 0;
         __syncthreads();
         const uint32_t i = base + tid;
-        const uint32_t* sw = scalars + (size_t)i * 8;
-        const int cls = i < hi ? msm_scalar_class(sw) : 0;
+        const MsmScalar sc = msm_load_scalar(scalars, i, i < hi);
+        const int cls = msm_scalar_class(sc);
         uint32_t unit_entry;
         const uint64_t ones = msm_unit_lanes(cls, i, sub, unit_entry);  // the lanes with an entry of bucket 0 of their own: unit scalars, block leaders
         const bool unit = (ones >> (tid & 63u)) & 1ull;
         const int leader = ones ? __ffsll((unsigned long long)ones) - 1 : -1;
         // ONE pass over the digits of a tile: the counting atomic already hands out the entry's rank inside its bin, the entry
         // and (rank, bin, low bucket bits) wait in registers for the scan of the counts (the digits were extracted and counted twice before)
-        uint32_t ent[32], key[32];  // key: rank (16 bits: at most 1024 x 32 entries per tile) | bin << 16 | low bucket bits << 24
+        uint32_t ent[32], key[32];  // key: rank (16 bits: at most MSM_PART_TILE x 32 entries per tile) | bin << 16 | low bucket bits << 24
         uint32_t unit_rank = 0;
         if (ones) {  // unit scalars: table 0, bucket 0, positive
             if ((int)(tid & 63u) == leader) unit_rank = atomicAdd(&cnt[0], (uint32_t)__popcll(ones));
@@ -375,7 +407,7 @@ k_msm_partition(const uint32_t* __restrict__ scalars, size_t scalar_stride, uint
 #pragma unroll
         for (int j = 0; j < 32; ++j) key[j] = 0xffffffffu;
         if (cls == 2) {
-            MsmDigitIter it(sw, g);
+            MsmDigitIter it(sc, g);
 #pragma unroll
             for (int j = 0; j < 32; ++j) {
                 if (j < g.W) {

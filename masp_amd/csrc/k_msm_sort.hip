@@ -6,6 +6,11 @@
 
 namespace masp {
 
+// LDS of k_msm_partition: the bins' counters, and per staged entry `entry_bytes` (a word and its bin's byte; wide: one more byte) for a tile of
+// W windows — within the 160 KiB of a CU, and at most 30 windows (the registers a lane keeps its tile's entries in)
+static constexpr int PART_FIXED = 4 * (4 * 256 + 8);
+static constexpr int part_windows_max(int entry_bytes) { return std::min(30, (160 * 1024 - PART_FIXED) / ((int)MSM_PART_TILE * entry_bytes)); }
+
 int msm_sort_enqueue(hipStream_t s, uint32_t n, const MsmGeom& g, MsmSortBuf& sb, const uint32_t* d_scalars, size_t scalar_stride,
                                    uint32_t np, uint32_t pad_log, const MsmSubset& sub) {
     static_assert((1u << 15) / MSM_SCAN_BLOCK <= 64, "k_msm_offsets_scan_b: a wave's lanes fetch the block totals");
@@ -39,14 +44,13 @@ int msm_sort_enqueue(hipStream_t s, uint32_t n, const MsmGeom& g, MsmSortBuf& sb
     // ... and the second pass is one workgroup per (proof, coarse bin): with too few of them (a lone proof's b_g2 on 8-bit windows: ONE,
     // 0.57 ms for 600 000 entries) the single-pass scatter over the scalar ranges is the shorter chain
     const uint32_t wide = MsmSortBuf::msm_rows_wide(rows) ? 1u : 0u;  // the low bucket bits of an entry in `tmpf` instead of the entry word
-    // LDS of the first pass: the bins' counters + per staged entry a word and a byte (its bin), wide: one more byte — of the 160 KiB of a CU
-    const int part_entry = wide ? 6 : 5, part_fixed = 4 * (4 * 256 + 8), part_w_max = std::min(30, (160 * 1024 - part_fixed) / ((int)MSM_PART_TILE * part_entry));
+    const int part_entry = wide ? 6 : 5, part_w_max = part_windows_max(part_entry);
     const bool two_pass = nb >= MSM_FINE && g.W <= part_w_max && (uint64_t)(nb >> MSM_FINE_LOG) * np >= 8;
-    const int part_lds = part_fixed + part_entry * (int)MSM_PART_TILE * g.W;
+    const int part_lds = PART_FIXED + part_entry * (int)MSM_PART_TILE * g.W;
     static PerDeviceOnce once;
     const bool lds_ok = once([] {
         int bytes = 4 << 15;
-        const int part_bytes = 4 * (4 * 256 + 8) + 5 * (int)MSM_PART_TILE * 30;  // = the largest part_lds below (6 x 25 = 5 x 30)
+        const int part_bytes = PART_FIXED + (int)MSM_PART_TILE * std::max(5 * part_windows_max(5), 6 * part_windows_max(6));  // the largest part_lds above
         return hipFuncSetAttribute((const void*)k_msm_hist, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess &&
                hipFuncSetAttribute((const void*)k_msm_scatter, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess &&
                hipFuncSetAttribute((const void*)k_msm_partition, hipFuncAttributeMaxDynamicSharedMemorySize, part_bytes) == hipSuccess;
