@@ -38,7 +38,7 @@ extern "C" {
 #define MASP_HIP_E_PARAMS_SHAPE 3         /* query lengths disagree with the circuit (SURVEY.md App. C invariants) */
 #define MASP_HIP_E_NO_DEVICE 4            /* no gfx950 device / HIP extension unusable — there is NO CPU fallback */
 #define MASP_HIP_E_HIP 5                  /* HIP runtime error (see masp_hip_last_error) */
-#define MASP_HIP_E_UNEXPECTED_IDENTITY 6  /* delta_g1 / delta_g2 is the identity (bellperson SynthesisError::UnexpectedIdentity) */
+#define MASP_HIP_E_UNEXPECTED_IDENTITY 6  /* delta_g1 / delta_g2 is the identity (bellperson SynthesisError::UnexpectedIdentity); toxic waste that would make h so */
 #define MASP_HIP_E_NOT_LOADED 7           /* circuit slot empty */
 #define MASP_HIP_E_SCALAR_RANGE 8         /* a scalar >= r was supplied */
 #define MASP_HIP_E_POINT_ENCODING 9       /* a Jubjub point encoding does not decode (JPoint::from_bytes, ZIP 216 rules) */
@@ -309,7 +309,10 @@ int masp_hip_prove_batch(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs, 
  * written in the bellman Parameters wire format.  Mirrors bellperson `generate_random_parameters`, which the
  * reference's benches call (/root/reference/masp_proofs/benches/sapling.rs:24-36); needed because the real
  * MPC parameters cannot be downloaded here.  *out_len receives the size; if cap is too small nothing is
- * written and MASP_HIP_E_INVALID_ARG is returned (upper bound: masp_hip_parameters_max_size). */
+ * written and MASP_HIP_E_INVALID_ARG is returned (upper bound: masp_hip_parameters_max_size).
+ * MASP_HIP_E_UNEXPECTED_IDENTITY if gamma or delta is 0, or if tau lies on the circuit's evaluation domain
+ * (tau^m = 1 for m = 2^ceil(log2(n_constraints + n_inputs)); tau = 1 and tau = r - 1 always do): Z(tau) = 0
+ * there, so every h point would be the identity, which masp_hip_circuit_load and bellman both refuse. */
 int masp_hip_generate_parameters(masp_hip_ctx* ctx, const masp_hip_r1cs* cs, const uint8_t toxic[160], uint8_t* out, size_t cap,
                                  size_t* out_len);
 size_t masp_hip_parameters_max_size(const masp_hip_r1cs* cs);

@@ -210,6 +210,15 @@ int masp_hip_circuit_load(masp_hip_ctx* ctx, uint32_t slot, const uint8_t* param
     // length invariants
     if (L.n_ic != cs->n_inputs || L.n_h < C->m - 1 || L.n_l != cs->n_aux || L.n_a != C->na || L.n_b1 != C->nbq || L.n_b2 != C->nbq)
         return call.done(MASP_HIP_E_PARAMS_SHAPE);
+    {
+        // gamma_g2 and ic are the verifier's: no table is built from them, but a file whose encoding of them bellman's `Parameters::read`
+        // refuses is refused here too (at most 8 + 1 points: decoded on the host).  Infinity is legal in both.
+        G2Affine gamma;
+        G1Affine ic;
+        int st = g2_read_uncompressed(L.gamma_g2, gamma);
+        for (uint32_t i = 0; i < L.n_ic; ++i) st |= g1_read_uncompressed(L.ic + 96 * (size_t)i, ic);
+        if (st & (PT_BAD_FLAGS | PT_NOT_CANONICAL)) return call.done(MASP_HIP_E_PARAMS_FORMAT);
+    }
     int rc;
     if ((rc = C->a_var.upload(a_var.data(), a_var.size(), s)) || (rc = C->b_var.upload(b_var.data(), b_var.size(), s))) return call.done(rc);
     // static R1CS -> device (coefficients to Montgomery form)

@@ -64,7 +64,7 @@ const char* masp_hip_strerror(int code) {
         case MASP_HIP_E_PARAMS_SHAPE: return "Parameters do not match the circuit shape";
         case MASP_HIP_E_NO_DEVICE: return "no usable HIP device (there is no CPU fallback)";
         case MASP_HIP_E_HIP: return "HIP runtime error";
-        case MASP_HIP_E_UNEXPECTED_IDENTITY: return "delta is the identity (UnexpectedIdentity)";
+        case MASP_HIP_E_UNEXPECTED_IDENTITY: return "delta is the identity, or the toxic waste would put the identity into h (UnexpectedIdentity)";
         case MASP_HIP_E_NOT_LOADED: return "circuit slot is empty";
         case MASP_HIP_E_SCALAR_RANGE: return "scalar is not a canonical field element";
         case MASP_HIP_E_POINT_ENCODING: return "a Jubjub point encoding does not decode";

@@ -98,6 +98,9 @@ int masp_hip_generate_parameters(masp_hip_ctx* ctx, const masp_hip_r1cs* cs, con
     for (uint32_t i = logm; i < 32; ++i) omega = fe_sqr(omega);
     uint32_t em[2] = {(uint32_t)m, (uint32_t)((uint64_t)m >> 32)};
     Fr z = fe_sub(fe_pow(tau, em, 2), fe_one<FrCfg>());
+    // tau on the domain: Z(tau) = 0, every h point would be the identity (which the loader and bellman refuse inside a query), and the
+    // closed formula below has no value there
+    if (fe_is_zero(z)) return call.done(MASP_HIP_E_UNEXPECTED_IDENTITY);
     Fr z_over_m = fe_mul(z, fe_inv(fr_from_u64_mont(m)));
     Fr dinv = fe_inv(delta), ginv = fe_inv(gamma);
     int rc;
