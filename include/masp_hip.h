@@ -628,6 +628,45 @@ int masp_hip_sapling_allowed_conversions(masp_hip_ctx* ctx, size_t n_conv, const
 int masp_hip_allowed_conversions_configure(masp_hip_ctx* ctx, int lanes_per_conversion, size_t chunk_conversions, size_t chunk_terms);
 int masp_hip_allowed_conversions_last_timing(masp_hip_ctx* ctx, double ms[3]);
 
+/* ---- Output descriptions without their proofs on the GPU: cv, cmu, epk and the two ciphertexts in batches ----
+ * masp_hip_sapling_build_outputs <- what SaplingOutputInfo::build (masp_primitives/src/transaction/components/sapling/builder.rs:533-575)
+ * puts around an Output proof, for n outputs.  The call draws no randomness: the caller supplies every random value, and the result is a
+ * function of the inputs.  Per output:
+ *    rcm = the 32 bytes of rseeds (lead byte 1) | PRF^expand(rseed, [4]) mod r_J (lead byte 2)            (Note::rcm),
+ *    esk = the 32 bytes of esks (lead byte 1) | PRF^expand(rseed, [5]) mod r_J (lead byte 2)              (Note::derive_esk),
+ *    cv  = what masp_host_value_commitment(id, value, rcv) returns, cmu = what masp_host_note_cmu(id, value, diversifier, pk_d, rcm) returns,
+ *    epk = [esk] g_d,
+ *    enc_ciphertext (612 bytes) = AEAD(KDF([8 esk] pk_d, epk), lead | d | value | id | rseed | memo): masp_host_sapling_note_encrypt,
+ *    out_ciphertext (80 bytes) = AEAD(PRF^ock(ovk, cv, cmu, epk), pk_d | esk) with an ovk, or AEAD(r[0:32], r[32:96]) of the output's 96
+ *    bytes of out_randoms without one (the ovk = bottom case of encrypt_outgoing_plaintext).
+ * asset_identifiers, pk_ds, rseeds, esks, rcvs, ovks: n x 32; diversifiers: n x 11; values, lead_bytes: n; memos: n x 512; ovk_flags: n,
+ * 0 = the ovk is absent; out_randoms: n x 96, read only where the ovk is absent; esks are read only where the lead byte is 1.
+ * May be NULL: memos (every memo is the empty memo, 0xf6 then zeros, and nothing is uploaded for it), ovk_flags (every ovk is present),
+ * out_randoms when no flag is 0, esks when no lead byte is 1; these conditions are checked on the host before any GPU work.
+ * Result: status (n bytes), cvs_out, cmus_out, epks_out (n x 32), encs_out (n x 612), couts_out (n x 80).  status[i] is 0, or the first check
+ * that fails, in this order: 1 the asset identifier has no generator, 2 the diversifier has no g_d, 3 pk_d is not the canonical encoding of
+ * a curve point, 4 the lead byte is neither 1 nor 2, or lead byte 1 with rcm >= r_J (1 to 4 as in masp_hip_sapling_note_nullifiers),
+ * 5 lead byte 1 with esk >= r_J, 6 rcv >= r_J.  An output with status != 0 has zeros in all five outputs and changes neither the return
+ * code nor its neighbours' results.  A zero esk is NOT refused, as on the host, and the subgroup membership of pk_d is NOT tested, as in
+ * the nullifier call: it is decoded, canonical and on the curve, and the bytes encrypted are the bytes given.
+ * n <= 2^20 a call; n = 0: MASP_HIP_OK, no GPU work, no array is read.  Any other NULL array, or n > 2^20: MASP_HIP_E_INVALID_ARG with
+ * nothing written.  The device works through chunks of at most 2^16 outputs (about 225 MB of inputs, state and ciphertexts), one after the
+ * other.  The result is deterministic and the same for any chunk size.  Re-entrant next to proving and verification calls; on the context's
+ * first verifier stream, under the lock of the note scans, the trees, the nullifiers and the conversions (a context runs one of them at a
+ * time: they share the Pedersen and nullifier tables), no stream or hardware queue of its own; on a multi-device context on the first device.
+ * masp_host_sapling_build_outputs (include/masp_host.h) is the same on the host.
+ * masp_hip_build_outputs_configure - chunk_outputs: outputs per chunk, 0 = the default; for measurements and tests, the bytes do not
+ * depend on it.  Values above the default: MASP_HIP_E_INVALID_ARG.
+ * masp_hip_build_outputs_last_timing - of the last such call of this context, summed over its chunks from HIP events on its stream:
+ * ms[0] the host-to-device copies, ms[1] the kernels, ms[2] the device-to-host copies. */
+int masp_hip_sapling_build_outputs(masp_hip_ctx* ctx, size_t n, const uint8_t* asset_identifiers, const uint64_t* values,
+                                   const uint8_t* diversifiers, const uint8_t* pk_ds, const uint8_t* lead_bytes, const uint8_t* rseeds,
+                                   const uint8_t* esks, const uint8_t* rcvs, const uint8_t* memos, const uint8_t* ovks, const uint8_t* ovk_flags,
+                                   const uint8_t* out_randoms, uint8_t* status, uint8_t* cvs_out, uint8_t* cmus_out, uint8_t* epks_out,
+                                   uint8_t* encs_out, uint8_t* couts_out);
+int masp_hip_build_outputs_configure(masp_hip_ctx* ctx, size_t chunk_outputs);
+int masp_hip_build_outputs_last_timing(masp_hip_ctx* ctx, double ms[3]);
+
 /* ---- measurement hooks (bench.py): device-resident workloads, HIP-event timing on the ctx stream ---- */
 /* Keeps `n` jobs' assignments resident in HBM; returns a handle (>= 0) or a negative error code. */
 int masp_hip_batch_upload(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs);

@@ -126,6 +126,19 @@ int masp_host_note_cmu(const uint8_t id[32], uint64_t value, const uint8_t diver
 int masp_host_sapling_note_nullifiers(size_t n, const uint8_t* asset_identifiers, const uint64_t* values, const uint8_t* diversifiers,
                                       const uint8_t* pk_ds, const uint8_t* lead_bytes, const uint8_t* rseeds, const uint8_t* nks,
                                       const uint64_t* positions, uint8_t* status, uint8_t* cmus_out, uint8_t* nfs_out, int threads);
+/* Output descriptions without their proofs (SaplingOutputInfo::build of masp_primitives/src/transaction/components/sapling/builder.rs) for
+ * n <= 2^20 outputs on `threads` host threads: the arguments and results of masp_hip_sapling_build_outputs (include/masp_hip.h) without the
+ * context, composed from masp_host_value_commitment, masp_host_note_cmu, masp_host_sapling_note_encrypt, masp_host_prf_ock and
+ * masp_host_sapling_encrypt_outgoing.  No randomness is drawn.  memos, ovk_flags, out_randoms (no flag is 0) and esks (no lead byte is 1)
+ * may be NULL, as there.  status[i]: 0, or the first check that fails: 1 the asset identifier has no generator, 2 the diversifier has no g_d,
+ * 3 pk_d does not decode, 4 the lead byte is neither 1 nor 2 or rcm >= r_J, 5 lead byte 1 with esk >= r_J, 6 rcv >= r_J; the output's five
+ * outputs are then zeros and nothing else changes.  A zero esk is not refused; pk_d's subgroup membership is not tested.
+ * MASP_HOST_E_INVALID: any other NULL array with n > 0, n > 2^20; nothing is written. */
+int masp_host_sapling_build_outputs(size_t n, const uint8_t* asset_identifiers, const uint64_t* values, const uint8_t* diversifiers,
+                                    const uint8_t* pk_ds, const uint8_t* lead_bytes, const uint8_t* rseeds, const uint8_t* esks,
+                                    const uint8_t* rcvs, const uint8_t* memos, const uint8_t* ovks, const uint8_t* ovk_flags,
+                                    const uint8_t* out_randoms, uint8_t* status, uint8_t* cvs_out, uint8_t* cmus_out, uint8_t* epks_out,
+                                    uint8_t* encs_out, uint8_t* couts_out, int threads);
 int masp_host_merkle_hash(unsigned depth, const uint8_t lhs[32], const uint8_t rhs[32], uint8_t out32[32]);
 /* empty_root(0..32) of the commitment tree, 33 x 32 bytes: the uncommitted leaf 1 and the roots of the empty subtrees above it */
 void masp_host_merkle_empty_roots(uint8_t out[33 * 32]);

@@ -157,6 +157,26 @@ MASP_HD JExt nf_commit_partial(const NfState& st, const JNiels* ped, const JNiel
     return nf_table_sum(r, ncr, NF_NCR_WINDOWS, st.rcm, lane, lanes);   // (the digits straight from the state: no indexed array in registers)
 }
 
+#if defined(__HIPCC__)
+// the sum of the L partial sums of a lane group (L a power of two, groups aligned in the wave), in every lane of the group; device
+// only: the kernels of k_nullifier.hip and k_output_build.hip fold with it
+template <int L>
+__device__ __forceinline__ JExt nf_fold(JExt r) {
+    for (int m = 1; m < L; m <<= 1) {
+        JExt o;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            o.U.v[k] = __shfl_xor(r.U.v[k], m);
+            o.V.v[k] = __shfl_xor(r.V.v[k], m);
+            o.Z.v[k] = __shfl_xor(r.Z.v[k], m);
+            o.T.v[k] = __shfl_xor(r.T.v[k], m);
+        }
+        r = jj_add(r, o);
+    }
+    return r;
+}
+#endif
+
 // the folded sum is cm: kept for the nullifier, and its affine u is cmu
 MASP_HD void nf_commit_finish(NfState& st, const JExt& cm, uint32_t cmu[8]) {
     st.cm = cm;

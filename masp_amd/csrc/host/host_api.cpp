@@ -1207,4 +1207,90 @@ int masp_host_sapling_try_output_recovery_batch(size_t n_ovk, const uint8_t* ovk
     for (auto& t : pool) t.join();
     return MASP_HOST_OK;
 }
+// SaplingOutputInfo::build without the proof for n outputs, dealt to `threads` host threads sixteen at a time; what
+// masp_hip_sapling_build_outputs computes, and its other side in the tests.  Composed from what the one-output calls are made of:
+// value_commitment, note_commitment, note_encrypt, prf_ock, encrypt_outgoing.
+int masp_host_sapling_build_outputs(size_t n, const uint8_t* asset_identifiers, const uint64_t* values, const uint8_t* diversifiers,
+                                    const uint8_t* pk_ds, const uint8_t* lead_bytes, const uint8_t* rseeds, const uint8_t* esks,
+                                    const uint8_t* rcvs, const uint8_t* memos, const uint8_t* ovks, const uint8_t* ovk_flags,
+                                    const uint8_t* out_randoms, uint8_t* status, uint8_t* cvs_out, uint8_t* cmus_out, uint8_t* epks_out,
+                                    uint8_t* encs_out, uint8_t* couts_out, int threads) {
+    if (n > ((size_t)1 << 20)) return MASP_HOST_E_INVALID;
+    if (n == 0) return MASP_HOST_OK;
+    if (!asset_identifiers || !values || !diversifiers || !pk_ds || !lead_bytes || !rseeds || !rcvs || !ovks || !status || !cvs_out || !cmus_out ||
+        !epks_out || !encs_out || !couts_out)
+        return MASP_HOST_E_INVALID;
+    if (!esks && memchr(lead_bytes, 1, n)) return MASP_HOST_E_INVALID;                          // a lead byte 1 needs its esk
+    if (!out_randoms && ovk_flags && memchr(ovk_flags, 0, n)) return MASP_HOST_E_INVALID;       // an absent ovk needs its 96 bytes
+    (void)pedersen_windows();   // the lazily built tables, before the threads race for them
+    (void)generators();
+    auto one = [&](size_t i) {
+        uint8_t *cv = cvs_out + 32 * i, *cmu = cmus_out + 32 * i, *epk = epks_out + 32 * i, *enc = encs_out + ENC_CIPHERTEXT_SIZE * i,
+                *cout = couts_out + OUT_CIPHERTEXT_SIZE * i;
+        auto refuse = [&](int s) {
+            memset(cv, 0, 32);
+            memset(cmu, 0, 32);
+            memset(epk, 0, 32);
+            memset(enc, 0, ENC_CIPHERTEXT_SIZE);
+            memset(cout, 0, OUT_CIPHERTEXT_SIZE);
+            return s;
+        };
+        JPoint g, gd, pk;
+        uint8_t rcm[32], esk[32], pt[NOTE_PLAINTEXT_SIZE];
+        const uint8_t lead = lead_bytes[i], *id = asset_identifiers + 32 * i, *d = diversifiers + 11 * i, *pkd = pk_ds + 32 * i, *r = rseeds + 32 * i;
+        if (!asset_generator(g, id)) return refuse(1);
+        if (!group_hash(gd, d, 11, "MASP__gd")) return refuse(2);
+        if (!JPoint::from_bytes(pk, pkd)) return refuse(3);
+        if (lead == 1) {
+            if (!rj_is_canonical(r)) return refuse(4);   // jubjub::Fr::from_repr(rcm)
+            if (!rj_is_canonical(esks + 32 * i)) return refuse(5);
+            memcpy(rcm, r, 32);
+            memcpy(esk, esks + 32 * i, 32);
+        } else if (lead == 2) {
+            rseed_scalar(rcm, r, 4);   // Note::rcm
+            rseed_scalar(esk, r, 5);   // Note::derive_esk
+        } else {
+            return refuse(4);
+        }
+        if (!rj_is_canonical(rcvs + 32 * i)) return refuse(6);
+        value_commitment(g, values[i], rcvs + 32 * i).to_bytes(cv);
+        note_commitment(g, values[i], gd, pk, rcm).to_affine().u.to_bytes(cmu);
+        pt[0] = lead;
+        memcpy(pt + 1, d, 11);
+        for (int k = 0; k < 8; ++k) pt[12 + k] = (uint8_t)(values[i] >> (8 * k));
+        memcpy(pt + 20, id, 32);
+        memcpy(pt + 52, r, 32);
+        if (memos) {
+            memcpy(pt + 84, memos + 512 * i, 512);
+        } else {
+            memset(pt + 84, 0, 512);
+            pt[84] = 0xf6;   // the empty memo
+        }
+        (void)note_encrypt(esk, d, pkd, pt, epk, enc);   // (g_d and pk_d were decoded above)
+        if (!ovk_flags || ovk_flags[i]) {
+            uint8_t ock[32];
+            prf_ock(ock, ovks + 32 * i, cv, cmu, epk);
+            encrypt_outgoing(cout, ock, pkd, esk);
+        } else {
+            const uint8_t* rnd = out_randoms + 96 * i;
+            encrypt_outgoing(cout, rnd, rnd + 32, rnd + 64);
+        }
+        return 0;
+    };
+    const int nt = std::max(1, std::min<int>(threads, 256));
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (;;) {
+            const size_t i0 = next.fetch_add(16);
+            if (i0 >= n) return;
+            for (size_t i = i0; i < std::min(n, i0 + 16); ++i) status[i] = (uint8_t)one(i);
+        }
+    };
+    std::vector<std::thread> pool;
+    if (n >= 64)   // (a few outputs are not worth the threads' start)
+        for (int k = 1; k < nt; ++k) pool.emplace_back(work);
+    work();
+    for (auto& th : pool) th.join();
+    return MASP_HOST_OK;
+}
 }  // extern "C"

@@ -333,9 +333,9 @@ struct JubjubState {
 
 // What the wallet-side entry points of a device context keep between calls: the note scan (k_note_scan.hip), the compact note scan
 // (k_note_scan_compact.hip), the output recovery scan (k_out_recovery.hip), the commitment trees (k_merkle.hip), the note nullifiers
-// (k_nullifier.hip) and the allowed conversions (k_conversion.hip).  One of these calls runs at a time per context: `mu` guards every member but the atomics and the timing records, and is
+// (k_nullifier.hip), the allowed conversions (k_conversion.hip) and the output descriptions (k_output_build.hip).  One of these calls runs at a time per context: `mu` guards every member but the atomics and the timing records, and is
 // taken by WalletCall alone.  The scans alternate their chunks between the two verifier streams (streams.vk), each with a buffer set of its
-// own; the trees, the nullifiers and the conversions run on streams.vk[0].  Every buffer grows on demand and is kept.
+// own; the trees, the nullifiers, the conversions and the output descriptions run on streams.vk[0].  Every buffer grows on demand and is kept.
 struct WalletState {
     std::mutex mu;
     struct NoteScanSet {
@@ -381,6 +381,13 @@ struct WalletState {
     std::atomic<int> cv_lanes{0};     // masp_hip_allowed_conversions_configure: lanes per conversion, 0 = by the number of conversions
     std::atomic<size_t> cv_chunk_conv{0}, cv_chunk_terms{0};   // ... and a chunk's limits, 0 = the defaults
     LastTiming<3> cv_timing;          // masp_hip_allowed_conversions_last_timing: upload, kernels, download
+    // the output descriptions (k_output_build.hip), on nsc_table's Pedersen points and nf_table's G_ncr windows: G_vcr's windows
+    // (output_table.h), a chunk's arrays as they come, the memos in columns, the per-output state, the two ciphertexts in columns, and
+    // cv | cmu | epk | enc_ciphertext | out_ciphertext | status as they leave
+    OnceTable<uint8_t> ob_table;
+    DevBuf<uint8_t> ob_in, ob_memo, ob_state, ob_cols, ob_out;
+    std::atomic<size_t> ob_chunk{0};  // masp_hip_build_outputs_configure: outputs per chunk, 0 = the default
+    LastTiming<3> ob_timing;          // masp_hip_build_outputs_last_timing: upload, kernels, download
     // The end of a call that may have uploaded tables: one that failed with a HIP error cannot tell whether they arrived, so they are released
     // and the next call uploads them again; any other end confirms them.  A table of an earlier call is not marked and survives either way.
     void settle_tables(int rc) {
@@ -391,6 +398,7 @@ struct WalletState {
         settle(nsc_table);
         settle(mt_empties);
         settle(nf_table);
+        settle(ob_table);
     }
 };
 

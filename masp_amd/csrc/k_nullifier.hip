@@ -48,23 +48,6 @@ __global__ __launch_bounds__(NF_BLOCK) void k_nf_keys(const NfArgs a) {
     nf_key(a.state[i], a.in, i, (int)blockIdx.y);
 }
 
-// the sum of the L partial sums of a lane group (L a power of two, groups aligned in the wave), in every lane of the group
-template <int L>
-__device__ __forceinline__ JExt nf_fold(JExt r) {
-    for (int m = 1; m < L; m <<= 1) {
-        JExt o;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            o.U.v[k] = __shfl_xor(r.U.v[k], m);
-            o.V.v[k] = __shfl_xor(r.V.v[k], m);
-            o.Z.v[k] = __shfl_xor(r.Z.v[k], m);
-            o.T.v[k] = __shfl_xor(r.T.v[k], m);
-        }
-        r = jj_add(r, o);
-    }
-    return r;
-}
-
 // (a lane group is wholly inside the notes or wholly outside, and a note's status is the same for its lanes: the lanes that fold are
 // all there)
 template <int L>

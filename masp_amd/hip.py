@@ -216,6 +216,10 @@ def load_library():
         L.masp_hip_sapling_allowed_conversions.argtypes = [vp, sz, vp, sz, vp, vp, vp, vp, vp]
         L.masp_hip_allowed_conversions_configure.argtypes = [vp, C.c_int, sz, sz]
         L.masp_hip_allowed_conversions_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
+    if hasattr(L, "masp_hip_sapling_build_outputs"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
+        L.masp_hip_sapling_build_outputs.argtypes = [vp, sz] + [vp] * 18
+        L.masp_hip_build_outputs_configure.argtypes = [vp, sz]
+        L.masp_hip_build_outputs_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
     if hasattr(L, "masp_hip_sapling_check_bundles"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
         L.masp_hip_sapling_check_bundles.argtypes = [vp, C.POINTER(BundleCheckStruct)]
         L.masp_hip_check_bundles_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
@@ -681,6 +685,31 @@ class Context:
     def allowed_conversions_last_timing(self):
         """(upload ms, kernel ms, download ms) of the last allowed_conversions call of this context, HIP events summed over its chunks"""
         return self._timing(self._L.masp_hip_allowed_conversions_last_timing, 3)
+
+    # ---- output descriptions without their proofs on the GPU ----
+    def build_outputs(self, asset_identifiers, values, diversifiers, pk_ds, lead_bytes, rseeds, esks, rcvs, memos, ovks, ovk_flags=None,
+                      out_randoms=None):
+        """cv, cmu, epk, enc_ciphertext and out_ciphertext of n outputs on the GPU (masp_hip_sapling_build_outputs).  Arrays in, in the C
+        ABI's order (n x 32 bytes each, diversifiers n x 11, values / lead bytes / ovk flags n, memos n x 512, out_randoms n x 96); esks (no
+        lead byte is 1), memos (every memo empty, nothing uploaded), ovk_flags (every ovk present) and out_randoms (no flag is 0) may be None
+        -> (status uint8[n], cvs, cmus, epks uint8[n, 32], encs uint8[n, 612], couts uint8[n, 80]).  status: 0, or 1 asset identifier,
+        2 diversifier, 3 pk_d, 4 lead byte or rcm, 5 esk, 6 rcv; such an output's outputs are zeros.  No randomness is drawn.
+        host.build_outputs is the same on the host."""
+        from .host import build_output_args, build_output_results
+        args = build_output_args(asset_identifiers, values, diversifiers, pk_ds, lead_bytes, rseeds, esks, rcvs, memos, ovks, ovk_flags, out_randoms)
+        n = args[0].shape[0]
+        res = build_output_results(n)
+        p = lambda a: _p(a) if a is not None and a.size else None
+        self._check(self._L.masp_hip_sapling_build_outputs(self._h, n, *[p(a) for a in args], *[p(a) for a in res]))
+        return res
+
+    def build_outputs_configure(self, chunk_outputs=0):
+        """outputs per chunk: 0 = the default, nothing above it.  For measurements and tests: the bytes do not depend on it."""
+        self._check(self._L.masp_hip_build_outputs_configure(self._h, int(chunk_outputs)))
+
+    def build_outputs_last_timing(self):
+        """(upload ms, kernel ms, download ms) of the last build_outputs call of this context, HIP events summed over its chunks"""
+        return self._timing(self._L.masp_hip_build_outputs_last_timing, 3)
 
     # ---- building blocks ----
     def msm_g1(self, bases, scalars):

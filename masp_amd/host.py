@@ -59,6 +59,7 @@ def load_library():
         L.masp_host_value_commitment.argtypes = [cp, u64, cp, cp, cp]
         L.masp_host_note_cmu.argtypes = [cp, u64, cp, cp, cp, cp]
         L.masp_host_sapling_note_nullifiers.argtypes = [C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]
+        L.masp_host_sapling_build_outputs.argtypes = [C.c_size_t] + [vp] * 18 + [C.c_int]
         L.masp_host_merkle_hash.argtypes = [C.c_uint, cp, cp, cp]
         L.masp_host_merkle_empty_roots.argtypes = [vp]
         L.masp_host_merkle_empty_roots.restype = None
@@ -425,6 +426,44 @@ def note_nullifiers(asset_identifiers, values, diversifiers, pk_ds, lead_bytes, 
     _check(load_library().masp_host_sapling_note_nullifiers(n, *[vp(a) for a in args], vp(status), vp(cmus), vp(nfs),
                                                            int(threads or effective_cpus())))
     return status, cmus, nfs
+
+
+def build_output_args(asset_identifiers, values, diversifiers, pk_ds, lead_bytes, rseeds, esks, rcvs, memos, ovks, ovk_flags, out_randoms):
+    """the arguments of either build_outputs as contiguous arrays, in the C ABI's order: uint8[n, 32] (bytes or arrays), uint64[n],
+    uint8[n, 11], uint8[n], uint8[n, 512], uint8[n, 96]; esks, memos, ovk_flags and out_randoms may be None and stay None"""
+    def u8(a, w):
+        if a is None:
+            return None
+        if isinstance(a, (bytes, bytearray, memoryview)):
+            a = np.frombuffer(a, dtype=np.uint8)
+        return np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, w) if w else np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+    out = (u8(asset_identifiers, 32), np.ascontiguousarray(values, dtype=np.uint64).reshape(-1), u8(diversifiers, 11), u8(pk_ds, 32),
+           u8(lead_bytes, 0), u8(rseeds, 32), u8(esks, 32), u8(rcvs, 32), u8(memos, 512), u8(ovks, 32), u8(ovk_flags, 0), u8(out_randoms, 96))
+    n = out[0].shape[0]
+    if any(a is not None and a.shape[0] != n for a in out):
+        raise ValueError("build_outputs: the arrays differ in length: %s" % ([None if a is None else a.shape[0] for a in out],))
+    return out
+
+
+def build_output_results(n):
+    """(status uint8[n], cvs, cmus, epks uint8[n, 32], encs uint8[n, 612], couts uint8[n, 80]), zeroed"""
+    return (np.zeros(n, np.uint8), np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8), np.zeros((n, 32), np.uint8),
+            np.zeros((n, ENC_CIPHERTEXT_SIZE), np.uint8), np.zeros((n, OUT_CIPHERTEXT_SIZE), np.uint8))
+
+
+def build_outputs(asset_identifiers, values, diversifiers, pk_ds, lead_bytes, rseeds, esks, rcvs, memos, ovks, ovk_flags=None, out_randoms=None,
+                  threads=None):
+    """masp_host_sapling_build_outputs: cv, cmu, epk, enc_ciphertext and out_ciphertext of n outputs on host threads (default:
+    effective_cpus()).  Arrays in, in the C ABI's order (n x 32 bytes each, diversifiers n x 11, values / lead bytes / ovk flags n, memos
+    n x 512, out_randoms n x 96); esks (no lead byte is 1), memos (every memo empty), ovk_flags (every ovk present) and out_randoms (no flag
+    is 0) may be None -> (status uint8[n], cvs, cmus, epks uint8[n, 32], encs uint8[n, 612], couts uint8[n, 80]).  status: 0, or 1 asset
+    identifier, 2 diversifier, 3 pk_d, 4 lead byte or rcm, 5 esk, 6 rcv; such an output's outputs are zeros.  No randomness is drawn."""
+    args = build_output_args(asset_identifiers, values, diversifiers, pk_ds, lead_bytes, rseeds, esks, rcvs, memos, ovks, ovk_flags, out_randoms)
+    n = args[0].shape[0]
+    res = build_output_results(n)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    _check(load_library().masp_host_sapling_build_outputs(n, *[vp(a) for a in args], *[vp(a) for a in res], int(threads or effective_cpus())))
+    return res
 
 
 def merkle_hash(depth, lhs, rhs):

@@ -16,7 +16,10 @@ The sender's side: `encrypt_outgoing_plaintext` makes an output's out_ciphertext
 every pair) and finishes the pairs whose tag verifies on the host (masp_host_sapling_try_output_recovery_with_ock: everything else).
 
 Once a note is the wallet's: `note_nf` is Note::nf(&nk, position) on the host, and `batch.note_nullifiers` computes the commitments and
-nullifiers of a list of notes on the GPU (masp_hip_sapling_note_nullifiers) or on host threads."""
+nullifiers of a list of notes on the GPU (masp_hip_sapling_note_nullifiers) or on host threads.
+
+Making outputs: `batch.build_outputs` turns output plans into `OutputDescription`s without their proofs, cv, cmu, epk and the two
+ciphertexts, on the GPU (masp_hip_sapling_build_outputs) or on host threads."""
 import os
 from collections import namedtuple
 
@@ -70,6 +73,26 @@ def _nullifier_arrays(items):
 
 NULLIFIER_STATUS = {1: "the asset identifier has no generator", 2: "the diversifier has no g_d", 3: "pk_d does not decode",
                     4: "the lead byte is neither 1 nor 2, or rcm is not below r_J", 5: "nk does not decode"}
+
+
+BUILD_OUTPUT_STATUS = {1: "the asset identifier has no generator", 2: "the diversifier has no g_d", 3: "pk_d does not decode",
+                       4: "the lead byte is neither 1 nor 2, or rcm is not below r_J", 5: "esk is not below r_J", 6: "rcv is not below r_J"}
+
+
+def _build_output_arrays(plans):
+    """plans: (ovk or None, Note, PaymentAddress, memo, rcv, esk=None, out_random=None) each -> the twelve arrays of either build_outputs.
+    An absent ovk without out_random gets os.urandom(96), as encrypt_outgoing_plaintext draws it."""
+    plans = [tuple(p) + (None,) * (7 - len(p)) for p in plans]
+    cat = lambda f: np.frombuffer(b"".join(f(p) for p in plans), dtype=np.uint8)
+    scalar = lambda x: bytes(32) if x is None else H._b(x)
+    flags = np.array([p[0] is not None for p in plans], dtype=np.uint8)
+    randoms = None if flags.all() else cat(lambda p: bytes(96) if p[0] is not None else os.urandom(96) if p[6] is None else H._b(p[6], 96))
+    esks = cat(lambda p: scalar(p[5])) if any(p[1].rseed.lead_byte == 1 for p in plans) else None
+    return (cat(lambda p: H._b(p[1].asset_identifier)), np.array([int(p[1].value) for p in plans], dtype=np.uint64),
+            cat(lambda p: H._b(p[2].diversifier, 11)), cat(lambda p: H._b(p[2].pk_d)),
+            np.array([int(p[1].rseed.lead_byte) & 0xff for p in plans], dtype=np.uint8), cat(lambda p: H._b(p[1].rseed.bytes)), esks,
+            cat(lambda p: scalar(p[4])), cat(lambda p: H._b(EMPTY_MEMO if p[3] is None else p[3], MEMO_SIZE)), cat(lambda p: scalar(p[0])),
+            flags, randoms)
 
 
 def note_nf(note, to, nk, position):
@@ -200,6 +223,21 @@ class batch:
         arrays = _nullifier_arrays(items)
         status, cmus, nfs = H.note_nullifiers(*arrays, threads=threads) if ctx is None else ctx.note_nullifiers(*arrays)
         return [None if s else (c.tobytes(), f.tobytes()) for s, c, f in zip(status.tolist(), cmus, nfs)]
+
+    @staticmethod
+    def build_outputs(plans, ctx, threads=None):
+        """plans: (ovk or None, Note, PaymentAddress, memo, rcv, esk=None, out_random=None) each -> one entry per plan, in order: an
+        OutputDescription (without the proof), or None where the plan is refused (BUILD_OUTPUT_STATUS).  esk: for a lead-byte-1 note (a
+        ZIP 212 note derives its own); rcv, esk: 32 bytes or an int; out_random: the 96 bytes (ock | op) of an output without ovk, default
+        os.urandom(96) as encrypt_outgoing_plaintext draws them.  Everything below this is a function of its inputs.  ctx: a
+        masp_amd.Context, the outputs are built on its GPU (masp_hip_sapling_build_outputs); None: on `threads` host threads."""
+        plans = list(plans)
+        if not plans:
+            return []
+        arrays = _build_output_arrays(plans)
+        status, cvs, cmus, epks, encs, couts = H.build_outputs(*arrays, threads=threads) if ctx is None else ctx.build_outputs(*arrays)
+        return [None if s else OutputDescription(cv.tobytes(), cmu.tobytes(), epk.tobytes(), enc.tobytes(), cout.tobytes())
+                for s, cv, cmu, epk, enc, cout in zip(status.tolist(), cvs, cmus, epks, encs, couts)]
 
     @staticmethod
     def try_output_recovery(ovks, outputs, ctx, lead_byte=2):
