@@ -667,6 +667,57 @@ int masp_hip_sapling_build_outputs(masp_hip_ctx* ctx, size_t n, const uint8_t* a
 int masp_hip_build_outputs_configure(masp_hip_ctx* ctx, size_t chunk_outputs);
 int masp_hip_build_outputs_last_timing(masp_hip_ctx* ctx, double ms[3]);
 
+/* ---- Spend descriptions without their proofs, and RedJubjub signatures, on the GPU: cv, rk, nf and sig in batches ----
+ * Both calls draw no randomness: the caller supplies every random byte, and the result is a function of the inputs.
+ * masp_hip_redjubjub_sign_batch <- PrivateKey::randomize, PublicKey::from_private and PrivateKey::sign as spend_sig_internal composes them
+ *    (masp_primitives/src/sapling.rs:167-195, sapling/redjubjub.rs:121-160), over either basepoint, for n items:
+ *    rsk  = sk + alpha mod r_J,  vk = [rsk] G_kind                      (rk for kind 0, bvk for kind 1),
+ *    r    = H*(T || vk || sighash),  Rbar = repr([r] G_kind),  S = r + H*(Rbar || vk || sighash) rsk mod r_J,
+ *    H* = BLAKE2b-512, personal "MASP__RedJubjubH", reduced mod r_J.
+ * sks, alphas, sighashes: n x 32; kinds: n bytes, 0 spend authorisation on spending_key_generator, 1 binding on
+ * value_commitment_randomness_generator (as in masp_hip_redjubjub_verify_each), anything else MASP_HIP_E_INVALID_ARG before any work;
+ * randoms: n x 80, the reference's T.  alphas may be NULL: no randomisation (the binding signature's case).
+ * Result: status (n bytes), vks_out (n x 32, may be NULL: not downloaded), sigs_out (n x 64, Rbar || Sbar).  status[i] is 0, or the first
+ * check that fails: 1 sk >= r_J (what PrivateKey::read refuses), 2 alpha >= r_J.  A refused item has zeros in both outputs and changes
+ * neither the return code nor its neighbours' results.  rsk = 0 is NOT refused: the reference signs with it, so this call does too, and vk
+ * is then the identity's encoding.
+ * masp_hip_sapling_build_spends <- what the builder (masp_primitives/src/transaction/components/sapling/builder.rs) puts around a Spend
+ * proof, for n spends:
+ *    nk = [nsk] G_pgk (ProofGenerationKey::to_viewing_key),  rk = ak + [ar] G_spend (ViewingKey::rk),
+ *    cv = what masp_host_value_commitment(id, value, rcv) returns,
+ *    cmu, nf = what masp_hip_sapling_note_nullifiers gives for (note, nk, position).
+ * The six note arrays are that call's (asset_identifiers, pk_ds, rseeds: n x 32; diversifiers: n x 11; values, lead_bytes: n); aks, nsks,
+ * ars, rcvs: n x 32; positions: n.  The anchor is the caller's, from the tree, and is not an input.
+ * Result: status (n bytes), cvs_out, rks_out, nfs_out (n x 32), cmus_out and nks_out (n x 32, either may be NULL: not downloaded).
+ * status[i] is 0, or the first check that fails, in this order: 1 to 4 as in masp_hip_sapling_note_nullifiers, 5 ak is not the canonical
+ * encoding of a curve point, 6 [8] ak is the identity (the Spend circuit asserts that ak is not of small order: a spend built here is
+ * provable), 7 nsk >= r_J, 8 ar >= r_J, 9 rcv >= r_J.  A refused spend has zeros in all five outputs and changes neither the return code
+ * nor its neighbours' results.  Beyond check 6 the membership of ak in the prime-order subgroup is NOT tested, and that of pk_d is NOT
+ * tested either, as in the neighbouring calls: both are decoded, canonical and on the curve.
+ * Both: n <= 2^20 a call; n = 0: MASP_HIP_OK, no GPU work, no array is read.  A NULL array other than those named, or n > 2^20:
+ * MASP_HIP_E_INVALID_ARG with nothing written.  The device works through chunks of at most 2^16 items, one after the other; the result is
+ * deterministic and the same for any chunk size.  Re-entrant next to proving and verification calls; on the context's first verifier
+ * stream, under the lock of the note scans, the trees, the nullifiers, the conversions and the outputs, no stream or hardware queue of
+ * their own; on a multi-device context on the first device.
+ * Secrets: sks, alphas, randoms, nsks, ars and rcvs pass through pinned staging memory of the context; that staging memory, every uploaded
+ * input and the per-item state on the device (rsk and r among it) are zeroed on the call's stream before the call releases the lock, on
+ * success and on every error path.  This is a guarantee of the call, not a best effort; memory of the caller's is the caller's.
+ * masp_host_redjubjub_sign_batch and masp_host_sapling_build_spends (include/masp_host.h) are the same on the host.
+ * masp_hip_redjubjub_sign_configure, masp_hip_build_spends_configure - items per chunk, 0 = the default; for measurements and tests, the
+ * bytes do not depend on it.  Values above the default: MASP_HIP_E_INVALID_ARG.
+ * masp_hip_redjubjub_sign_last_timing, masp_hip_build_spends_last_timing - of the last such call of this context, summed over its chunks
+ * from HIP events on its stream: ms[0] the host-to-device copies, ms[1] the kernels, ms[2] the device-to-host copies. */
+int masp_hip_redjubjub_sign_batch(masp_hip_ctx* ctx, size_t n, const uint8_t* sks, const uint8_t* alphas, const uint8_t* sighashes,
+                                  const uint8_t* kinds, const uint8_t* randoms, uint8_t* status, uint8_t* vks_out, uint8_t* sigs_out);
+int masp_hip_redjubjub_sign_configure(masp_hip_ctx* ctx, size_t chunk_items);
+int masp_hip_redjubjub_sign_last_timing(masp_hip_ctx* ctx, double ms[3]);
+int masp_hip_sapling_build_spends(masp_hip_ctx* ctx, size_t n, const uint8_t* asset_identifiers, const uint64_t* values,
+                                  const uint8_t* diversifiers, const uint8_t* pk_ds, const uint8_t* lead_bytes, const uint8_t* rseeds,
+                                  const uint8_t* aks, const uint8_t* nsks, const uint8_t* ars, const uint8_t* rcvs, const uint64_t* positions,
+                                  uint8_t* status, uint8_t* cvs_out, uint8_t* rks_out, uint8_t* nfs_out, uint8_t* cmus_out, uint8_t* nks_out);
+int masp_hip_build_spends_configure(masp_hip_ctx* ctx, size_t chunk_spends);
+int masp_hip_build_spends_last_timing(masp_hip_ctx* ctx, double ms[3]);
+
 /* ---- measurement hooks (bench.py): device-resident workloads, HIP-event timing on the ctx stream ---- */
 /* Keeps `n` jobs' assignments resident in HBM; returns a handle (>= 0) or a negative error code. */
 int masp_hip_batch_upload(masp_hip_ctx* ctx, size_t n, const masp_hip_job* jobs);

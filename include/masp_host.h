@@ -139,6 +139,23 @@ int masp_host_sapling_build_outputs(size_t n, const uint8_t* asset_identifiers, 
                                     const uint8_t* rcvs, const uint8_t* memos, const uint8_t* ovks, const uint8_t* ovk_flags,
                                     const uint8_t* out_randoms, uint8_t* status, uint8_t* cvs_out, uint8_t* cmus_out, uint8_t* epks_out,
                                     uint8_t* encs_out, uint8_t* couts_out, int threads);
+/* RedJubjub signatures (spend_sig_internal of masp_primitives/src/sapling.rs over sapling/redjubjub.rs:121-160) for n <= 2^20 items on
+ * `threads` host threads: the arguments and results of masp_hip_redjubjub_sign_batch (include/masp_hip.h) without the context.  No
+ * randomness is drawn: randoms holds the reference's 80 bytes T per item.  alphas and vks_out may be NULL.  kinds: 0 spend authorisation,
+ * 1 binding; anything else MASP_HOST_E_INVALID before any work.  status[i]: 0, 1 sk >= r_J, 2 alpha >= r_J; the item's outputs are then
+ * zeros and nothing else changes.  rsk = 0 is not refused.  MASP_HOST_E_INVALID: any other NULL array with n > 0, n > 2^20. */
+int masp_host_redjubjub_sign_batch(size_t n, const uint8_t* sks, const uint8_t* alphas, const uint8_t* sighashes, const uint8_t* kinds,
+                                   const uint8_t* randoms, uint8_t* status, uint8_t* vks_out, uint8_t* sigs_out, int threads);
+/* Spend descriptions without their proofs (the builder of masp_primitives/src/transaction/components/sapling/builder.rs) for n <= 2^20
+ * spends on `threads` host threads: the arguments and results of masp_hip_sapling_build_spends (include/masp_hip.h) without the context.
+ * cmus_out and nks_out may be NULL.  status[i]: 0, or the first check that fails: 1 to 4 as in masp_host_sapling_note_nullifiers, 5 ak
+ * does not decode, 6 [8] ak is the identity, 7 nsk >= r_J, 8 ar >= r_J, 9 rcv >= r_J; the spend's outputs are then zeros and nothing else
+ * changes.  Beyond check 6 the subgroup membership of ak is not tested, nor is pk_d's.  MASP_HOST_E_INVALID: any other NULL array with
+ * n > 0, n > 2^20; nothing is written. */
+int masp_host_sapling_build_spends(size_t n, const uint8_t* asset_identifiers, const uint64_t* values, const uint8_t* diversifiers,
+                                   const uint8_t* pk_ds, const uint8_t* lead_bytes, const uint8_t* rseeds, const uint8_t* aks,
+                                   const uint8_t* nsks, const uint8_t* ars, const uint8_t* rcvs, const uint64_t* positions, uint8_t* status,
+                                   uint8_t* cvs_out, uint8_t* rks_out, uint8_t* nfs_out, uint8_t* cmus_out, uint8_t* nks_out, int threads);
 int masp_host_merkle_hash(unsigned depth, const uint8_t lhs[32], const uint8_t rhs[32], uint8_t out32[32]);
 /* empty_root(0..32) of the commitment tree, 33 x 32 bytes: the uncommitted leaf 1 and the roots of the empty subtrees above it */
 void masp_host_merkle_empty_roots(uint8_t out[33 * 32]);

@@ -11,6 +11,8 @@ from .verifier import (BatchValidator, Bundle, ConvertDescription, OutputDescrip
 from . import note_encryption  # noqa: F401
 from .note_encryption import (CompactShieldedOutput, Note, PaymentAddress, Rseed, ShieldedOutput, note_nf, sapling_note_encrypt,  # noqa: F401
                               try_sapling_compact_note_decryption, try_sapling_note_decryption)
+from . import redjubjub  # noqa: F401
+from .redjubjub import sign_batch, spend_sigs  # noqa: F401
 from . import merkle_tree  # noqa: F401
 from .merkle_tree import CommitmentTree, FrozenCommitmentTree, IncrementalWitness, MerklePath, advance, empty_root  # noqa: F401
 from . import convert  # noqa: F401

@@ -1294,3 +1294,160 @@ int masp_host_sapling_build_outputs(size_t n, const uint8_t* asset_identifiers, 
     return MASP_HOST_OK;
 }
 }  // extern "C"
+
+// ---- spend descriptions and RedJubjub signatures in batches --------------------------------------------
+namespace {
+// a + b mod r_J, both below r_J, 32 little-endian bytes each
+void rj_add(uint8_t out[32], const uint8_t a[32], const uint8_t b[32]) {
+    uint64_t x[4], y[4], d[4];
+    memcpy(x, a, 32);
+    memcpy(y, b, 32);
+    unsigned __int128 c = 0;
+    for (int i = 0; i < 4; ++i) {
+        c += (unsigned __int128)x[i] + y[i];
+        x[i] = (uint64_t)c;
+        c >>= 64;
+    }   // (below 2 r_J < 2^253: no carry out)
+    unsigned __int128 borrow = 0;
+    for (int i = 0; i < 4; ++i) {
+        const unsigned __int128 t = (unsigned __int128)x[i] - RJ[i] - (uint64_t)borrow;
+        d[i] = (uint64_t)t;
+        borrow = (t >> 64) & 1;
+    }
+    memcpy(out, borrow ? x : d, 32);
+}
+// a b mod r_J: the 512-bit product through rj_from_bytes_wide
+void rj_mul(uint8_t out[32], const uint8_t a[32], const uint8_t b[32]) {
+    uint64_t x[4], y[4], p[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    memcpy(x, a, 32);
+    memcpy(y, b, 32);
+    for (int i = 0; i < 4; ++i) {
+        unsigned __int128 c = 0;
+        for (int j = 0; j < 4; ++j) {
+            c += (unsigned __int128)x[i] * y[j] + p[i + j];
+            p[i + j] = (uint64_t)c;
+            c >>= 64;
+        }
+        p[i + 4] = (uint64_t)c;
+    }
+    uint8_t wide[64];
+    memcpy(wide, p, 64);
+    rj_from_bytes_wide(out, wide);
+}
+// H*(a | b | c) mod r_J (masp_primitives/src/sapling/util.rs: hash_to_scalar, personal "MASP__RedJubjubH")
+void h_star(uint8_t out[32], const uint8_t* a, size_t alen, const uint8_t* b, const uint8_t* c) {
+    uint8_t wide[64];
+    Blake2b h((const uint8_t*)"MASP__RedJubjubH", 64);
+    h.update(a, alen);
+    h.update(b, 32);
+    h.update(c, 32);
+    h.finalize(wide);
+    rj_from_bytes_wide(out, wide);
+}
+// one(i) -> status[i] for i < n, dealt to `threads` host threads sixteen at a time
+template <class F>
+void deal(size_t n, int threads, uint8_t* status, F one) {
+    const int nt = std::max(1, std::min<int>(threads, 256));
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (;;) {
+            const size_t i0 = next.fetch_add(16);
+            if (i0 >= n) return;
+            for (size_t i = i0; i < std::min(n, i0 + 16); ++i) status[i] = (uint8_t)one(i);
+        }
+    };
+    std::vector<std::thread> pool;
+    if (n >= 64)   // (a few items are not worth the threads' start)
+        for (int k = 1; k < nt; ++k) pool.emplace_back(work);
+    work();
+    for (auto& th : pool) th.join();
+}
+}  // namespace
+
+extern "C" {
+// spend_sig_internal (masp_primitives/src/sapling.rs:167-195: PrivateKey::randomize, PublicKey::from_private, PrivateKey::sign of
+// sapling/redjubjub.rs:121-160) over either basepoint for n items; what masp_hip_redjubjub_sign_batch computes, and its other side in the
+// tests.  rsk = 0 is signed with, as the reference does.
+int masp_host_redjubjub_sign_batch(size_t n, const uint8_t* sks, const uint8_t* alphas, const uint8_t* sighashes, const uint8_t* kinds,
+                                   const uint8_t* randoms, uint8_t* status, uint8_t* vks_out, uint8_t* sigs_out, int threads) {
+    if (n > ((size_t)1 << 20)) return MASP_HOST_E_INVALID;
+    if (n == 0) return MASP_HOST_OK;
+    if (!sks || !sighashes || !kinds || !randoms || !status || !sigs_out) return MASP_HOST_E_INVALID;
+    for (size_t i = 0; i < n; ++i)
+        if (kinds[i] > 1) return MASP_HOST_E_INVALID;
+    (void)generators();   // the lazily built tables, before the threads race for them
+    deal(n, threads, status, [&](size_t i) {
+        uint8_t* sig = sigs_out + 64 * i;
+        memset(sig, 0, 64);
+        if (vks_out) memset(vks_out + 32 * i, 0, 32);
+        const uint8_t *sk = sks + 32 * i, *m = sighashes + 32 * i;
+        if (!rj_is_canonical(sk)) return 1;   // PrivateKey::read
+        uint8_t rsk[32], vk[32], r[32], c[32], cr[32];
+        memcpy(rsk, sk, 32);
+        if (alphas) {
+            if (!rj_is_canonical(alphas + 32 * i)) return 2;
+            rj_add(rsk, sk, alphas + 32 * i);
+        }
+        const JPoint& g = kinds[i] ? generators().value_commitment_randomness : generators().spending_key;
+        g.mul(rsk).to_bytes(vk);
+        h_star(r, randoms + 80 * i, 80, vk, m);
+        g.mul(r).to_bytes(sig);
+        h_star(c, sig, 32, vk, m);
+        rj_mul(cr, c, rsk);
+        rj_add(sig + 32, r, cr);
+        if (vks_out) memcpy(vks_out + 32 * i, vk, 32);
+        return 0;
+    });
+    return MASP_HOST_OK;
+}
+// What the builder puts around a Spend proof for n spends; what masp_hip_sapling_build_spends computes, and its other side in the tests.
+// Composed from what the one-item calls are made of: value_commitment, note_commitment, nullifier.
+int masp_host_sapling_build_spends(size_t n, const uint8_t* asset_identifiers, const uint64_t* values, const uint8_t* diversifiers,
+                                   const uint8_t* pk_ds, const uint8_t* lead_bytes, const uint8_t* rseeds, const uint8_t* aks,
+                                   const uint8_t* nsks, const uint8_t* ars, const uint8_t* rcvs, const uint64_t* positions, uint8_t* status,
+                                   uint8_t* cvs_out, uint8_t* rks_out, uint8_t* nfs_out, uint8_t* cmus_out, uint8_t* nks_out, int threads) {
+    if (n > ((size_t)1 << 20)) return MASP_HOST_E_INVALID;
+    if (n == 0) return MASP_HOST_OK;
+    if (!asset_identifiers || !values || !diversifiers || !pk_ds || !lead_bytes || !rseeds || !aks || !nsks || !ars || !rcvs || !positions ||
+        !status || !cvs_out || !rks_out || !nfs_out)
+        return MASP_HOST_E_INVALID;
+    (void)pedersen_windows();   // the lazily built tables, before the threads race for them
+    (void)generators();
+    deal(n, threads, status, [&](size_t i) {
+        memset(cvs_out + 32 * i, 0, 32);
+        memset(rks_out + 32 * i, 0, 32);
+        memset(nfs_out + 32 * i, 0, 32);
+        if (cmus_out) memset(cmus_out + 32 * i, 0, 32);
+        if (nks_out) memset(nks_out + 32 * i, 0, 32);
+        JPoint g, gd, pk, ak;
+        uint8_t rcm[32], nkb[32];
+        const uint8_t lead = lead_bytes[i], *r = rseeds + 32 * i;
+        if (!asset_generator(g, asset_identifiers + 32 * i)) return 1;
+        if (!group_hash(gd, diversifiers + 11 * i, 11, "MASP__gd")) return 2;
+        if (!JPoint::from_bytes(pk, pk_ds + 32 * i)) return 3;
+        if (lead == 1) {
+            if (!rj_is_canonical(r)) return 4;   // jubjub::Fr::from_repr(rcm)
+            memcpy(rcm, r, 32);
+        } else if (lead == 2) {
+            rseed_scalar(rcm, r, 4);
+        } else {
+            return 4;
+        }
+        if (!JPoint::from_bytes(ak, aks + 32 * i)) return 5;
+        if (ak.mul_by_cofactor().is_identity()) return 6;   // the Spend circuit: ak is not of small order
+        if (!rj_is_canonical(nsks + 32 * i)) return 7;
+        if (!rj_is_canonical(ars + 32 * i)) return 8;
+        if (!rj_is_canonical(rcvs + 32 * i)) return 9;
+        const JPoint nk = generators().proof_generation_key.mul(nsks + 32 * i);
+        nk.to_bytes(nkb);
+        ak.add(generators().spending_key.mul(ars + 32 * i)).to_bytes(rks_out + 32 * i);
+        value_commitment(g, values[i], rcvs + 32 * i).to_bytes(cvs_out + 32 * i);
+        const JPoint cm = note_commitment(g, values[i], gd, pk, rcm);
+        if (cmus_out) cm.to_affine().u.to_bytes(cmus_out + 32 * i);
+        nullifier(nfs_out + 32 * i, cm, positions[i], nk);
+        if (nks_out) memcpy(nks_out + 32 * i, nkb, 32);
+        return 0;
+    });
+    return MASP_HOST_OK;
+}
+}  // extern "C"

@@ -333,9 +333,9 @@ struct JubjubState {
 
 // What the wallet-side entry points of a device context keep between calls: the note scan (k_note_scan.hip), the compact note scan
 // (k_note_scan_compact.hip), the output recovery scan (k_out_recovery.hip), the commitment trees (k_merkle.hip), the note nullifiers
-// (k_nullifier.hip), the allowed conversions (k_conversion.hip) and the output descriptions (k_output_build.hip).  One of these calls runs at a time per context: `mu` guards every member but the atomics and the timing records, and is
+// (k_nullifier.hip), the allowed conversions (k_conversion.hip), the output descriptions (k_output_build.hip) and the spend descriptions with their signatures (k_spend_build.hip).  One of these calls runs at a time per context: `mu` guards every member but the atomics and the timing records, and is
 // taken by WalletCall alone.  The scans alternate their chunks between the two verifier streams (streams.vk), each with a buffer set of its
-// own; the trees, the nullifiers, the conversions and the output descriptions run on streams.vk[0].  Every buffer grows on demand and is kept.
+// own; the trees, the nullifiers, the conversions, the output and the spend descriptions run on streams.vk[0].  Every buffer grows on demand and is kept.
 struct WalletState {
     std::mutex mu;
     struct NoteScanSet {
@@ -388,6 +388,15 @@ struct WalletState {
     DevBuf<uint8_t> ob_in, ob_memo, ob_state, ob_cols, ob_out;
     std::atomic<size_t> ob_chunk{0};  // masp_hip_build_outputs_configure: outputs per chunk, 0 = the default
     LastTiming<3> ob_timing;          // masp_hip_build_outputs_last_timing: upload, kernels, download
+    // the spend descriptions and the RedJubjub signatures (k_spend_build.hip), on the tables above: the windows of G_spend and G_pgk
+    // (spend_table.h), and per call kind a chunk's arrays as they come, the per-item state and the results as they leave.  The secret
+    // inputs pass through a pinned staging buffer; it, the uploaded secrets and the states are zeroed before a call releases the lock.
+    OnceTable<uint8_t> sb_table;
+    DevBuf<uint8_t> sb_in, sb_state, sb_out, rs_in, rs_state, rs_out;
+    PinnedBuf<uint8_t> sb_stage, rs_stage;
+    std::atomic<size_t> sb_chunk{0};  // masp_hip_build_spends_configure: spends per chunk, 0 = the default
+    std::atomic<size_t> rs_chunk{0};  // masp_hip_redjubjub_sign_configure: items per chunk, 0 = the default
+    LastTiming<3> sb_timing, rs_timing;   // masp_hip_build_spends_last_timing, masp_hip_redjubjub_sign_last_timing: upload, kernels, download
     // The end of a call that may have uploaded tables: one that failed with a HIP error cannot tell whether they arrived, so they are released
     // and the next call uploads them again; any other end confirms them.  A table of an earlier call is not marked and survives either way.
     void settle_tables(int rc) {
@@ -399,6 +408,7 @@ struct WalletState {
         settle(mt_empties);
         settle(nf_table);
         settle(ob_table);
+        settle(sb_table);
     }
 };
 

@@ -220,6 +220,13 @@ def load_library():
         L.masp_hip_sapling_build_outputs.argtypes = [vp, sz] + [vp] * 18
         L.masp_hip_build_outputs_configure.argtypes = [vp, sz]
         L.masp_hip_build_outputs_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
+    if hasattr(L, "masp_hip_sapling_build_spends"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
+        L.masp_hip_redjubjub_sign_batch.argtypes = [vp, sz] + [vp] * 8
+        L.masp_hip_redjubjub_sign_configure.argtypes = [vp, sz]
+        L.masp_hip_redjubjub_sign_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
+        L.masp_hip_sapling_build_spends.argtypes = [vp, sz] + [vp] * 17
+        L.masp_hip_build_spends_configure.argtypes = [vp, sz]
+        L.masp_hip_build_spends_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
     if hasattr(L, "masp_hip_sapling_check_bundles"):      # (an older build passed as MASP_HIP_LIBRARY lacks them)
         L.masp_hip_sapling_check_bundles.argtypes = [vp, C.POINTER(BundleCheckStruct)]
         L.masp_hip_check_bundles_last_timing.argtypes = [vp, C.POINTER(C.c_double)]
@@ -710,6 +717,53 @@ class Context:
     def build_outputs_last_timing(self):
         """(upload ms, kernel ms, download ms) of the last build_outputs call of this context, HIP events summed over its chunks"""
         return self._timing(self._L.masp_hip_build_outputs_last_timing, 3)
+
+    # ---- spend descriptions without their proofs, and RedJubjub signatures, on the GPU ----
+    def redjubjub_sign_batch(self, sks, alphas, sighashes, kinds, randoms, want_vks=True):
+        """n RedJubjub signatures on the GPU (masp_hip_redjubjub_sign_batch): rsk = sk + alpha, vk = [rsk] G_kind, sig = Rbar | S with the
+        nonce from the item's 80 bytes of randoms.  sks, alphas (or None: no randomisation), sighashes n x 32, kinds n (0 spend
+        authorisation, 1 binding), randoms n x 80 -> (status uint8[n], vks uint8[n, 32] or None with want_vks=False: not downloaded, sigs
+        uint8[n, 64]).  status: 0, or 1 sk >= r_J, 2 alpha >= r_J; such an item's outputs are zeros.  No randomness is drawn; what the call
+        uploaded and kept of the secrets is zeroed before it returns.  host.redjubjub_sign_batch is the same on the host."""
+        from .host import sign_batch_args
+        args = sign_batch_args(sks, alphas, sighashes, kinds, randoms)
+        n = args[0].shape[0]
+        status, sigs = np.zeros(n, np.uint8), np.zeros((n, 64), np.uint8)
+        vks = np.zeros((n, 32), np.uint8) if want_vks else None
+        p = lambda a: _p(a) if a is not None and a.size else None
+        self._check(self._L.masp_hip_redjubjub_sign_batch(self._h, n, *[p(a) for a in args], p(status), p(vks), p(sigs)))
+        return status, vks, sigs
+
+    def redjubjub_sign_configure(self, chunk_items=0):
+        """items per chunk: 0 = the default, nothing above it.  For measurements and tests: the bytes do not depend on it."""
+        self._check(self._L.masp_hip_redjubjub_sign_configure(self._h, int(chunk_items)))
+
+    def redjubjub_sign_last_timing(self):
+        """(upload ms, kernel ms, download ms) of the last redjubjub_sign_batch call of this context, HIP events summed over its chunks"""
+        return self._timing(self._L.masp_hip_redjubjub_sign_last_timing, 3)
+
+    def build_spends(self, asset_identifiers, values, diversifiers, pk_ds, lead_bytes, rseeds, aks, nsks, ars, rcvs, positions,
+                     want_cmus=True, want_nks=True):
+        """cv, rk, nf, cmu and nk of n spends on the GPU (masp_hip_sapling_build_spends).  Arrays in, in the C ABI's order (n x 32 bytes each,
+        diversifiers n x 11, values / lead bytes / positions n) -> (status uint8[n], cvs, rks, nfs uint8[n, 32], cmus, nks uint8[n, 32] or
+        None where not wanted: not downloaded).  status: 0, or 1 asset identifier, 2 diversifier, 3 pk_d, 4 lead byte or rcm, 5 ak does not
+        decode, 6 ak of small order, 7 nsk, 8 ar, 9 rcv; such a spend's outputs are zeros.  No randomness is drawn.  host.build_spends is
+        the same on the host."""
+        from .host import build_spend_args, build_spend_results
+        args = build_spend_args(asset_identifiers, values, diversifiers, pk_ds, lead_bytes, rseeds, aks, nsks, ars, rcvs, positions)
+        n = args[0].shape[0]
+        res = build_spend_results(n, want_cmus, want_nks)
+        p = lambda a: _p(a) if a is not None and a.size else None
+        self._check(self._L.masp_hip_sapling_build_spends(self._h, n, *[p(a) for a in args], *[p(a) for a in res]))
+        return res
+
+    def build_spends_configure(self, chunk_spends=0):
+        """spends per chunk: 0 = the default, nothing above it.  For measurements and tests: the bytes do not depend on it."""
+        self._check(self._L.masp_hip_build_spends_configure(self._h, int(chunk_spends)))
+
+    def build_spends_last_timing(self):
+        """(upload ms, kernel ms, download ms) of the last build_spends call of this context, HIP events summed over its chunks"""
+        return self._timing(self._L.masp_hip_build_spends_last_timing, 3)
 
     # ---- building blocks ----
     def msm_g1(self, bases, scalars):

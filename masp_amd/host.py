@@ -60,6 +60,8 @@ def load_library():
         L.masp_host_note_cmu.argtypes = [cp, u64, cp, cp, cp, cp]
         L.masp_host_sapling_note_nullifiers.argtypes = [C.c_size_t, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int]
         L.masp_host_sapling_build_outputs.argtypes = [C.c_size_t] + [vp] * 18 + [C.c_int]
+        L.masp_host_redjubjub_sign_batch.argtypes = [C.c_size_t] + [vp] * 8 + [C.c_int]
+        L.masp_host_sapling_build_spends.argtypes = [C.c_size_t] + [vp] * 17 + [C.c_int]
         L.masp_host_merkle_hash.argtypes = [C.c_uint, cp, cp, cp]
         L.masp_host_merkle_empty_roots.argtypes = [vp]
         L.masp_host_merkle_empty_roots.restype = None
@@ -463,6 +465,70 @@ def build_outputs(asset_identifiers, values, diversifiers, pk_ds, lead_bytes, rs
     res = build_output_results(n)
     vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
     _check(load_library().masp_host_sapling_build_outputs(n, *[vp(a) for a in args], *[vp(a) for a in res], int(threads or effective_cpus())))
+    return res
+
+
+def _rows(a, w):
+    if a is None:
+        return None
+    if isinstance(a, (bytes, bytearray, memoryview)):
+        a = np.frombuffer(a, dtype=np.uint8)
+    return np.ascontiguousarray(a, dtype=np.uint8).reshape(-1, w) if w else np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+
+
+def sign_batch_args(sks, alphas, sighashes, kinds, randoms):
+    """the arguments of either redjubjub_sign_batch as contiguous arrays, in the C ABI's order: uint8[n, 32] (bytes or arrays), uint8[n],
+    uint8[n, 80]; alphas may be None and stays None"""
+    out = (_rows(sks, 32), _rows(alphas, 32), _rows(sighashes, 32), _rows(kinds, 0), _rows(randoms, 80))
+    n = out[0].shape[0]
+    if any(a is not None and a.shape[0] != n for a in out):
+        raise ValueError("redjubjub_sign_batch: the arrays differ in length: %s" % ([None if a is None else a.shape[0] for a in out],))
+    return out
+
+
+def redjubjub_sign_batch(sks, alphas, sighashes, kinds, randoms, threads=None, want_vks=True):
+    """masp_host_redjubjub_sign_batch: n RedJubjub signatures on host threads (default: effective_cpus()): rsk = sk + alpha, vk = [rsk] G_kind,
+    sig = Rbar | S with the nonce from the item's 80 bytes of randoms.  sks, alphas (or None: no randomisation), sighashes n x 32, kinds n
+    (0 spend authorisation, 1 binding), randoms n x 80 -> (status uint8[n], vks uint8[n, 32] or None with want_vks=False, sigs uint8[n, 64]).
+    status: 0, or 1 sk >= r_J, 2 alpha >= r_J; such an item's outputs are zeros.  No randomness is drawn."""
+    args = sign_batch_args(sks, alphas, sighashes, kinds, randoms)
+    n = args[0].shape[0]
+    status, sigs = np.zeros(n, np.uint8), np.zeros((n, 64), np.uint8)
+    vks = np.zeros((n, 32), np.uint8) if want_vks else None
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    _check(load_library().masp_host_redjubjub_sign_batch(n, *[vp(a) for a in args], vp(status), vp(vks), vp(sigs), int(threads or effective_cpus())))
+    return status, vks, sigs
+
+
+def build_spend_args(asset_identifiers, values, diversifiers, pk_ds, lead_bytes, rseeds, aks, nsks, ars, rcvs, positions):
+    """the arguments of either build_spends as contiguous arrays, in the C ABI's order: uint8[n, 32] (bytes or arrays), uint64[n],
+    uint8[n, 11], uint8[n]"""
+    out = (_rows(asset_identifiers, 32), np.ascontiguousarray(values, dtype=np.uint64).reshape(-1), _rows(diversifiers, 11), _rows(pk_ds, 32),
+           _rows(lead_bytes, 0), _rows(rseeds, 32), _rows(aks, 32), _rows(nsks, 32), _rows(ars, 32), _rows(rcvs, 32),
+           np.ascontiguousarray(positions, dtype=np.uint64).reshape(-1))
+    n = out[0].shape[0]
+    if any(a.shape[0] != n for a in out):
+        raise ValueError("build_spends: the arrays differ in length: %s" % ([a.shape[0] for a in out],))
+    return out
+
+
+def build_spend_results(n, want_cmus=True, want_nks=True):
+    """(status uint8[n], cvs, rks, nfs uint8[n, 32], cmus, nks uint8[n, 32] or None), zeroed"""
+    z = lambda: np.zeros((n, 32), np.uint8)
+    return (np.zeros(n, np.uint8), z(), z(), z(), z() if want_cmus else None, z() if want_nks else None)
+
+
+def build_spends(asset_identifiers, values, diversifiers, pk_ds, lead_bytes, rseeds, aks, nsks, ars, rcvs, positions, threads=None,
+                 want_cmus=True, want_nks=True):
+    """masp_host_sapling_build_spends: cv, rk, nf, cmu and nk of n spends on host threads (default: effective_cpus()).  Arrays in, in the C
+    ABI's order (n x 32 bytes each, diversifiers n x 11, values / lead bytes / positions n) -> (status uint8[n], cvs, rks, nfs uint8[n, 32],
+    cmus, nks uint8[n, 32] or None where not wanted).  status: 0, or 1 asset identifier, 2 diversifier, 3 pk_d, 4 lead byte or rcm, 5 ak does
+    not decode, 6 ak of small order, 7 nsk, 8 ar, 9 rcv; such a spend's outputs are zeros.  No randomness is drawn."""
+    args = build_spend_args(asset_identifiers, values, diversifiers, pk_ds, lead_bytes, rseeds, aks, nsks, ars, rcvs, positions)
+    n = args[0].shape[0]
+    res = build_spend_results(n, want_cmus, want_nks)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    _check(load_library().masp_host_sapling_build_spends(n, *[vp(a) for a in args], *[vp(a) for a in res], int(threads or effective_cpus())))
     return res
 
 

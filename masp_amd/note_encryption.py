@@ -19,7 +19,8 @@ Once a note is the wallet's: `note_nf` is Note::nf(&nk, position) on the host, a
 nullifiers of a list of notes on the GPU (masp_hip_sapling_note_nullifiers) or on host threads.
 
 Making outputs: `batch.build_outputs` turns output plans into `OutputDescription`s without their proofs, cv, cmu, epk and the two
-ciphertexts, on the GPU (masp_hip_sapling_build_outputs) or on host threads."""
+ciphertexts, on the GPU (masp_hip_sapling_build_outputs) or on host threads.  Making spends: `batch.build_spends` turns spend plans into
+what the builder puts around a Spend proof, cv, rk and nf with cmu and nk, on the GPU (masp_hip_sapling_build_spends) or on host threads."""
 import os
 from collections import namedtuple
 
@@ -93,6 +94,21 @@ def _build_output_arrays(plans):
             np.array([int(p[1].rseed.lead_byte) & 0xff for p in plans], dtype=np.uint8), cat(lambda p: H._b(p[1].rseed.bytes)), esks,
             cat(lambda p: scalar(p[4])), cat(lambda p: H._b(EMPTY_MEMO if p[3] is None else p[3], MEMO_SIZE)), cat(lambda p: scalar(p[0])),
             flags, randoms)
+
+
+BUILD_SPEND_STATUS = {1: "the asset identifier has no generator", 2: "the diversifier has no g_d", 3: "pk_d does not decode",
+                      4: "the lead byte is neither 1 nor 2, or rcm is not below r_J", 5: "ak does not decode", 6: "ak is of small order",
+                      7: "nsk is not below r_J", 8: "ar is not below r_J", 9: "rcv is not below r_J"}
+
+
+def _build_spend_arrays(plans):
+    """plans: ((ak, nsk), Note, PaymentAddress, position, ar, rcv) each -> the eleven arrays of either build_spends"""
+    cat = lambda f: np.frombuffer(b"".join(f(p) for p in plans), dtype=np.uint8)
+    return (cat(lambda p: H._b(p[1].asset_identifier)), np.array([int(p[1].value) for p in plans], dtype=np.uint64),
+            cat(lambda p: H._b(p[2].diversifier, 11)), cat(lambda p: H._b(p[1].pk_d)),
+            np.array([int(p[1].rseed.lead_byte) & 0xff for p in plans], dtype=np.uint8), cat(lambda p: H._b(p[1].rseed.bytes)),
+            cat(lambda p: H._b(p[0][0])), cat(lambda p: H._b(p[0][1])), cat(lambda p: H._b(p[4])), cat(lambda p: H._b(p[5])),
+            np.array([int(p[3]) for p in plans], dtype=np.uint64))
 
 
 def note_nf(note, to, nk, position):
@@ -238,6 +254,20 @@ class batch:
         status, cvs, cmus, epks, encs, couts = H.build_outputs(*arrays, threads=threads) if ctx is None else ctx.build_outputs(*arrays)
         return [None if s else OutputDescription(cv.tobytes(), cmu.tobytes(), epk.tobytes(), enc.tobytes(), cout.tobytes())
                 for s, cv, cmu, epk, enc, cout in zip(status.tolist(), cvs, cmus, epks, encs, couts)]
+
+    @staticmethod
+    def build_spends(plans, ctx, threads=None):
+        """plans: ((ak, nsk), Note, PaymentAddress, position, ar, rcv) each -> one entry per plan, in order: (cv, rk, nf, cmu, nk), 32 bytes
+        each, what the builder puts around a Spend proof and the nk it derived on the way, or None where the plan is refused
+        (BUILD_SPEND_STATUS).  (ak, nsk): the proof generation key; nsk, ar, rcv: 32 bytes or an int.  The anchor is the caller's, from the
+        tree.  A function of its inputs.  ctx: a masp_amd.Context, the spends are built on its GPU (masp_hip_sapling_build_spends); None: on
+        `threads` host threads."""
+        plans = list(plans)
+        if not plans:
+            return []
+        arrays = _build_spend_arrays(plans)
+        status, cvs, rks, nfs, cmus, nks = H.build_spends(*arrays, threads=threads) if ctx is None else ctx.build_spends(*arrays)
+        return [None if s else tuple(a.tobytes() for a in row) for s, *row in zip(status.tolist(), cvs, rks, nfs, cmus, nks)]
 
     @staticmethod
     def try_output_recovery(ovks, outputs, ctx, lead_byte=2):

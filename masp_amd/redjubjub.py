@@ -2,9 +2,15 @@
 (/root/reference/masp_proofs/src/sapling/prover.rs:279-326), restated from
 /root/reference/masp_primitives/src/sapling/redjubjub.rs:36-38,138-160,166-169,191-239 and
 masp_primitives/src/sapling/util.rs:9-15.  Host-side and tiny: it closes the `TxProver` surface around the GPU prover;
-group arithmetic goes through libmasp_host's Jubjub (`host.jubjub_mul / jubjub_add`)."""
+group arithmetic goes through libmasp_host's Jubjub (`host.jubjub_mul / jubjub_add`).
+
+Signing in batches: `sign_batch` and `spend_sigs` run `spend_sig_internal` (masp_primitives/src/sapling.rs:167-195) for many items in one
+call, on the GPU (masp_hip_redjubjub_sign_batch) or on host threads (masp_host_redjubjub_sign_batch)."""
 import hashlib
+import os
 import secrets
+
+import numpy as np
 
 from . import host as H
 
@@ -47,3 +53,26 @@ def verify(vk, msg, sig, generator):
         return H.jubjub_mul(acc, 8) == H.JUBJUB_IDENTITY
     except (H.HostError, ValueError):
         return False            # R or vk is not a canonical point encoding
+
+
+def sign_batch(items, ctx, threads=None, rng=os.urandom):
+    """items: (sk, alpha or None, sighash, kind) each -> one entry per item, in order: (vk, sig), 32 and 64 bytes, or None where the item is
+    refused (sk or alpha not below r_J).  Per item rsk = sk + alpha, vk = [rsk] G_kind and sig = PrivateKey::sign(rsk, vk || sighash): what
+    spend_sig_internal returns next to the rk it signs under.  kind: 0 spend authorisation, 1 binding.  sk, alpha: 32 bytes or an int;
+    rng(80) draws each item's T, and everything below that is a function of its inputs.  ctx: a masp_amd.Context, the items are signed on
+    its GPU (masp_hip_redjubjub_sign_batch); None: on `threads` host threads."""
+    items = list(items)
+    if not items:
+        return []
+    cat = lambda f: np.frombuffer(b"".join(f(it) for it in items), dtype=np.uint8)
+    alphas = None if all(it[1] is None for it in items) else cat(lambda it: bytes(32) if it[1] is None else H._b(it[1]))
+    arrays = (cat(lambda it: H._b(it[0])), alphas, cat(lambda it: H._b(it[2])), np.array([int(it[3]) for it in items], dtype=np.uint8),
+              cat(lambda it: H._b(rng(80), 80)))
+    status, vks, sigs = H.redjubjub_sign_batch(*arrays, threads=threads) if ctx is None else ctx.redjubjub_sign_batch(*arrays)
+    return [None if s else (vk.tobytes(), sig.tobytes()) for s, vk, sig in zip(status.tolist(), vks, sigs)]
+
+
+def spend_sigs(asks, ars, sighash, ctx, threads=None, rng=os.urandom):
+    """The loop a builder runs over its spends: one sighash, spend i signed with ask_i randomised by ar_i -> (rk, spend_auth_sig) per spend,
+    or None where ask_i or ar_i is not below r_J.  ctx, threads, rng: as sign_batch."""
+    return sign_batch([(ask, ar, sighash, 0) for ask, ar in zip(asks, ars)], ctx, threads=threads, rng=rng)
