@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "chunk_pipeline.h"
+#include "column_call.h"
 #include "host/eval_form.h"
 #include "device/io.hpp"
 #include "device/ntt_geom.h"
@@ -331,6 +332,25 @@ struct JubjubState {
     LastTiming<3> bc_timing;          // masp_hip_check_bundles_last_timing: upload, kernels, download
 };
 
+// What a per-item call (column_call.h, column_host.h) keeps between calls: a chunk's arrays as they come, the per-item state, the results
+// as they leave with the status bytes last, and the pinned staging of the secret inputs if it has any (it, the uploaded inputs and the
+// state are zeroed before such a call releases the lock).  Every buffer holds ColumnCall::n_pad items.
+struct PerItemCall {
+    DevBuf<uint8_t> in, state, out;
+    PinnedBuf<uint8_t> stage;
+    std::atomic<size_t> chunk{0};   // the call's configure: items per chunk, 0 = the default
+    LastTiming<3> timing;           // the call's last_timing: upload, kernels, download
+    // room for cc's chunks with state_bytes of state an item; cc gets the buffers
+    int reserve(ColumnCall& cc, size_t state_bytes) {
+        const size_t n = cc.n_pad;
+        int rc;
+        if ((rc = in.reserve(cc.iw.total * n)) || (rc = state.reserve(state_bytes * n)) || (rc = out.reserve(cc.ow.total * n)) || (rc = stage.reserve(cc.iw.stage_total * n)))
+            return rc;
+        cc.d_in = in.p, cc.d_out = out.p, cc.stage = stage.p;
+        return MASP_HIP_OK;
+    }
+};
+
 // What the wallet-side entry points of a device context keep between calls: the note scan (k_note_scan.hip), the compact note scan
 // (k_note_scan_compact.hip), the output recovery scan (k_out_recovery.hip), the commitment trees (k_merkle.hip), the note nullifiers
 // (k_nullifier.hip), the allowed conversions (k_conversion.hip), the output descriptions (k_output_build.hip) and the spend descriptions with their signatures (k_spend_build.hip).  One of these calls runs at a time per context: `mu` guards every member but the atomics and the timing records, and is
@@ -369,12 +389,10 @@ struct WalletState {
     OnceTable<uint32_t> mt_empties;
     DevBuf<uint64_t> mt_pos;
     LastTiming<3> mt_timing;          // masp_hip_merkle_last_timing: upload, kernels, download
-    // the nullifiers: a table of their own beside nsc_table (nullifier_table.h: the windows of G_ncr and G_nf), a chunk's arrays as they
-    // come, the per-note state, and cmu | nf | status
+    // the nullifiers: a table of their own beside nsc_table (nullifier_table.h: the windows of G_ncr and G_nf)
     OnceTable<uint8_t> nf_table;
-    DevBuf<uint8_t> nf_in, nf_state, nf_out;
+    PerItemCall nf;
     std::atomic<int> nf_lanes{0};     // masp_hip_note_nullifiers_configure: lanes per note, 0 = by the number of notes
-    LastTiming<3> nf_timing;          // masp_hip_note_nullifiers_last_timing: upload, kernels, download
     // the allowed conversions (k_conversion.hip), on nsc_table's Pedersen points: a chunk's offsets, identifiers and values as they come, the
     // terms' points with their status bytes behind them, and generator | cmu | status
     DevBuf<uint8_t> cv_in, cv_terms, cv_out;
@@ -382,21 +400,13 @@ struct WalletState {
     std::atomic<size_t> cv_chunk_conv{0}, cv_chunk_terms{0};   // ... and a chunk's limits, 0 = the defaults
     LastTiming<3> cv_timing;          // masp_hip_allowed_conversions_last_timing: upload, kernels, download
     // the output descriptions (k_output_build.hip), on nsc_table's Pedersen points and nf_table's G_ncr windows: G_vcr's windows
-    // (output_table.h), a chunk's arrays as they come, the memos in columns, the per-output state, the two ciphertexts in columns, and
-    // cv | cmu | epk | enc_ciphertext | out_ciphertext | status as they leave
+    // (output_table.h), the memos as they come and in columns, and the two ciphertexts in columns
     OnceTable<uint8_t> ob_table;
-    DevBuf<uint8_t> ob_in, ob_memo, ob_state, ob_cols, ob_out;
-    std::atomic<size_t> ob_chunk{0};  // masp_hip_build_outputs_configure: outputs per chunk, 0 = the default
-    LastTiming<3> ob_timing;          // masp_hip_build_outputs_last_timing: upload, kernels, download
-    // the spend descriptions and the RedJubjub signatures (k_spend_build.hip), on the tables above: the windows of G_spend and G_pgk
-    // (spend_table.h), and per call kind a chunk's arrays as they come, the per-item state and the results as they leave.  The secret
-    // inputs pass through a pinned staging buffer; it, the uploaded secrets and the states are zeroed before a call releases the lock.
+    PerItemCall ob;
+    DevBuf<uint8_t> ob_memo, ob_cols;
+    // the spend descriptions and the RedJubjub signatures (k_spend_build.hip), on the tables above: the windows of G_spend and G_pgk (spend_table.h)
     OnceTable<uint8_t> sb_table;
-    DevBuf<uint8_t> sb_in, sb_state, sb_out, rs_in, rs_state, rs_out;
-    PinnedBuf<uint8_t> sb_stage, rs_stage;
-    std::atomic<size_t> sb_chunk{0};  // masp_hip_build_spends_configure: spends per chunk, 0 = the default
-    std::atomic<size_t> rs_chunk{0};  // masp_hip_redjubjub_sign_configure: items per chunk, 0 = the default
-    LastTiming<3> sb_timing, rs_timing;   // masp_hip_build_spends_last_timing, masp_hip_redjubjub_sign_last_timing: upload, kernels, download
+    PerItemCall sb, rs;
     // The end of a call that may have uploaded tables: one that failed with a HIP error cannot tell whether they arrived, so they are released
     // and the next call uploads them again; any other end confirms them.  A table of an earlier call is not marked and survives either way.
     void settle_tables(int rc) {

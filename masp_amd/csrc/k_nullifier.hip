@@ -101,7 +101,7 @@ inline void nf_enqueue(hipStream_t s, const NfArgs& a, int lanes) {
 }  // namespace masp
 
 #ifndef MASP_NF_KERNELS_ONLY   // (tests/native/nullifier_dev.hip runs the kernels above for both lane widths without a context)
-#include "internal.h"
+#include "column_host.h"
 #include "nullifier_table.h"
 
 using namespace masp;
@@ -110,6 +110,9 @@ namespace {
 
 constexpr size_t NF_MAX_NOTES = (size_t)1 << 22;
 constexpr size_t NF_CHUNK = (size_t)1 << 19;   // notes per launch sequence: 272 bytes of state, 156 in and 65 out a note, 250 MB in all
+constexpr ColumnWidths NF_IN{32, 32, 32, 32, 8, 8, 11, 1};   // ids, pk_ds, rseeds, nks, values, positions, diversifiers, lead bytes
+constexpr ColumnWidths NF_OUT{32, 32, 1};                    // cmus, nfs, status
+static_assert(sizeof(NfState) == 272 && NF_IN.total == 156 && NF_OUT.total == 65, "NF_CHUNK's sizing");
 
 struct NfHost {
     const uint8_t *ids, *divs, *pk_ds, *leads, *rseeds, *nks;
@@ -117,59 +120,24 @@ struct NfHost {
     uint8_t *status, *cmus, *nfs;
 };
 
-// everything of one call on the context's first verifier stream, chunk after chunk; the caller is a WalletCall
+// everything of one call on the context's first verifier stream, chunk after chunk; the caller is a WalletCall and ends it (end_per_item)
 int run_nullifiers(masp_hip_ctx* ctx, size_t n, const NfHost& h) {
     WalletState& w = ctx->wallet;
     hipStream_t s = ctx->streams.vk[0];
-    const size_t cap = std::min(NF_CHUNK, (n + 63) / 64 * 64);   // every array of the input buffer starts on a multiple of 8 bytes
+    ColumnCall cc(NF_IN, NF_OUT, column_chunk(0, NF_CHUNK, n));
     int rc;
-    if ((rc = w.nf_in.reserve(156 * cap)) || (rc = w.nf_state.reserve(sizeof(NfState) * cap)) || (rc = w.nf_out.reserve(65 * cap)))
-        return rc;
-    if ((rc = pedersen_table_ensure(w, s)) || (rc = nullifier_table_ensure(w, s))) return rc;
-    uint8_t* in = w.nf_in.p;
-    uint8_t *d_ids = in, *d_pk = in + 32 * cap, *d_rs = in + 64 * cap, *d_nk = in + 96 * cap, *d_val = in + 128 * cap, *d_pos = in + 136 * cap,
-            *d_div = in + 144 * cap, *d_lead = in + 155 * cap;
-    uint8_t *d_cmu = w.nf_out.p, *d_nf = d_cmu + 32 * cap, *d_status = d_cmu + 64 * cap;
-    NfArgs a;
-    a.in = {(const uint32_t*)d_ids, (const uint64_t*)d_val, d_div, (const uint32_t*)d_pk, d_lead, (const uint32_t*)d_rs, (const uint32_t*)d_nk,
-            (const uint64_t*)d_pos};
-    a.state = (NfState*)w.nf_state.p;
+    if ((rc = w.nf.reserve(cc, sizeof(NfState))) || (rc = pedersen_table_ensure(w, s)) || (rc = nullifier_table_ensure(w, s))) return rc;
+    NfArgs a;   // (the columns in NF_IN's and NF_OUT's order)
+    a.in.ids = cc.in<uint32_t>(h.ids), a.in.pk_ds = cc.in<uint32_t>(h.pk_ds), a.in.rseeds = cc.in<uint32_t>(h.rseeds);
+    a.in.nks = cc.in<uint32_t>(h.nks), a.in.values = cc.in<uint64_t>(h.values), a.in.positions = cc.in<uint64_t>(h.positions);
+    a.in.diversifiers = cc.in(h.divs), a.in.leads = cc.in(h.leads);
+    a.state = (NfState*)w.nf.state.p;
     a.ped = (const JNiels*)w.nsc_table.p;
     a.tab = (const JNiels*)w.nf_table.p;
-    a.status = d_status;
-    a.cmus = (uint32_t*)d_cmu;
-    a.nfs = (uint32_t*)d_nf;
+    a.cmus = cc.out<uint32_t>(h.cmus), a.nfs = cc.out<uint32_t>(h.nfs), a.status = cc.out(h.status);
     const int forced = w.nf_lanes.load();
     const int lanes = forced ? forced : n < NF_WIDE_BELOW ? 8 : 1;
-    Event ev[4];
-    if ((rc = create_events(ev))) return rc;
-    double ms[3] = {0, 0, 0};
-    for (size_t o = 0; o < n; o += cap) {
-        const size_t c = std::min(cap, n - o);
-        HIP_TRY(hipEventRecord(ev[0], s));
-        HIP_TRY(hipMemcpyAsync(d_ids, h.ids + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_pk, h.pk_ds + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_rs, h.rseeds + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_nk, h.nks + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_val, h.values + o, 8 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_pos, h.positions + o, 8 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_div, h.divs + 11 * o, 11 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_lead, h.leads + o, c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemsetAsync(d_cmu, 0, 64 * cap, s));   // a refused note's outputs are zeros
-        HIP_TRY(hipEventRecord(ev[1], s));
-        a.n = (uint32_t)c;
-        nf_enqueue(s, a, lanes);
-        HIP_TRY(hipEventRecord(ev[2], s));
-        HIP_TRY(hipMemcpyAsync(h.status + o, d_status, c, hipMemcpyDeviceToHost, s));
-        if (h.cmus) HIP_TRY(hipMemcpyAsync(h.cmus + 32 * o, d_cmu, 32 * c, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h.nfs + 32 * o, d_nf, 32 * c, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipEventRecord(ev[3], s));
-        HIP_TRY(hipStreamSynchronize(s));   // the next chunk overwrites the buffers
-        if (launch_status() != MASP_HIP_OK) return MASP_HIP_E_HIP;   // a refused launch: the buffers mean nothing
-        if ((rc = add_elapsed(ev, 3, ms))) return rc;
-    }
-    w.nf_timing.store(ms);
-    return MASP_HIP_OK;
+    return run_per_item(s, w.nf, cc, n, [&](size_t c) { a.n = (uint32_t)c, nf_enqueue(s, a, lanes); });
 }
 
 }  // namespace
@@ -187,9 +155,7 @@ int masp_hip_sapling_note_nullifiers(masp_hip_ctx* ctx, size_t n, const uint8_t*
     (void)nullifier_table();
     WalletCall call(ctx);
     const NfHost h = {asset_identifiers, diversifiers, pk_ds, lead_bytes, rseeds, nks, values, positions, status, cmus_out, nfs_out};
-    const int rc = run_nullifiers(call.ctx, n, h);
-    if (rc == MASP_HIP_E_HIP) (void)hipStreamSynchronize(call.ctx->streams.vk[0]);   // nothing of this call stays in flight
-    return call.done(rc);
+    return call.done(end_per_item(call.ctx->streams.vk[0], call.w.nf, NF_IN, run_nullifiers(call.ctx, n, h)));
 }
 
 int masp_hip_note_nullifiers_configure(masp_hip_ctx* ctx, int lanes_per_note) {
@@ -198,11 +164,7 @@ int masp_hip_note_nullifiers_configure(masp_hip_ctx* ctx, int lanes_per_note) {
     return MASP_HIP_OK;
 }
 
-int masp_hip_note_nullifiers_last_timing(masp_hip_ctx* ctx, double ms[3]) {
-    if (!ctx || !ms) return MASP_HIP_E_INVALID_ARG;
-    FIRST_DEVICE(ctx)->wallet.nf_timing.load(ms);
-    return MASP_HIP_OK;
-}
+int masp_hip_note_nullifiers_last_timing(masp_hip_ctx* ctx, double ms[3]) { return per_item_last_timing(ctx, &WalletState::nf, ms); }
 
 }  // extern "C"
 #endif   // MASP_NF_KERNELS_ONLY

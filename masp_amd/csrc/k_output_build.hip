@@ -121,7 +121,7 @@ inline void ob_enqueue(hipStream_t s, const ObArgs& a) {
 }  // namespace masp
 
 #ifndef MASP_OB_KERNELS_ONLY   // (tests/native/output_build_dev.hip runs the kernels above without a context)
-#include "internal.h"
+#include "column_host.h"
 #include "output_table.h"
 
 using namespace masp;
@@ -131,6 +131,11 @@ namespace {
 constexpr size_t OB_MAX_OUTPUTS = (size_t)1 << 20;
 // outputs per launch sequence: 309 bytes in, 512 of memo twice, 592 of state, 704 of columns and 789 out an output, 225 MB in all
 constexpr size_t OB_CHUNK = (size_t)1 << 16;
+// ids, pk_ds, rseeds, esks, rcvs, ovks, out_randoms, values, diversifiers, lead bytes, ovk flags
+constexpr ColumnWidths OB_IN{32, 32, 32, 32, 32, 32, 96, 8, 11, 1, 1};
+constexpr ColumnWidths OB_OUT{32, 32, 32, 4 * OB_ENC_WORDS, 4 * OB_OUT_WORDS, 1};   // cvs, cmus, epks, enc_ciphertexts, out_ciphertexts, status
+constexpr size_t OB_MEMO = 16 * OB_MEMO_COLS;
+static_assert(OB_IN.total == 309 && OB_MEMO == 512 && sizeof(ObState) == 592 && 16 * OB_COLS == 704 && OB_OUT.total == 789, "OB_CHUNK's sizing");
 
 struct ObHost {
     const uint8_t *ids, *divs, *pk_ds, *leads, *rseeds, *esks, *rcvs, *memos, *ovks, *flags, *randoms;
@@ -138,77 +143,32 @@ struct ObHost {
     uint8_t *status, *cvs, *cmus, *epks, *encs, *couts;
 };
 
-// everything of one call on the context's first verifier stream, chunk after chunk; the caller is a WalletCall
+// everything of one call on the context's first verifier stream, chunk after chunk; the caller is a WalletCall and ends it (end_per_item)
 int run_build_outputs(masp_hip_ctx* ctx, size_t n, const ObHost& h) {
     WalletState& w = ctx->wallet;
     hipStream_t s = ctx->streams.vk[0];
-    const size_t configured = w.ob_chunk.load();
-    const size_t cap = std::min(configured ? configured : OB_CHUNK, (n + 63) / 64 * 64);   // every array of the input buffer starts on a multiple of 8 bytes
-    const size_t n_pad = (cap + OB_BLOCK - 1) / OB_BLOCK * OB_BLOCK;
+    ColumnCall cc(OB_IN, OB_OUT, column_chunk(w.ob.chunk.load(), OB_CHUNK, n));
     int rc;
-    if ((rc = w.ob_in.reserve(309 * n_pad)) || (rc = w.ob_state.reserve(sizeof(ObState) * n_pad)) || (rc = w.ob_cols.reserve(16 * (size_t)OB_COLS * n_pad)) ||
-        (rc = w.ob_out.reserve(789 * n_pad)) || (h.memos && (rc = w.ob_memo.reserve(2 * 512 * n_pad))))
+    if ((rc = w.ob.reserve(cc, sizeof(ObState))) || (rc = w.ob_cols.reserve(16 * (size_t)OB_COLS * cc.n_pad)) ||
+        (h.memos && (rc = w.ob_memo.reserve(2 * OB_MEMO * cc.n_pad))) || (rc = pedersen_table_ensure(w, s)) || (rc = nullifier_table_ensure(w, s)) ||
+        (rc = output_table_ensure(w, s)))
         return rc;
-    if ((rc = pedersen_table_ensure(w, s)) || (rc = nullifier_table_ensure(w, s)) || (rc = output_table_ensure(w, s))) return rc;
-    uint8_t* in = w.ob_in.p;
-    uint8_t *d_ids = in, *d_pk = in + 32 * n_pad, *d_rs = in + 64 * n_pad, *d_esk = in + 96 * n_pad, *d_rcv = in + 128 * n_pad, *d_ovk = in + 160 * n_pad,
-            *d_rnd = in + 192 * n_pad, *d_val = in + 288 * n_pad, *d_div = in + 296 * n_pad, *d_lead = in + 307 * n_pad, *d_flag = in + 308 * n_pad;
-    uint8_t* out = w.ob_out.p;
-    uint8_t *d_cv = out, *d_cmu = out + 32 * n_pad, *d_epk = out + 64 * n_pad, *d_enc = out + 96 * n_pad, *d_cout = out + 708 * n_pad, *d_status = out + 788 * n_pad;
-    ObArgs a;
-    a.in = {(const uint32_t*)d_ids, (const uint64_t*)d_val, d_div, (const uint32_t*)d_pk, d_lead, (const uint32_t*)d_rs,
-            h.esks ? (const uint32_t*)d_esk : nullptr, (const uint32_t*)d_rcv, (const uint32_t*)d_ovk, h.flags ? d_flag : nullptr,
-            h.randoms ? (const uint32_t*)d_rnd : nullptr};
-    a.state = (ObState*)w.ob_state.p;
+    ObArgs a;   // (the columns in OB_IN's and OB_OUT's order; the memo rows go up behind them into a buffer of their own)
+    a.in.ids = cc.in<uint32_t>(h.ids), a.in.pk_ds = cc.in<uint32_t>(h.pk_ds), a.in.rseeds = cc.in<uint32_t>(h.rseeds);
+    a.in.esks = cc.in<uint32_t>(h.esks), a.in.rcvs = cc.in<uint32_t>(h.rcvs), a.in.ovks = cc.in<uint32_t>(h.ovks);
+    a.in.out_randoms = cc.in<uint32_t>(h.randoms), a.in.values = cc.in<uint64_t>(h.values), a.in.diversifiers = cc.in(h.divs);
+    a.in.leads = cc.in(h.leads), a.in.ovk_flags = cc.in(h.flags);
+    a.memo_rows = cc.in_at<uint4>(w.ob_memo.p, OB_MEMO, h.memos);
+    a.memo_cols = h.memos ? (uint4*)(w.ob_memo.p + OB_MEMO * cc.n_pad) : nullptr;
+    a.state = (ObState*)w.ob.state.p;
     a.ped = (const JNiels*)w.nsc_table.p;
     a.ncr = (const JNiels*)w.nf_table.p;
     a.vcr = (const JNiels*)w.ob_table.p;
-    a.memo_rows = h.memos ? (const uint4*)w.ob_memo.p : nullptr;
-    a.memo_cols = h.memos ? (uint4*)(w.ob_memo.p + 512 * n_pad) : nullptr;
     a.cols = (uint4*)w.ob_cols.p;
-    a.status = d_status;
-    a.cvs = (uint32_t*)d_cv;
-    a.cmus = (uint32_t*)d_cmu;
-    a.epks = (uint32_t*)d_epk;
-    a.encs = (uint32_t*)d_enc;
-    a.couts = (uint32_t*)d_cout;
-    a.n_pad = (uint32_t)n_pad;
-    Event ev[4];
-    if ((rc = create_events(ev))) return rc;
-    double ms[3] = {0, 0, 0};
-    for (size_t o = 0; o < n; o += cap) {
-        const size_t c = std::min(cap, n - o);
-        HIP_TRY(hipEventRecord(ev[0], s));
-        HIP_TRY(hipMemcpyAsync(d_ids, h.ids + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_pk, h.pk_ds + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_rs, h.rseeds + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
-        if (h.esks) HIP_TRY(hipMemcpyAsync(d_esk, h.esks + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_rcv, h.rcvs + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_ovk, h.ovks + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
-        if (h.randoms) HIP_TRY(hipMemcpyAsync(d_rnd, h.randoms + 96 * o, 96 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_val, h.values + o, 8 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_div, h.divs + 11 * o, 11 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_lead, h.leads + o, c, hipMemcpyHostToDevice, s));
-        if (h.flags) HIP_TRY(hipMemcpyAsync(d_flag, h.flags + o, c, hipMemcpyHostToDevice, s));
-        if (h.memos) HIP_TRY(hipMemcpyAsync(w.ob_memo.p, h.memos + 512 * o, 512 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemsetAsync(out, 0, 788 * n_pad, s));   // a refused output's outputs are zeros
-        HIP_TRY(hipEventRecord(ev[1], s));
-        a.n = (uint32_t)c;
-        ob_enqueue(s, a);
-        HIP_TRY(hipEventRecord(ev[2], s));
-        HIP_TRY(hipMemcpyAsync(h.status + o, d_status, c, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h.cvs + 32 * o, d_cv, 32 * c, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h.cmus + 32 * o, d_cmu, 32 * c, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h.epks + 32 * o, d_epk, 32 * c, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h.encs + 612 * o, d_enc, 612 * c, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h.couts + 80 * o, d_cout, 80 * c, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipEventRecord(ev[3], s));
-        HIP_TRY(hipStreamSynchronize(s));   // the next chunk overwrites the buffers
-        if (launch_status() != MASP_HIP_OK) return MASP_HIP_E_HIP;   // a refused launch: the buffers mean nothing
-        if ((rc = add_elapsed(ev, 3, ms))) return rc;
-    }
-    w.ob_timing.store(ms);
-    return MASP_HIP_OK;
+    a.cvs = cc.out<uint32_t>(h.cvs), a.cmus = cc.out<uint32_t>(h.cmus), a.epks = cc.out<uint32_t>(h.epks);
+    a.encs = cc.out<uint32_t>(h.encs), a.couts = cc.out<uint32_t>(h.couts), a.status = cc.out(h.status);
+    a.n_pad = (uint32_t)cc.n_pad;
+    return run_per_item(s, w.ob, cc, n, [&](size_t c) { a.n = (uint32_t)c, ob_enqueue(s, a); });
 }
 
 }  // namespace
@@ -233,22 +193,12 @@ int masp_hip_sapling_build_outputs(masp_hip_ctx* ctx, size_t n, const uint8_t* a
     WalletCall call(ctx);
     const ObHost h = {asset_identifiers, diversifiers, pk_ds,  lead_bytes, rseeds,   esks,     rcvs,     memos,    ovks,
                       ovk_flags,         out_randoms,  values, status,     cvs_out,  cmus_out, epks_out, encs_out, couts_out};
-    const int rc = run_build_outputs(call.ctx, n, h);
-    if (rc == MASP_HIP_E_HIP) (void)hipStreamSynchronize(call.ctx->streams.vk[0]);   // nothing of this call stays in flight
-    return call.done(rc);
+    return call.done(end_per_item(call.ctx->streams.vk[0], call.w.ob, OB_IN, run_build_outputs(call.ctx, n, h)));
 }
 
-int masp_hip_build_outputs_configure(masp_hip_ctx* ctx, size_t chunk_outputs) {
-    if (!ctx || chunk_outputs > OB_CHUNK) return MASP_HIP_E_INVALID_ARG;
-    FIRST_DEVICE(ctx)->wallet.ob_chunk.store(chunk_outputs);
-    return MASP_HIP_OK;
-}
+int masp_hip_build_outputs_configure(masp_hip_ctx* ctx, size_t chunk_outputs) { return per_item_configure(ctx, &WalletState::ob, chunk_outputs, OB_CHUNK); }
 
-int masp_hip_build_outputs_last_timing(masp_hip_ctx* ctx, double ms[3]) {
-    if (!ctx || !ms) return MASP_HIP_E_INVALID_ARG;
-    FIRST_DEVICE(ctx)->wallet.ob_timing.load(ms);
-    return MASP_HIP_OK;
-}
+int masp_hip_build_outputs_last_timing(masp_hip_ctx* ctx, double ms[3]) { return per_item_last_timing(ctx, &WalletState::ob, ms); }
 
 }  // extern "C"
 #endif   // MASP_OB_KERNELS_ONLY

@@ -152,7 +152,7 @@ inline void sb_enqueue(hipStream_t s, const SbArgs& a) {
 }  // namespace masp
 
 #ifndef MASP_SB_KERNELS_ONLY   // (tests/native/spend_build_dev.hip runs the kernels above without a context)
-#include "internal.h"
+#include "column_host.h"
 #include "spend_table.h"
 
 using namespace masp;
@@ -160,79 +160,35 @@ using namespace masp;
 namespace {
 
 constexpr size_t SB_MAX_ITEMS = (size_t)1 << 20;
-// items per launch sequence.  Spends: 252 bytes in, 704 of state and 161 out a spend, 73 MB in all; signatures: 177 in, 132 of state, 97 out.
+// items per launch sequence.  Spends: 252 bytes in, 664 of state and 161 out a spend, 71 MB in all; signatures: 177 in, 132 of state, 97 out.
 constexpr size_t SB_CHUNK = (size_t)1 << 16;
-
-size_t chunk_cap(size_t configured, size_t n) {
-    return std::min(configured ? configured : SB_CHUNK, (n + 63) / 64 * 64);   // every array of the input buffer starts on a multiple of 8 bytes
-}
+// nsks, ars, rcvs (the secret ones stand first: 96 and 144 bytes an item of pinned staging); ids, pk_ds, rseeds, aks, values, positions, diversifiers, lead bytes
+constexpr ColumnWidths SB_IN{{32, 32, 32, 32, 32, 32, 32, 8, 8, 11, 1}, 0b111};
+constexpr ColumnWidths SB_OUT{32, 32, 32, 32, 32, 1};        // cvs, rks, nfs, cmus, nks, status
+constexpr ColumnWidths RS_IN{{32, 32, 80, 32, 1}, 0b111};    // sks, alphas, randoms; sighashes, kinds
+constexpr ColumnWidths RS_OUT{32, 64, 1};                    // vks, sigs, status
+static_assert(SB_IN.total == 252 && sizeof(SbState) == 664 && SB_OUT.total == 161 && SB_IN.stage_total == 96, "SB_CHUNK's sizing: spends");
+static_assert(RS_IN.total == 177 && sizeof(RsState) == 132 && RS_OUT.total == 97 && RS_IN.stage_total == 144, "SB_CHUNK's sizing: signatures");
 
 struct RsHost {
     const uint8_t *sks, *alphas, *sighashes, *kinds, *randoms;
     uint8_t *status, *vks, *sigs;
 };
 
-// everything of one call on the context's first verifier stream, chunk after chunk; the caller is a WalletCall and scrubs behind it
+// everything of one call on the context's first verifier stream, chunk after chunk; the caller is a WalletCall and ends it (end_per_item: the scrub)
 int run_sign(masp_hip_ctx* ctx, size_t n, const RsHost& h) {
     WalletState& w = ctx->wallet;
     hipStream_t s = ctx->streams.vk[0];
-    const size_t cap = chunk_cap(w.rs_chunk.load(), n);
-    const size_t n_pad = (cap + SB_BLOCK - 1) / SB_BLOCK * SB_BLOCK;
+    ColumnCall cc(RS_IN, RS_OUT, column_chunk(w.rs.chunk.load(), SB_CHUNK, n));
     int rc;
-    if ((rc = w.rs_in.reserve(177 * n_pad)) || (rc = w.rs_state.reserve(sizeof(RsState) * n_pad)) || (rc = w.rs_out.reserve(97 * n_pad)) ||
-        (rc = w.rs_stage.reserve(144 * n_pad)))
-        return rc;
-    if ((rc = spend_table_ensure(w, s)) || (rc = output_table_ensure(w, s))) return rc;
-    uint8_t* in = w.rs_in.p;
-    uint8_t *d_sk = in, *d_al = in + 32 * n_pad, *d_rnd = in + 64 * n_pad, *d_sh = in + 144 * n_pad, *d_kind = in + 176 * n_pad;
-    uint8_t *p_sk = w.rs_stage.p, *p_al = p_sk + 32 * n_pad, *p_rnd = p_sk + 64 * n_pad;   // the secrets' pinned staging
-    uint8_t* out = w.rs_out.p;
-    uint8_t *d_vk = out, *d_sig = out + 32 * n_pad, *d_status = out + 96 * n_pad;
-    RsArgs a;
-    a.in = {(const uint32_t*)d_sk, h.alphas ? (const uint32_t*)d_al : nullptr, (const uint32_t*)d_sh, d_kind, (const uint32_t*)d_rnd};
-    a.state = (RsState*)w.rs_state.p;
+    if ((rc = w.rs.reserve(cc, sizeof(RsState))) || (rc = spend_table_ensure(w, s)) || (rc = output_table_ensure(w, s))) return rc;
+    RsArgs a;   // (the columns in RS_IN's and RS_OUT's order)
+    a.in.sks = cc.in<uint32_t>(h.sks), a.in.alphas = cc.in<uint32_t>(h.alphas), a.in.randoms = cc.in<uint32_t>(h.randoms);
+    a.in.sighashes = cc.in<uint32_t>(h.sighashes), a.in.kinds = cc.in(h.kinds);
+    a.state = (RsState*)w.rs.state.p;
     a.tab = {{(const JNiels*)w.sb_table.p, (const JNiels*)w.ob_table.p}};
-    a.status = d_status;
-    a.vks = (uint32_t*)d_vk;
-    a.sigs = (uint32_t*)d_sig;
-    Event ev[4];
-    if ((rc = create_events(ev))) return rc;
-    double ms[3] = {0, 0, 0};
-    for (size_t o = 0; o < n; o += cap) {
-        const size_t c = std::min(cap, n - o);
-        memcpy(p_sk, h.sks + 32 * o, 32 * c);
-        if (h.alphas) memcpy(p_al, h.alphas + 32 * o, 32 * c);
-        memcpy(p_rnd, h.randoms + 80 * o, 80 * c);
-        HIP_TRY(hipEventRecord(ev[0], s));
-        HIP_TRY(hipMemcpyAsync(d_sk, p_sk, 32 * c, hipMemcpyHostToDevice, s));
-        if (h.alphas) HIP_TRY(hipMemcpyAsync(d_al, p_al, 32 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_rnd, p_rnd, 80 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_sh, h.sighashes + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_kind, h.kinds + o, c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemsetAsync(out, 0, 96 * n_pad, s));   // a refused item's outputs are zeros
-        HIP_TRY(hipEventRecord(ev[1], s));
-        a.n = (uint32_t)c;
-        rs_enqueue(s, a);
-        HIP_TRY(hipEventRecord(ev[2], s));
-        HIP_TRY(hipMemcpyAsync(h.status + o, d_status, c, hipMemcpyDeviceToHost, s));
-        if (h.vks) HIP_TRY(hipMemcpyAsync(h.vks + 32 * o, d_vk, 32 * c, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h.sigs + 64 * o, d_sig, 64 * c, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipEventRecord(ev[3], s));
-        HIP_TRY(hipStreamSynchronize(s));   // the next chunk overwrites the buffers
-        if (launch_status() != MASP_HIP_OK) return MASP_HIP_E_HIP;   // a refused launch: the buffers mean nothing
-        if ((rc = add_elapsed(ev, 3, ms))) return rc;
-    }
-    w.rs_timing.store(ms);
-    return MASP_HIP_OK;
-}
-
-// What a call leaves of its secrets, on success and on every error path, before the wallet lock is released: the uploaded inputs (the
-// secret ones among them) and the per-item state on the device, the pinned staging on the host.  (A failed memset is not reported over the call's own result.)
-void scrub(hipStream_t s, DevBuf<uint8_t>& in, DevBuf<uint8_t>& state, PinnedBuf<uint8_t>& stage) {
-    if (in.p) (void)hipMemsetAsync(in.p, 0, in.cap, s);
-    if (state.p) (void)hipMemsetAsync(state.p, 0, state.cap, s);
-    (void)hipStreamSynchronize(s);
-    if (stage.p) memset(stage.p, 0, stage.cap);
+    a.vks = cc.out<uint32_t>(h.vks), a.sigs = cc.out<uint32_t>(h.sigs), a.status = cc.out(h.status);
+    return run_per_item(s, w.rs, cc, n, [&](size_t c) { a.n = (uint32_t)c, rs_enqueue(s, a); });
 }
 
 struct SbHost {
@@ -244,75 +200,25 @@ struct SbHost {
 int run_build_spends(masp_hip_ctx* ctx, size_t n, const SbHost& h) {
     WalletState& w = ctx->wallet;
     hipStream_t s = ctx->streams.vk[0];
-    const size_t cap = chunk_cap(w.sb_chunk.load(), n);
-    const size_t n_pad = (cap + SB_BLOCK - 1) / SB_BLOCK * SB_BLOCK;
+    ColumnCall cc(SB_IN, SB_OUT, column_chunk(w.sb.chunk.load(), SB_CHUNK, n));
     int rc;
-    if ((rc = w.sb_in.reserve(252 * n_pad)) || (rc = w.sb_state.reserve(sizeof(SbState) * n_pad)) || (rc = w.sb_out.reserve(161 * n_pad)) ||
-        (rc = w.sb_stage.reserve(96 * n_pad)))
+    if ((rc = w.sb.reserve(cc, sizeof(SbState))) || (rc = pedersen_table_ensure(w, s)) || (rc = nullifier_table_ensure(w, s)) ||
+        (rc = output_table_ensure(w, s)) || (rc = spend_table_ensure(w, s)))
         return rc;
-    if ((rc = pedersen_table_ensure(w, s)) || (rc = nullifier_table_ensure(w, s)) || (rc = output_table_ensure(w, s)) || (rc = spend_table_ensure(w, s)))
-        return rc;
-    uint8_t* in = w.sb_in.p;
-    uint8_t *d_nsk = in, *d_ar = in + 32 * n_pad, *d_rcv = in + 64 * n_pad, *d_ids = in + 96 * n_pad, *d_pk = in + 128 * n_pad, *d_rs = in + 160 * n_pad,
-            *d_ak = in + 192 * n_pad, *d_val = in + 224 * n_pad, *d_pos = in + 232 * n_pad, *d_div = in + 240 * n_pad, *d_lead = in + 251 * n_pad;
-    uint8_t *p_nsk = w.sb_stage.p, *p_ar = p_nsk + 32 * n_pad, *p_rcv = p_nsk + 64 * n_pad;
-    uint8_t* out = w.sb_out.p;
-    uint8_t *d_cv = out, *d_rk = out + 32 * n_pad, *d_nf = out + 64 * n_pad, *d_cmu = out + 96 * n_pad, *d_nk = out + 128 * n_pad, *d_status = out + 160 * n_pad;
-    SbArgs a;
-    a.in.note = {(const uint32_t*)d_ids, (const uint64_t*)d_val, d_div, (const uint32_t*)d_pk, d_lead, (const uint32_t*)d_rs, nullptr, (const uint64_t*)d_pos};
-    a.in.aks = (const uint32_t*)d_ak;
-    a.in.nsks = (const uint32_t*)d_nsk;
-    a.in.ars = (const uint32_t*)d_ar;
-    a.in.rcvs = (const uint32_t*)d_rcv;
-    a.state = (SbState*)w.sb_state.p;
+    SbArgs a;   // (the columns in SB_IN's and SB_OUT's order)
+    a.in.nsks = cc.in<uint32_t>(h.nsks), a.in.ars = cc.in<uint32_t>(h.ars), a.in.rcvs = cc.in<uint32_t>(h.rcvs);
+    a.in.note.ids = cc.in<uint32_t>(h.ids), a.in.note.pk_ds = cc.in<uint32_t>(h.pk_ds), a.in.note.rseeds = cc.in<uint32_t>(h.rseeds);
+    a.in.aks = cc.in<uint32_t>(h.aks), a.in.note.values = cc.in<uint64_t>(h.values), a.in.note.positions = cc.in<uint64_t>(h.positions);
+    a.in.note.diversifiers = cc.in(h.divs), a.in.note.leads = cc.in(h.leads);
+    a.in.note.nks = nullptr;
+    a.state = (SbState*)w.sb.state.p;
     a.ped = (const JNiels*)w.nsc_table.p;
     a.nft = (const JNiels*)w.nf_table.p;
     a.vcr = (const JNiels*)w.ob_table.p;
     a.sbt = (const JNiels*)w.sb_table.p;
-    a.status = d_status;
-    a.cvs = (uint32_t*)d_cv;
-    a.rks = (uint32_t*)d_rk;
-    a.nfs = (uint32_t*)d_nf;
-    a.cmus = (uint32_t*)d_cmu;
-    a.nks = (uint32_t*)d_nk;
-    Event ev[4];
-    if ((rc = create_events(ev))) return rc;
-    double ms[3] = {0, 0, 0};
-    for (size_t o = 0; o < n; o += cap) {
-        const size_t c = std::min(cap, n - o);
-        memcpy(p_nsk, h.nsks + 32 * o, 32 * c);
-        memcpy(p_ar, h.ars + 32 * o, 32 * c);
-        memcpy(p_rcv, h.rcvs + 32 * o, 32 * c);
-        HIP_TRY(hipEventRecord(ev[0], s));
-        HIP_TRY(hipMemcpyAsync(d_nsk, p_nsk, 32 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_ar, p_ar, 32 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_rcv, p_rcv, 32 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_ids, h.ids + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_pk, h.pk_ds + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_rs, h.rseeds + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_ak, h.aks + 32 * o, 32 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_val, h.values + o, 8 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_pos, h.positions + o, 8 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_div, h.divs + 11 * o, 11 * c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d_lead, h.leads + o, c, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemsetAsync(out, 0, 160 * n_pad, s));   // a refused spend's outputs are zeros
-        HIP_TRY(hipEventRecord(ev[1], s));
-        a.n = (uint32_t)c;
-        sb_enqueue(s, a);
-        HIP_TRY(hipEventRecord(ev[2], s));
-        HIP_TRY(hipMemcpyAsync(h.status + o, d_status, c, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h.cvs + 32 * o, d_cv, 32 * c, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h.rks + 32 * o, d_rk, 32 * c, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(h.nfs + 32 * o, d_nf, 32 * c, hipMemcpyDeviceToHost, s));
-        if (h.cmus) HIP_TRY(hipMemcpyAsync(h.cmus + 32 * o, d_cmu, 32 * c, hipMemcpyDeviceToHost, s));
-        if (h.nks) HIP_TRY(hipMemcpyAsync(h.nks + 32 * o, d_nk, 32 * c, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipEventRecord(ev[3], s));
-        HIP_TRY(hipStreamSynchronize(s));   // the next chunk overwrites the buffers
-        if (launch_status() != MASP_HIP_OK) return MASP_HIP_E_HIP;   // a refused launch: the buffers mean nothing
-        if ((rc = add_elapsed(ev, 3, ms))) return rc;
-    }
-    w.sb_timing.store(ms);
-    return MASP_HIP_OK;
+    a.cvs = cc.out<uint32_t>(h.cvs), a.rks = cc.out<uint32_t>(h.rks), a.nfs = cc.out<uint32_t>(h.nfs);
+    a.cmus = cc.out<uint32_t>(h.cmus), a.nks = cc.out<uint32_t>(h.nks), a.status = cc.out(h.status);
+    return run_per_item(s, w.sb, cc, n, [&](size_t c) { a.n = (uint32_t)c, sb_enqueue(s, a); });
 }
 
 }  // namespace
@@ -330,22 +236,12 @@ int masp_hip_redjubjub_sign_batch(masp_hip_ctx* ctx, size_t n, const uint8_t* sk
     (void)output_table();
     WalletCall call(ctx);
     const RsHost h = {sks, alphas, sighashes, kinds, randoms, status, vks_out, sigs_out};
-    const int rc = run_sign(call.ctx, n, h);
-    scrub(call.ctx->streams.vk[0], call.w.rs_in, call.w.rs_state, call.w.rs_stage);   // (waits for the stream: nothing of this call stays in flight)
-    return call.done(rc);
+    return call.done(end_per_item(call.ctx->streams.vk[0], call.w.rs, RS_IN, run_sign(call.ctx, n, h)));
 }
 
-int masp_hip_redjubjub_sign_configure(masp_hip_ctx* ctx, size_t chunk_items) {
-    if (!ctx || chunk_items > SB_CHUNK) return MASP_HIP_E_INVALID_ARG;
-    FIRST_DEVICE(ctx)->wallet.rs_chunk.store(chunk_items);
-    return MASP_HIP_OK;
-}
+int masp_hip_redjubjub_sign_configure(masp_hip_ctx* ctx, size_t chunk_items) { return per_item_configure(ctx, &WalletState::rs, chunk_items, SB_CHUNK); }
 
-int masp_hip_redjubjub_sign_last_timing(masp_hip_ctx* ctx, double ms[3]) {
-    if (!ctx || !ms) return MASP_HIP_E_INVALID_ARG;
-    FIRST_DEVICE(ctx)->wallet.rs_timing.load(ms);
-    return MASP_HIP_OK;
-}
+int masp_hip_redjubjub_sign_last_timing(masp_hip_ctx* ctx, double ms[3]) { return per_item_last_timing(ctx, &WalletState::rs, ms); }
 
 int masp_hip_sapling_build_spends(masp_hip_ctx* ctx, size_t n, const uint8_t* asset_identifiers, const uint64_t* values,
                                   const uint8_t* diversifiers, const uint8_t* pk_ds, const uint8_t* lead_bytes, const uint8_t* rseeds,
@@ -363,22 +259,12 @@ int masp_hip_sapling_build_spends(masp_hip_ctx* ctx, size_t n, const uint8_t* as
     WalletCall call(ctx);
     const SbHost h = {asset_identifiers, diversifiers, pk_ds, lead_bytes, rseeds, aks, nsks, ars, rcvs, values, positions,
                       status,            cvs_out,      rks_out, nfs_out,  cmus_out, nks_out};
-    const int rc = run_build_spends(call.ctx, n, h);
-    scrub(call.ctx->streams.vk[0], call.w.sb_in, call.w.sb_state, call.w.sb_stage);   // (waits for the stream: nothing of this call stays in flight)
-    return call.done(rc);
+    return call.done(end_per_item(call.ctx->streams.vk[0], call.w.sb, SB_IN, run_build_spends(call.ctx, n, h)));
 }
 
-int masp_hip_build_spends_configure(masp_hip_ctx* ctx, size_t chunk_spends) {
-    if (!ctx || chunk_spends > SB_CHUNK) return MASP_HIP_E_INVALID_ARG;
-    FIRST_DEVICE(ctx)->wallet.sb_chunk.store(chunk_spends);
-    return MASP_HIP_OK;
-}
+int masp_hip_build_spends_configure(masp_hip_ctx* ctx, size_t chunk_spends) { return per_item_configure(ctx, &WalletState::sb, chunk_spends, SB_CHUNK); }
 
-int masp_hip_build_spends_last_timing(masp_hip_ctx* ctx, double ms[3]) {
-    if (!ctx || !ms) return MASP_HIP_E_INVALID_ARG;
-    FIRST_DEVICE(ctx)->wallet.sb_timing.load(ms);
-    return MASP_HIP_OK;
-}
+int masp_hip_build_spends_last_timing(masp_hip_ctx* ctx, double ms[3]) { return per_item_last_timing(ctx, &WalletState::sb, ms); }
 
 }  // extern "C"
 #endif   // MASP_SB_KERNELS_ONLY

@@ -43,13 +43,15 @@ def test_sizes_against_the_host_twin_and_the_reference(ctx):
 def test_chunks_give_the_same_bytes(ctx):
     plans, want = R.batch(257)
     arrays = R.arrays(plans)
-    ctx.build_outputs_configure(64)     # five chunks, the last partial
-    try:
-        chunked = ctx.build_outputs(*arrays)
-    finally:
-        ctx.build_outputs_configure(0)
-    R.check(chunked, want)
-    _same(chunked, ctx.build_outputs(*arrays))
+    whole = ctx.build_outputs(*arrays)
+    for chunk in (64, 1, 128):
+        ctx.build_outputs_configure(chunk)     # 64: five chunks, the last partial
+        try:
+            chunked = ctx.build_outputs(*arrays)
+        finally:
+            ctx.build_outputs_configure(0)
+        R.check(chunked, want)
+        _same(chunked, whole)
 
 
 def test_null_memos_and_null_flags(ctx):
