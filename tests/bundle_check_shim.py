@@ -1,40 +1,23 @@
-"""Build of the test-only shim tests/native/bundle_check_dev.hip (device/bundle_check.hpp on the host: the per-item steps of
-masp_hip_sapling_check_bundles and a whole call, lane after lane), with the product's flags as device_shim.py reads them from the
-Makefile; rebuilt when it or a source it includes is newer than the library.  `HostContext` serves Context.check_bundles from it, with the
+"""The test-only shim tests/native/bundle_check_dev.hip (device/bundle_check.hpp on the host: the per-item steps of
+masp_hip_sapling_check_bundles and a whole call, lane after lane), with the product's flags as native_build.py reads them from the
+Makefile.  `HostContext` serves Context.check_bundles from it, with the
 proofs' statuses from the host library's `Proof::read`: BatchValidator.check_bundles runs over it without a GPU."""
 import ctypes as C
-import glob
-import os
-import subprocess
 
 import numpy as np
 
-import device_shim
+import native_build
 from masp_amd import hip as HIP
 from masp_amd import host as H
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "bundle_check_dev.hip")
-SO = os.path.join(HERE, "native", "_bundle_check_dev.so")
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "masp_amd", "csrc")
+UNIT = native_build.unit("bundle_check_dev")
 _lib = None
-
-
-def dependencies():
-    return [SRC, device_shim.MAKEFILE, os.path.join(ROOT, "include", "masp_hip.h")] + \
-        [p for pat in ("device/*.hpp", "device/*.h") for p in glob.glob(os.path.join(CSRC, pat))]
 
 
 def load():
     global _lib
     if _lib is None:
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in dependencies()):
-            flags = device_shim.makefile_flags()
-            tmp = SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call([device_shim.HIPCC] + flags + ["-shared", SRC, "-o", tmp])
-            os.replace(tmp, SO)
-        _lib = C.CDLL(SO)
+        _lib = native_build.load(UNIT)
         _lib.bcd_point.argtypes = [C.c_char_p, C.c_char_p]
         _lib.bcd_balance_term.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p]
         _lib.bcd_multipack.argtypes = [C.c_char_p, C.c_char_p]

@@ -1,37 +1,16 @@
-"""Build of the test-only shim tests/native/conversion_dev.hip (device/conversion.hpp on the host, and the product's conversion kernels for
-either lane width on the GPU), with the product's flags as device_shim.py reads them from the Makefile; rebuilt when it or a source it
-includes is newer than the library."""
+"""The test-only shim tests/native/conversion_dev.hip (device/conversion.hpp on the host, and the product's conversion kernels for
+either lane width on the GPU), with the product's flags as native_build.py reads them from the Makefile."""
 import ctypes as C
-import glob
-import os
-import subprocess
 
 import numpy as np
 
-import device_shim
+import native_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "conversion_dev.hip")
-SO = os.path.join(HERE, "native", "_conversion_dev.so")
-CSRC = os.path.join(os.path.dirname(HERE), "masp_amd", "csrc")
-_lib = None
-
-
-def dependencies():
-    return [SRC, device_shim.MAKEFILE, os.path.join(CSRC, "k_conversion.hip")] + \
-        [p for pat in ("device/*.hpp", "device/*.h", "host/*.h", "*.h") for p in glob.glob(os.path.join(CSRC, pat))]
+UNIT = native_build.unit("conversion_dev")
 
 
 def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in dependencies()):
-            flags = device_shim.makefile_flags()
-            tmp = SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call([device_shim.HIPCC] + flags + ["-shared", SRC, "-o", tmp])
-            os.replace(tmp, SO)
-        _lib = C.CDLL(SO)
-    return _lib
+    return native_build.load(UNIT)
 
 
 def _p(a):

@@ -1,23 +1,16 @@
-"""Build and loader of the test-only unit tests/native/groth16_dev.hip (the proof-assembly kernels of masp_amd/csrc/device/groth16.hpp, each
-launched on its own through the product's launch_* wrapper), with the product's flags as device_shim.py reads them from the Makefile; rebuilt
-when the unit or a file it includes is newer than the library.
+"""Loader of the test-only unit tests/native/groth16_dev.hip (the proof-assembly kernels of masp_amd/csrc/device/groth16.hpp, each
+launched on its own through the product's launch_* wrapper), with the product's flags as native_build.py reads them from the Makefile.
 Everything that goes in or comes out is plain: points as affine pairs of ints with None for the identity (tests/pyref.py), scalars as
 ints.  A point that stands for an MSM result or an assembly piece is a WithZ(point, z): it is uploaded as (x z^2, y z^3, z^2, z^3); a bare
 point means z = 1.  An XYZZ slot comes back as a point, or as POISON where it still holds the byte 0xA5 the unit filled it with; a slot
 that holds neither raises."""
 import collections
 import ctypes as C
-import glob
-import os
-import subprocess
 
-import device_shim
+import native_build
 from pyref import g1_unc, g2_unc
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "groth16_dev.hip")
-SO = os.path.join(HERE, "native", "_groth16_dev.so")
-CSRC = os.path.join(os.path.dirname(HERE), "masp_amd", "csrc")
+UNIT = native_build.unit("groth16_dev")
 _lib = None
 
 POISON = "poison"
@@ -25,25 +18,10 @@ WithZ = collections.namedtuple("WithZ", "p z")      # z: an int below p for G1, 
 TAB = 32 * 255
 
 
-def dependencies():
-    """the unit includes k_groth16.hip, and through it device/groth16.hpp (most of device/), launch.h and util.h"""
-    return [SRC, device_shim.MAKEFILE, os.path.join(os.path.dirname(HERE), "include", "masp_hip.h")] + \
-        [os.path.join(CSRC, f) for f in ("k_groth16.hip", "launch.h", "util.h")] + \
-        sorted(glob.glob(os.path.join(CSRC, "device", "*.hpp")) + glob.glob(os.path.join(CSRC, "device", "*.h")))
-
-
-def build_command(out=SO):
-    return [device_shim.HIPCC] + device_shim.makefile_flags() + ["-shared", SRC, "-o", out]
-
-
 def load():
     global _lib
     if _lib is None:
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in dependencies()):
-            tmp = SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call(build_command(tmp))
-            os.replace(tmp, SO)
-        _lib = C.CDLL(SO)
+        _lib = native_build.load(UNIT)
         _lib.g16_guard_slots.restype = C.c_uint32
         _lib.g16_tab_row_stride.restype = C.c_uint32
     return _lib

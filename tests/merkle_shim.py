@@ -1,29 +1,17 @@
-"""Build of the test-only shim tests/native/merkle_dev.hip (the commitment tree's device header on the host), with the product's flags as
-device_shim.py reads them from the Makefile; rebuilt when it or a header it includes is newer than the library."""
+"""The test-only shim tests/native/merkle_dev.hip (the commitment tree's device header on the host), with the product's flags as
+native_build.py reads them from the Makefile."""
 import ctypes as C
-import os
-import subprocess
 
-import device_shim
+import native_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "merkle_dev.hip")
-SO = os.path.join(HERE, "native", "_merkle_dev.so")
-CSRC = os.path.join(os.path.dirname(HERE), "masp_amd", "csrc")
-DEPS = [SRC] + [os.path.join(CSRC, "device", f) for f in ("merkle.hpp", "pedersen.hpp", "blake2b.hpp", "jubjub.hpp", "field.hpp", "consts.hpp")] + \
-    [os.path.join(CSRC, "host", f) for f in ("jubjub.h", "fr.h", "mont.h")]
+UNIT = native_build.unit("merkle_dev")
 _lib = None
 
 
 def load():
     global _lib
     if _lib is None:
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in DEPS):
-            flags = device_shim.makefile_flags()
-            tmp = SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call([device_shim.HIPCC] + flags + ["-shared", SRC, "-o", tmp])
-            os.replace(tmp, SO)
-        _lib = C.CDLL(SO)
+        _lib = native_build.load(UNIT)
         _lib.mkl_row_host.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         _lib.mkl_row_host.restype = None
     return _lib

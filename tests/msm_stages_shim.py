@@ -1,62 +1,28 @@
-"""Build and loader of the test-only unit tests/native/msm_stages_dev.hip (the MSM's stages, each through the product's own driver: the
-counting sort, the batch-affine bucket tree, the accumulation and the bucket tails), with the product's flags as device_shim.py reads them
-from the Makefile; rebuilt when the unit or a file it includes is newer than a library.  The unit is compiled once per curve, side by side —
+"""Loader of the test-only unit tests/native/msm_stages_dev.hip (the MSM's stages, each through the product's own driver: the
+counting sort, the batch-affine bucket tree, the accumulation and the bucket tails), with the product's flags as native_build.py reads them
+from the Makefile.  The unit is compiled once per curve, side by side —
 _msm_stages_dev_g1.so (the sort and G1) and _msm_stages_dev_g2.so (-DMST_G2) —: as one library it compiles for as long as the two after each
 other.  Measured: G1 81 s, G2 56 s, side by side 81 s (the two after each other 137 s).
 Everything that goes in or comes out is plain: scalars as Python ints, entry words and offsets as lists of ints, points as affine pairs of
 ints with the pair of zeros for the point at infinity (tests/msm_stage_models.py), on the wire as bellman uncompressed bytes."""
 import ctypes as C
-import glob
-import os
-import subprocess
 
 import numpy as np
 
-import device_shim
 import msm_stage_models as M
+import native_build
 from pyref import F1, F2, g1_unc, g2_unc
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "msm_stages_dev.hip")
-SO = {"g1": os.path.join(HERE, "native", "_msm_stages_dev_g1.so"), "g2": os.path.join(HERE, "native", "_msm_stages_dev_g2.so")}
-DEFINES = {"g1": [], "g2": ["-DMST_G2"]}
-CSRC = os.path.join(os.path.dirname(HERE), "masp_amd", "csrc")
+UNITS = {"g1": native_build.unit("msm_stages_dev", "_g1"), "g2": native_build.unit("msm_stages_dev", "_g2", ["-DMST_G2"])}
 _libs = {}
 
 
-def dependencies():
-    """the unit includes msm_impl.hpp, msm_acc_impl.hpp, msm_tree_impl.hpp and k_msm_sort.hip, and through them msm_host.h, util.h and device/"""
-    return [SRC, device_shim.MAKEFILE, os.path.join(os.path.dirname(HERE), "include", "masp_hip.h")] + \
-        [os.path.join(CSRC, f) for f in ("msm_impl.hpp", "msm_acc_impl.hpp", "msm_tree_impl.hpp", "msm_host.h", "k_msm_sort.hip", "util.h", "launch.h")] + \
-        sorted(glob.glob(os.path.join(CSRC, "device", "*.hpp")) + glob.glob(os.path.join(CSRC, "device", "*.h")))
-
-
-def build_command(curve, out):
-    return [device_shim.HIPCC] + device_shim.makefile_flags() + DEFINES[curve] + ["-shared", SRC, "-o", out]
-
-
-def build():
-    """both libraries, whichever is missing or older than a dependency, compiled side by side"""
-    newest = max(os.path.getmtime(p) for p in dependencies())
-    jobs = []
-    for curve, so in SO.items():
-        if not os.path.exists(so) or os.path.getmtime(so) < newest:
-            tmp = so + ".%d.tmp" % os.getpid()
-            jobs.append((subprocess.Popen(build_command(curve, tmp)), tmp, so))
-    failed = [so for proc, tmp, so in jobs if proc.wait() != 0]
-    assert not failed, failed
-    for proc, tmp, so in jobs:
-        os.replace(tmp, so)
-
-
 def load(curve):
-    if curve not in _libs:
-        build()
-        lib = C.CDLL(SO[curve])
-        if curve == "g1":
-            lib.mst_padded_entries.restype = C.c_uint64
-        getattr(lib, "mst_%s_tree_entries" % curve).restype = C.c_uint64
-        _libs[curve] = lib
+    if not _libs:
+        _libs.update(zip(UNITS, native_build.load_all(UNITS.values())))
+        _libs["g1"].mst_padded_entries.restype = C.c_uint64
+        for name, lib in _libs.items():
+            getattr(lib, "mst_%s_tree_entries" % name).restype = C.c_uint64
     return _libs[curve]
 
 

@@ -1,46 +1,26 @@
-"""Build and loader of the test-only units over doubled window rows: tests/native/msm_twin_host.hip (the geometry, host code only: needs no
+"""Loader of the test-only units over doubled window rows: tests/native/msm_twin_host.hip (the geometry, host code only: needs no
 device) and tests/native/msm_twin_dev.hip (the sort, the table, the accumulation and the tails through the product's drivers; once per
-curve, side by side, as tests/msm_stages_shim.py builds its unit), with the product's flags as device_shim.py reads them from the Makefile;
-rebuilt when a unit or a file it includes is newer than its library.  Everything that goes in or comes out is plain: Python ints, lists of
-ints, points as affine pairs with the pair of zeros for the point at infinity."""
+curve, side by side, as tests/msm_stages_shim.py builds its unit), with the product's flags as native_build.py reads them from the Makefile.
+Everything that goes in or comes out is plain: Python ints, lists of ints, points as affine pairs with the pair of zeros for the point at
+infinity."""
 import ctypes as C
-import glob
-import os
-import subprocess
 
 import numpy as np
 
-import device_shim
 import msm_stage_models as M
 import msm_twin_models as TM
+import native_build
 from pyref import F1, F2, g1_unc, g2_unc
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "masp_amd", "csrc")
-HOST_SRC = os.path.join(HERE, "native", "msm_twin_host.hip")
-HOST_SO = os.path.join(HERE, "native", "_msm_twin_host.so")
-SRC = os.path.join(HERE, "native", "msm_twin_dev.hip")
-SO = {"g1": os.path.join(HERE, "native", "_msm_twin_dev_g1.so"), "g2": os.path.join(HERE, "native", "_msm_twin_dev_g2.so")}
-DEFINES = {"g1": [], "g2": ["-DMTW_G2"]}
+HOST = native_build.unit("msm_twin_host")
+UNITS = {"g1": native_build.unit("msm_twin_dev", "_g1"), "g2": native_build.unit("msm_twin_dev", "_g2", ["-DMTW_G2"])}
 CURVES = {"g1": (F1, g1_unc, 96), "g2": (F2, g2_unc, 192)}
 _U32, _U64 = C.c_uint32, C.c_uint64
-_host = None
 _libs = {}
 
 
-def _stale(so, deps):
-    return not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(p) for p in deps)
-
-
 def load_host():
-    global _host
-    if _host is None:
-        if _stale(HOST_SO, [HOST_SRC, device_shim.MAKEFILE, os.path.join(CSRC, "device", "msm_geom.h")]):
-            tmp = HOST_SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call([device_shim.HIPCC] + device_shim.makefile_flags() + ["-shared", HOST_SRC, "-o", tmp])
-            os.replace(tmp, HOST_SO)
-        _host = C.CDLL(HOST_SO)
-    return _host
+    return native_build.load(HOST)
 
 
 def geom(c, twin=True):
@@ -63,37 +43,10 @@ def bucket(c, v):
     return 1 << mult.value, int(b)
 
 
-def dependencies():
-    return [SRC, device_shim.MAKEFILE, os.path.join(os.path.dirname(HERE), "include", "masp_hip.h")] + \
-        [os.path.join(CSRC, f) for f in ("msm_impl.hpp", "msm_acc_impl.hpp", "msm_host.h", "k_msm_sort.hip", "util.h")] + \
-        sorted(glob.glob(os.path.join(CSRC, "device", "*.hpp")) + glob.glob(os.path.join(CSRC, "device", "*.h")))
-
-
-def build_command(curve, out):
-    return [device_shim.HIPCC] + device_shim.makefile_flags() + DEFINES[curve] + ["-shared", SRC, "-o", out]
-
-
-def build():
-    """both device libraries, whichever is stale, compiled side by side"""
-    deps = dependencies()
-    jobs = []
-    for curve, so in SO.items():
-        if _stale(so, deps):
-            tmp = so + ".%d.tmp" % os.getpid()
-            jobs.append((subprocess.Popen(build_command(curve, tmp)), tmp, so))
-    failed = [so for proc, tmp, so in jobs if proc.wait() != 0]
-    assert not failed, failed
-    for proc, tmp, so in jobs:
-        os.replace(tmp, so)
-
-
 def load(curve):
-    if curve not in _libs:
-        build()
-        lib = C.CDLL(SO[curve])
-        if curve == "g1":
-            lib.mtw_padded_entries.restype = _U64
-        _libs[curve] = lib
+    if not _libs:
+        _libs.update(zip(UNITS, native_build.load_all(UNITS.values())))
+        _libs["g1"].mtw_padded_entries.restype = _U64
     return _libs[curve]
 
 

@@ -1,30 +1,15 @@
-"""Build of the test-only shim tests/native/note_crypto_dev.hip (the note scan's device headers on their own), with the product's
-flags as device_shim.py reads them from the Makefile; rebuilt when it or a header it includes is newer than the library."""
+"""The test-only shim tests/native/note_crypto_dev.hip (the note scan's device headers on their own), with the product's
+flags as native_build.py reads them from the Makefile."""
 import ctypes as C
-import os
-import subprocess
 
-import device_shim
+import native_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "note_crypto_dev.hip")
-SO = os.path.join(HERE, "native", "_note_crypto_dev.so")
-DEV = os.path.join(os.path.dirname(HERE), "masp_amd", "csrc", "device")
-DEPS = [SRC] + [os.path.join(DEV, f) for f in ("blake2b.hpp", "chacha20.hpp", "poly1305.hpp", "field.hpp", "consts.hpp")]
+UNIT = native_build.unit("note_crypto_dev")
 STRIDE = 160
-_lib = None
 
 
 def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in DEPS):
-            flags = device_shim.makefile_flags()
-            tmp = SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call([device_shim.HIPCC] + flags + ["-shared", SRC, "-o", tmp])
-            os.replace(tmp, SO)
-        _lib = C.CDLL(SO)
-    return _lib
+    return native_build.load(UNIT)
 
 
 def run(op, items, gpu):

@@ -1,36 +1,19 @@
-"""Build of the test-only shim tests/native/nullifier_dev.hip (device/nullifier.hpp on the host, and the product's nullifier kernels for
-either lane width on the GPU), with the product's flags as device_shim.py reads them from the Makefile; rebuilt when it or a source it
-includes is newer than the library."""
+"""The test-only shim tests/native/nullifier_dev.hip (device/nullifier.hpp on the host, and the product's nullifier kernels for
+either lane width on the GPU), with the product's flags as native_build.py reads them from the Makefile."""
 import ctypes as C
-import glob
-import os
-import subprocess
 
 import numpy as np
 
-import device_shim
+import native_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "nullifier_dev.hip")
-SO = os.path.join(HERE, "native", "_nullifier_dev.so")
-CSRC = os.path.join(os.path.dirname(HERE), "masp_amd", "csrc")
+UNIT = native_build.unit("nullifier_dev")
 _lib = None
-
-
-def dependencies():
-    return [SRC, device_shim.MAKEFILE, os.path.join(CSRC, "k_nullifier.hip")] + \
-        [p for pat in ("device/*.hpp", "device/*.h", "host/*.h", "*.h") for p in glob.glob(os.path.join(CSRC, pat))]
 
 
 def load():
     global _lib
     if _lib is None:
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in dependencies()):
-            flags = device_shim.makefile_flags()
-            tmp = SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call([device_shim.HIPCC] + flags + ["-shared", SRC, "-o", tmp])
-            os.replace(tmp, SO)
-        _lib = C.CDLL(SO)
+        _lib = native_build.load(UNIT)
         _lib.nfd_table_mul_host.argtypes = [C.c_int, C.c_char_p, C.c_char_p]
     return _lib
 

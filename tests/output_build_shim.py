@@ -1,38 +1,21 @@
-"""Build of the test-only shim tests/native/output_build_dev.hip (device/output_build.hpp on the host, and the product's output-building
-kernels on the GPU, one alone or all), with the product's flags as device_shim.py reads them from the Makefile; rebuilt when it or a
-source it includes is newer than the library."""
+"""The test-only shim tests/native/output_build_dev.hip (device/output_build.hpp on the host, and the product's output-building
+kernels on the GPU, one alone or all), with the product's flags as native_build.py reads them from the Makefile."""
 import ctypes as C
-import glob
-import os
-import subprocess
 
 import numpy as np
 
-import device_shim
+import native_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "output_build_dev.hip")
-SO = os.path.join(HERE, "native", "_output_build_dev.so")
-CSRC = os.path.join(os.path.dirname(HERE), "masp_amd", "csrc")
+UNIT = native_build.unit("output_build_dev")
 STAGES = ("parse", "memo", "commit", "cv", "ladder", "seal", "rows")     # stage k + 1 is kernel k_ob_<name>
 PARTS = ("state", "status", "cv", "cmu", "epk", "memo", "cols", "enc", "cout")
 _lib = None
 
 
-def dependencies():
-    return [SRC, device_shim.MAKEFILE, os.path.join(CSRC, "k_output_build.hip")] + \
-        [p for pat in ("device/*.hpp", "device/*.h", "host/*.h", "*.h") for p in glob.glob(os.path.join(CSRC, pat))]
-
-
 def load():
     global _lib
     if _lib is None:
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in dependencies()):
-            flags = device_shim.makefile_flags()
-            tmp = SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call([device_shim.HIPCC] + flags + ["-shared", SRC, "-o", tmp])
-            os.replace(tmp, SO)
-        _lib = C.CDLL(SO)
+        _lib = native_build.load(UNIT)
         _lib.obd_block_bytes.restype = C.c_size_t
         _lib.obd_block_bytes.argtypes = [C.c_uint32]
         _lib.obd_block_layout.argtypes = [C.c_uint32, C.c_void_p]

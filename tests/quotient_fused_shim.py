@@ -1,40 +1,21 @@
-"""Build of the test-only unit tests/native/quotient_fused_dev.hip (the evaluation-form quotient's three kernels, each on its own behind the
-product's launch wrapper, and the two whole chains), with the product's flags as device_shim.py reads them from the Makefile; rebuilt when it
-or a file it includes is newer than the library.  Scalars go in and come out as Python ints (canonical values), except in chains_gpu, which
-takes and returns numpy words as they lie in memory."""
+"""The test-only unit tests/native/quotient_fused_dev.hip (the evaluation-form quotient's three kernels, each on its own behind the
+product's launch wrapper, and the two whole chains), with the product's flags as native_build.py reads them from the Makefile.  Scalars go
+in and come out as Python ints (canonical values), except in chains_gpu, which takes and returns numpy words as they lie in memory."""
 import ctypes as C
-import glob
-import os
-import subprocess
 
 import numpy as np
 
-import device_shim
+import native_build
 from prove_stages_shim import MARKER, ints, words
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "quotient_fused_dev.hip")
-SO = os.path.join(HERE, "native", "_quotient_fused_dev.so")
-CSRC = os.path.join(os.path.dirname(HERE), "masp_amd", "csrc")
+UNIT = native_build.unit("quotient_fused_dev")
 _lib = None
-
-
-def dependencies():
-    """the unit includes k_ntt.hip, and through it device/ntt.hpp, device/r1cs.hpp, launch.h and util.h"""
-    return [SRC, device_shim.MAKEFILE, os.path.join(CSRC, "k_ntt.hip"), os.path.join(CSRC, "launch.h"), os.path.join(CSRC, "util.h"),
-            os.path.join(os.path.dirname(HERE), "include", "masp_hip.h")] + \
-        sorted(glob.glob(os.path.join(CSRC, "device", "*.hpp")) + glob.glob(os.path.join(CSRC, "device", "*.h")))
 
 
 def load():
     global _lib
     if _lib is None:
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in dependencies()):
-            flags = device_shim.makefile_flags()
-            tmp = SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call([device_shim.HIPCC] + flags + ["-shared", SRC, "-o", tmp])
-            os.replace(tmp, SO)
-        L = C.CDLL(SO)
+        L = native_build.load(UNIT)
         u32, u64, u8, p = C.c_uint32, C.c_uint64, C.c_uint8, C.c_void_p
         L.qf_fused_ok.argtypes = [u32]
         L.qf_tile_log.restype = u32

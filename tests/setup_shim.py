@@ -1,47 +1,26 @@
-"""Build and loader of the test-only unit tests/native/setup_dev.hip (the parameter-generation kernels of masp_amd/csrc/device/setup.hpp, the
-MSM tables' base import and the loader's single-point imports, each launched on its own), with the product's flags as device_shim.py reads
-them from the Makefile; rebuilt when the unit or a file it includes is newer than the library.
+"""Loader of the test-only unit tests/native/setup_dev.hip (the parameter-generation kernels of masp_amd/csrc/device/setup.hpp, the
+MSM tables' base import and the loader's single-point imports, each launched on its own), with the product's flags as native_build.py reads
+them from the Makefile.
 Everything that goes in or comes out is plain: scalars as ints below r, points as affine pairs of ints with None for the identity
 (tests/pyref.py), or as raw wire bytes where the encoding itself is under test.  Every function checks that the guard slots behind the
 kernel's output still hold the byte 0xA5 the unit filled them with."""
 import ctypes as C
-import glob
-import os
-import subprocess
 
-import device_shim
+import native_build
 from groth16_shim import g1_point, g2_point
 from pyref import g1_unc, g2_unc
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "setup_dev.hip")
-SO = os.path.join(HERE, "native", "_setup_dev.so")
-CSRC = os.path.join(os.path.dirname(HERE), "masp_amd", "csrc")
+UNIT = native_build.unit("setup_dev")
 _lib = None
 
 POISON, ZERO = "poison", "zero"
 TAB = 32 * 255
 
 
-def dependencies():
-    """the unit includes k_groth16.hip, device/setup.hpp and device/msm.hpp (through them most of device/), launch.h and util.h"""
-    return [SRC, device_shim.MAKEFILE, os.path.join(os.path.dirname(HERE), "include", "masp_hip.h")] + \
-        [os.path.join(CSRC, f) for f in ("k_groth16.hip", "launch.h", "util.h")] + \
-        sorted(glob.glob(os.path.join(CSRC, "device", "*.hpp")) + glob.glob(os.path.join(CSRC, "device", "*.h")))
-
-
-def build_command(out=SO):
-    return [device_shim.HIPCC] + device_shim.makefile_flags() + ["-shared", SRC, "-o", out]
-
-
 def load():
     global _lib
     if _lib is None:
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in dependencies()):
-            tmp = SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call(build_command(tmp))
-            os.replace(tmp, SO)
-        _lib = C.CDLL(SO)
+        _lib = native_build.load(UNIT)
         _lib.sd_guard_slots.restype = C.c_uint32
     return _lib
 

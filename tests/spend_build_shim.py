@@ -1,19 +1,12 @@
-"""Build of the test-only shim tests/native/spend_build_dev.hip (device/spend_build.hpp on the host, and the product's spend-building and
-signing kernels on the GPU, one alone or all), with the product's flags as device_shim.py reads them from the Makefile; rebuilt when it or
-a source it includes is newer than the library."""
+"""The test-only shim tests/native/spend_build_dev.hip (device/spend_build.hpp on the host, and the product's spend-building and
+signing kernels on the GPU, one alone or all), with the product's flags as native_build.py reads them from the Makefile."""
 import ctypes as C
-import glob
-import os
-import subprocess
 
 import numpy as np
 
-import device_shim
+import native_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "spend_build_dev.hip")
-SO = os.path.join(HERE, "native", "_spend_build_dev.so")
-CSRC = os.path.join(os.path.dirname(HERE), "masp_amd", "csrc")
+UNIT = native_build.unit("spend_build_dev")
 SIGN_STAGES = ("key", "nonce_hash", "nonce_point", "finish")     # stage k + 1 is kernel k_rs_<name>
 SIGN_PARTS = ("state", "status", "vk", "sig")
 SPEND_STAGES = ("parse", "keys", "commit", "cv", "finish")       # stage k + 1 is kernel k_sb_<name>
@@ -22,20 +15,10 @@ TABLES = {"spend": 0, "pgk": 1, "vcr": 2}
 _lib = None
 
 
-def dependencies():
-    return [SRC, device_shim.MAKEFILE, os.path.join(CSRC, "k_spend_build.hip")] + \
-        [p for pat in ("device/*.hpp", "device/*.h", "host/*.h", "*.h") for p in glob.glob(os.path.join(CSRC, pat))]
-
-
 def load():
     global _lib
     if _lib is None:
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in dependencies()):
-            flags = device_shim.makefile_flags()
-            tmp = SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call([device_shim.HIPCC] + flags + ["-shared", SRC, "-o", tmp])
-            os.replace(tmp, SO)
-        _lib = C.CDLL(SO)
+        _lib = native_build.load(UNIT)
         for f in (_lib.sbd_sign_block_bytes, _lib.sbd_spend_block_bytes):
             f.restype = C.c_size_t
             f.argtypes = [C.c_uint32]

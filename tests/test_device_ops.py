@@ -410,14 +410,19 @@ def test_shim_device_code_is_free_of_the_long_branch_hazard(tmp_path):
 
 
 def test_shim_is_built_with_the_product_flags():
-    """the shim's build command carries FLAGS of masp_amd/csrc/Makefile, in order, and stays a shared, position-independent library"""
+    """the build command of the shim, and of every other unit the *_shim modules declare, carries FLAGS of masp_amd/csrc/Makefile, in
+    order, and stays a shared, position-independent library; the shim's recorded dependencies are the headers it includes"""
     flags = device_shim.makefile_flags()
     assert "-O3" in flags and "-Wall" in flags and "--offload-arch=gfx950" in flags
-    cmd = device_shim.build_command()
-    i = cmd.index(flags[0])
-    assert cmd[i:i + len(flags)] == flags
-    assert "-shared" in cmd and "-fPIC" in cmd
-    assert not any(f.startswith("-O") and f != "-O3" for f in cmd)
-    deps = device_shim.dependencies()
+    units = device_shim.native_build.declared_units()
+    assert device_shim.UNIT in units and len(units) >= 22
+    for unit in units:
+        cmd = unit.command()
+        i = cmd.index(flags[0])
+        assert cmd[i:i + len(flags)] == flags, unit.so
+        assert "-shared" in cmd and "-fPIC" in cmd, unit.so
+        assert not any(f.startswith("-O") and f != "-O3" for f in cmd), unit.so
+    device_shim.load()
+    deps = device_shim.UNIT.dependencies()
     for h in ("field.hpp", "curve.hpp", "quad.hpp", "oct.hpp", "msm_tree.hpp", "msm_geom.h", "io.hpp", "consts.hpp", "fp28.hpp"):
         assert any(os.path.basename(d) == h for d in deps), h

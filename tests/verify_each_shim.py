@@ -1,34 +1,16 @@
-"""Build of the test-only unit tests/native/verify_each_dev.hip (k_final_exp and k_verify_acc of masp_hip_verify_each, each on its own,
-and a wrapper over the host's final exponentiation), in the manner of verify_shim.py: the product's flags, rebuilt when it or a header
-it includes is newer than the library, canonical values only (Fp12 as 12-tuples of ints, points as bellman uncompressed wire bytes)."""
+"""The test-only unit tests/native/verify_each_dev.hip (k_final_exp and k_verify_acc of masp_hip_verify_each, each on its own,
+and a wrapper over the host's final exponentiation), in the manner of verify_shim.py: the product's flags, canonical values only (Fp12
+as 12-tuples of ints, points as bellman uncompressed wire bytes)."""
 import ctypes as C
-import os
-import subprocess
 
-import device_shim
-import verify_shim
+import native_build
 from verify_shim import fp12_bytes, fp12_tuple
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "verify_each_dev.hip")
-SO = os.path.join(HERE, "native", "_verify_each_dev.so")
-_lib = None
-
-
-def dependencies():
-    csrc = verify_shim.CSRC
-    return [SRC] + verify_shim.dependencies()[1:] + [os.path.join(csrc, "host", f) for f in ("groth16_vk.h", "fr.h")]
+UNIT = native_build.unit("verify_each_dev")
 
 
 def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in dependencies()):
-            tmp = SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call([device_shim.HIPCC] + device_shim.makefile_flags() + ["-shared", SRC, "-o", tmp])
-            os.replace(tmp, SO)
-        _lib = C.CDLL(SO)
-    return _lib
+    return native_build.load(UNIT)
 
 
 def final_exp_gpu(vals):

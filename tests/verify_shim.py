@@ -1,39 +1,16 @@
-"""Build of the test-only unit tests/native/verify_dev.hip (the GPU batch verifier's kernels, each on its own, and wrappers over the host
-pairing), with the product's flags as device_shim.py reads them from the Makefile; rebuilt when it or a header it includes is newer than
-the library.  Everything that goes in or comes out is canonical: Fp as Python ints, Fp12 as 12-tuples in the host's flat coefficient
-order, points as bellman uncompressed wire bytes (pyref.g1_unc / g2_unc)."""
+"""The test-only unit tests/native/verify_dev.hip (the GPU batch verifier's kernels, each on its own, and wrappers over the host
+pairing), with the product's flags as native_build.py reads them from the Makefile.  Everything that goes in or comes out is canonical:
+Fp as Python ints, Fp12 as 12-tuples in the host's flat coefficient order, points as bellman uncompressed wire bytes (pyref.g1_unc /
+g2_unc)."""
 import ctypes as C
-import glob
-import os
-import subprocess
 
-import device_shim
+import native_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "verify_dev.hip")
-SO = os.path.join(HERE, "native", "_verify_dev.so")
-CSRC = os.path.join(os.path.dirname(HERE), "masp_amd", "csrc")
-_lib = None
-
-
-def dependencies():
-    """the unit includes device/pairing.hpp (and through it most of device/), host/pairing.h, host/pairing_prog.h, verify_launch.h, util.h"""
-    return [SRC, device_shim.MAKEFILE, os.path.join(CSRC, "verify_launch.h"), os.path.join(CSRC, "util.h"),
-            os.path.join(os.path.dirname(HERE), "include", "masp_hip.h")] + \
-        sorted(glob.glob(os.path.join(CSRC, "device", "*.hpp")) + glob.glob(os.path.join(CSRC, "device", "*.h"))) + \
-        [os.path.join(CSRC, "host", f) for f in ("pairing.h", "pairing_prog.h", "mont.h")]
+UNIT = native_build.unit("verify_dev")
 
 
 def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in dependencies()):
-            flags = device_shim.makefile_flags()
-            tmp = SO + ".%d.tmp" % os.getpid()
-            subprocess.check_call([device_shim.HIPCC] + flags + ["-shared", SRC, "-o", tmp])
-            os.replace(tmp, SO)
-        _lib = C.CDLL(SO)
-    return _lib
+    return native_build.load(UNIT)
 
 
 def fp12_bytes(f):
